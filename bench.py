@@ -676,6 +676,34 @@ def measure_mpc(api, rounds, device=0, workload="cartpole", batch=0):
         hs.close()
 
 
+DUMP_BYTES_MAX = 64 * 1000 * 1000   # --dump-outputs: all files together
+DUMP_SAMPLE_SEED = 20260928         # --dump-outputs: the trajectory sample when X / U do not fit
+
+
+def dump_outputs(out_dir, rec, res, X, U, lo):
+    """--dump-outputs: the arrays a caller of the timed path receives from its last step, as float64 .npy files -- the gathered
+    {final_objective, iterations, status} records of the whole batch (records_*), this rank's full result records (result_*) and its
+    trajectories X (B, N+1, nx), U (B, N, nu) with their global batch indices (trajectory_index).  When X and U would not fit into
+    DUMP_BYTES_MAX, a fixed seeded sample of the trajectories (sorted indices) is written instead; the inputs are seeded as well, so two
+    runs with the same arguments write comparable files."""
+    arrays = {}
+    for f in rec.dtype.names:
+        arrays["records_" + f] = rec[f]
+    for f in res.dtype.names:
+        arrays["result_" + f] = res[f]
+    B = X.shape[0]
+    fixed = sum(a.size for a in arrays.values()) * 8 + B * 8 + 4096 * (len(arrays) + 3)   # (+ the index array, + .npy headers)
+    per_traj = (X[0].size + U[0].size) * 8
+    n = max(0, min(B, (DUMP_BYTES_MAX - fixed) // per_traj))
+    idx = np.arange(B) if n == B else np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(B, n, replace=False))
+    arrays["trajectory_index"] = lo + idx
+    arrays["X"] = X[idx]
+    arrays["U"] = U[idx]
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -692,7 +720,14 @@ def main():
     ap.add_argument("--global-batch", type=int, default=0)
     ap.add_argument("--stackfed", action="store_true", help="only the stack-fed sweep lines (batch curves), one JSON line")
     ap.add_argument("--mpc", type=int, default=0, help="only the MPC re-solve measurement: K shift-and-re-solve rounds on a re-used handle (1 GPU), one JSON line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (result records, X / U of the trajectories) as DIR/<name>.npy "
+                         "in float64 (rank 0's shard under several GPUs; a fixed seeded sample of the trajectories when X / U exceed the size cap)")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
+    if args.dump_outputs and (args.stackfed or args.mpc > 0):
+        raise SystemExit("--dump-outputs applies to the batch-solve line, not to --stackfed / --mpc")
 
     import torch
     launched_by_torchrun = "RANK" in os.environ and "WORLD_SIZE" in os.environ
@@ -808,6 +843,7 @@ def main():
     # work counters of this rank's last step (identical work every step: same inputs)
     st = stats[-1]
     res = hs.results()
+    traj = hs.trajectory() if args.dump_outputs and rank == 0 else None   # the iterate the last timed solve left on the handle
     m = hs.m
     ipddp = args.solver == "ipddp"
     solve_ms = float(np.mean([s.solve_ms for s in stats]))
@@ -817,6 +853,8 @@ def main():
     assert np.array_equal(rec["iterations"][lo:hi], res["iterations"]) and np.array_equal(rec["status"][lo:hi], res["status"])
     gathered_converged = int(np.sum((rec["status"] == api.STATUS_OPTIMAL) | (rec["status"] == api.STATUS_ACCEPTABLE)))
     status_hist = {api.STATUS_STRINGS[int(s)]: int(c) for s, c in zip(*np.unique(res["status"], return_counts=True))}
+    if traj is not None:
+        dump_outputs(args.dump_outputs, rec, res, traj[0], traj[1], lo)
     total_traj = global_batch * args.steps
     out = {
         "metric": "trajectories_per_sec", "value": total_traj / dt_max, "unit": "trajectories/s",

@@ -16,9 +16,9 @@ def build_exe():
         g.build()
     os.makedirs(os.path.dirname(EXE), exist_ok=True)
     src = os.path.join(REPO, "tests", "cpp", "test_host_api.cpp")
-    if not os.path.exists(EXE) or os.path.getmtime(EXE) < max(os.path.getmtime(src), os.path.getmtime(lib)):
+    if not os.path.exists(EXE) or os.path.getmtime(EXE) < max(os.path.getmtime(src), os.path.getmtime(lib), os.path.getmtime(__file__)):   # (this file holds the link line)
         subprocess.check_call(["g++", "-std=c++17", "-O1", src, "-o", EXE, "-L" + os.path.dirname(lib), "-lcddp_hip",
-                               "-Wl,-rpath," + os.path.dirname(lib), "-L/opt/rocm/lib", "-Wl,-rpath,/opt/rocm/lib", "-lamdhip64"])
+                               "-Wl,-rpath,$ORIGIN/../lib", "-L/opt/rocm/lib", "-Wl,-rpath,/opt/rocm/lib", "-lamdhip64"])
     return EXE
 
 

@@ -43,6 +43,8 @@ def test_oracle_solvers_under_asan_ubsan():
     asan = subprocess.check_output(["gcc", "-print-file-name=libasan.so"], text=True).strip()
     if not os.path.isabs(asan) or not os.path.exists(asan):
         pytest.skip("libasan not found")
-    env = dict(os.environ, LD_PRELOAD=asan, CDDP_ORACLE_LIB=lib, ASAN_OPTIONS="detect_leaks=0:abort_on_error=1", UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
+    # libasan must come first; whatever the environment already preloads stays behind it
+    preload = " ".join(x for x in (asan, os.environ.get("LD_PRELOAD", "")) if x)
+    env = dict(os.environ, LD_PRELOAD=preload, CDDP_ORACLE_LIB=lib, ASAN_OPTIONS="detect_leaks=0:abort_on_error=1", UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
     r = subprocess.run([sys.executable, "-c", CHILD % {"repo": REPO}], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0 and "SANITIZED-OK" in r.stdout, (r.returncode, r.stdout[-2000:], r.stderr[-4000:])
