@@ -52,9 +52,9 @@ inline double clampd(double v, double lo, double hi) { return std::min(std::max(
 // keeps 1 (its callbacks serialise on the interpreter lock anyway).  Results do not depend on the count: every trajectory's arithmetic is
 // its own (tests/test_host_plugins.py::test_plugin_host_threads_do_not_change_results).
 int g_host_threads = -1;   // -1: unset (environment, then 1)
-// Time split of the LAST IPDDP / CLDDP plug-in solve of this process (cddp_hip_plugin_last_stats; bench.py's plug-in line): wall time of the
-// whole call, of the GPU sections (upload of the stacks, the sweep launch, download of the gains -- cddp_hip_set_stacks .. cddp_hip_stacks_get_*),
-// the sweeps' kernel time (hipEvents, cddp_hip_stacks_last_kernel_ms) and the batch sweeps run
+// Time split of the LAST plug-in solve of this process, any route (cddp_hip_plugin_last_stats; bench.py's plug-in line): wall time of the
+// outer loop, of the GPU sections (upload of the stacks, the sweep launch, download of the gains -- cddp_hip_set_stacks .. cddp_hip_stacks_get_*),
+// the sweeps' kernel time (hipEvents, cddp_hip_stacks_last_kernel_ms) and the batch sweeps run (BatchSweep::run fills it)
 struct PluginStats { double total_ms = 0, gpu_section_ms = 0, kernel_ms = 0; int sweeps = 0, threads = 1; };
 PluginStats g_last_stats;
 struct StatClock {
@@ -83,13 +83,18 @@ struct Trial {   // ForwardPassResult (cddp_core.hpp:105-145)
   std::vector<double> X, U, S, Y, G, Lam;
 };
 
-struct Traj {
-  std::vector<double> X, U, S, Y, G, Lam;
+struct TrajBase {   // what every route keeps per trajectory (the routes' own structs below set their initial values)
+  std::vector<double> X, U;
   double cost = 0, merit = 0, inf_pr = 0, inf_du = 0, inf_comp = 0, step_norm = 0, alpha_pr = 1.0, alpha_du = 1.0, reg = 0, mu = 0;
-  double dV0 = 0, dV1 = 0, phi = 0, theta = 0, filter_theta = 0, apr_max = 1.0, adu_max = 1.0;
-  std::vector<std::pair<double, double>> filter;   // (merit, violation)
+  double dV0 = 0, dV1 = 0;
   int iter = 0, status = CDDP_HIP_STATUS_RUNNING, n_bwd = 0, n_fwd = 0;
   bool done = false;
+};
+
+struct Traj : TrajBase {   // CLDDP / IPDDP
+  std::vector<double> S, Y, G, Lam;
+  double phi = 0, theta = 0, filter_theta = 0, apr_max = 1.0, adu_max = 1.0;
+  std::vector<std::pair<double, double>> filter;   // (merit, violation)
 };
 
 struct Ctx {
@@ -97,6 +102,7 @@ struct Ctx {
   const cddp_hip_options *o;
   int solver, nx, nu, m, N;
   double dt;
+  int threads;   // host threads of the per-trajectory work (1 on the LogDDP / MSIPDDP routes)
   std::vector<double> alphas;
   bool ipddp() const { return solver == CDDP_HIP_SOLVER_IPDDP; }
 };
@@ -109,14 +115,42 @@ double reg_increase(const cddp_hip_options &o, double r) {
 }
 double reg_decrease(const cddp_hip_options &o, double r) { r /= o.reg_update_factor; return std::max(r, o.reg_min_value); }
 
-// computeTheta / computeBarrierMerit / computePrimalAndComplementarity, constraint-major then t (ipddp_solver.cpp:2778-2937)
-void ip_reductions(const Ctx &c, const double *S, const double *Y, const double *G, double mu, double cost0,
-                   double &phi, double &theta, double &inf_pr, double &inf_comp) {
+struct TermInfo {   // the terminal-constraint set of ipddp_terminal_solve (kNoTerminal on the plain IPDDP route)
+  const cddp_hip_plugin_terminal *tc = nullptr;
+  int nobj = 0, rows = 0, mT = 0, pT = 0;
+  int dim[CDDP_HIP_PLUGIN_MAX_CONSTRAINTS], eq[CDDP_HIP_PLUGIN_MAX_CONSTRAINTS], src[CDDP_HIP_PLUGIN_MAX_CONSTRAINTS], dst[CDDP_HIP_PLUGIN_MAX_CONSTRAINTS];
+  // evaluate -> (g_T rows of the inequality objects in object order | h_T rows of the equality objects in object order) (+ Jacobian rows)
+  void eval(void *user, int nx, const double *xN, double *gT, double *GTx, double *hT, double *HT, std::vector<double> &r, std::vector<double> &rx) const {
+    if (!tc || rows == 0) return;
+    r.assign((size_t)rows, 0.0); rx.assign((size_t)rows * nx, 0.0);
+    tc->evaluate(user, xN, r.data(), (GTx || HT) ? rx.data() : nullptr);
+    for (int s = 0; s < nobj; ++s)
+      for (int i = 0; i < dim[s]; ++i) {
+        if (eq[s]) { if (hT) hT[dst[s] + i] = r[src[s] + i]; if (HT) std::copy(rx.begin() + (size_t)(src[s] + i) * nx, rx.begin() + (size_t)(src[s] + i + 1) * nx, HT + (size_t)(dst[s] + i) * nx); }
+        else { if (gT) gT[dst[s] + i] = r[src[s] + i]; if (GTx) std::copy(rx.begin() + (size_t)(src[s] + i) * nx, rx.begin() + (size_t)(src[s] + i + 1) * nx, GTx + (size_t)(dst[s] + i) * nx); }
+      }
+  }
+};
+const TermInfo kNoTerminal{};
+
+void repair_interior(const cddp_hip_options &o, double *s, double *y, int dim) {   // repairWarmstartInterior (:233-262), one constraint object
+  if (!o.ipddp_warmstart_repair || dim <= 0) return;
+  double mn = kInf, mny = kInf;
+  for (int i = 0; i < dim; ++i) { s[i] = std::max(s[i], o.ipddp_warmstart_s_min); mn = std::min(mn, s[i]); }
+  if (mn < o.ipddp_warmstart_s_min * o.ipddp_warmstart_interior_factor) for (int i = 0; i < dim; ++i) s[i] = s[i] * o.ipddp_warmstart_interior_factor;
+  for (int i = 0; i < dim; ++i) { y[i] = std::max(y[i], o.ipddp_warmstart_y_min); mny = std::min(mny, y[i]); }
+  if (mny < o.ipddp_warmstart_y_min * o.ipddp_warmstart_interior_factor) for (int i = 0; i < dim; ++i) y[i] = y[i] * o.ipddp_warmstart_interior_factor;
+}
+
+// computeTheta / computeBarrierMerit / computePrimalAndComplementarity (ipddp_solver.cpp:2778-2937): path objects (constraint-major, then t),
+// then the terminal-inequality objects, then the stacked terminal-equality residual (the terminal pointers are read only when ti has rows)
+void ip_reductions_t(const Ctx &c, const TermInfo &ti, const double *S, const double *Y, const double *G, const double *ST, const double *YT, const double *GT,
+                     const double *LamT, const double *hT, double mu, double cost0, double &phi, double &theta, double &inf_pr, double &inf_comp) {
   const int m = c.m, N = c.N;
   const bool l2 = c.o->ipddp_theta_norm_l2 != 0;
   double total = 0.0, max_entry = 0.0, ipr = 0.0, icomp = 0.0, mer = cost0;
   int off = 0;
-  for (int s = 0; s < c.pl->n_constraints; ++s) {
+  for (int s = 0; s < (m > 0 ? c.pl->n_constraints : 0); ++s) {
     const int dim = c.pl->constraint_dims[s];
     for (int t = 0; t < N; ++t) {
       double n1 = 0.0, ninf = 0.0;
@@ -125,14 +159,23 @@ void ip_reductions(const Ctx &c, const double *S, const double *Y, const double 
         const double r = G[j] + S[j];
         n1 += l2 ? r * r : std::fabs(r);
         ninf = std::max(ninf, std::fabs(r));
-        icomp = std::max(icomp, std::fabs(Y[j] * S[j] - mu));
       }
-      total += n1; max_entry = std::max(max_entry, ninf); ipr = std::max(ipr, ninf);
+      total += n1; max_entry = std::max(max_entry, ninf);
     }
     off += dim;
   }
+  for (int s = 0; s < ti.nobj; ++s) if (!ti.eq[s]) {
+    double n1 = 0.0, ninf = 0.0;
+    for (int i = 0; i < ti.dim[s]; ++i) { const double r = GT[ti.dst[s] + i] + ST[ti.dst[s] + i]; n1 += l2 ? r * r : std::fabs(r); ninf = std::max(ninf, std::fabs(r)); }
+    total += n1; max_entry = std::max(max_entry, ninf);
+  }
+  if (ti.pT > 0) {
+    double n1 = 0.0, ninf = 0.0;
+    for (int i = 0; i < ti.pT; ++i) { n1 += l2 ? hT[i] * hT[i] : std::fabs(hT[i]); ninf = std::max(ninf, std::fabs(hT[i])); }
+    total += n1; max_entry = std::max(max_entry, ninf);
+  }
   off = 0;
-  for (int s = 0; s < c.pl->n_constraints; ++s) {
+  for (int s = 0; s < (m > 0 ? c.pl->n_constraints : 0); ++s) {
     const int dim = c.pl->constraint_dims[s];
     for (int t = 0; t < N; ++t) {
       double ls = 0.0;
@@ -141,6 +184,24 @@ void ip_reductions(const Ctx &c, const double *S, const double *Y, const double 
     }
     off += dim;
   }
+  for (int s = 0; s < ti.nobj; ++s) if (!ti.eq[s]) {
+    double ls = 0.0;
+    for (int i = 0; i < ti.dim[s]; ++i) ls += std::log(std::max(ST[ti.dst[s] + i], kEpsSlack));
+    mer -= mu * ls;
+  }
+  if (ti.pT > 0) { double dp = 0.0; for (int i = 0; i < ti.pT; ++i) dp += LamT[i] * hT[i]; mer += dp; }
+  off = 0;
+  for (int s = 0; s < (m > 0 ? c.pl->n_constraints : 0); ++s) {
+    const int dim = c.pl->constraint_dims[s];
+    for (int t = 0; t < N; ++t)
+      for (int i = 0; i < dim; ++i) {
+        const size_t j = (size_t)t * m + off + i;
+        ipr = std::max(ipr, std::fabs(G[j] + S[j])); icomp = std::max(icomp, std::fabs(Y[j] * S[j] - mu));
+      }
+    off += dim;
+  }
+  for (int i = 0; i < ti.mT; ++i) { ipr = std::max(ipr, std::fabs(GT[i] + ST[i])); icomp = std::max(icomp, std::fabs(YT[i] * ST[i] - mu)); }
+  for (int i = 0; i < ti.pT; ++i) ipr = std::max(ipr, std::fabs(hT[i]));
   const double th = l2 ? std::sqrt(total) : total;
   theta = std::max(th, max_entry);
   phi = mer; inf_pr = ipr; inf_comp = icomp;
@@ -170,7 +231,6 @@ double total_cost(const Ctx &c, const double *X, const double *U) {   // CDDPSol
   return J;
 }
 
-void repair_interior(const cddp_hip_options &o, double *s, double *y, int dim);   // (defined with the terminal-constraint code below)
 // ---- ISolverAlgorithm::initialize ------------------------------------------------------------------------------------
 void initialize(const Ctx &c, Traj &T, const double *x0, const double *U0, const double *X0) {
   const int nx = c.nx, nu = c.nu, N = c.N, m = c.m;
@@ -226,8 +286,8 @@ void initialize(const Ctx &c, Traj &T, const double *x0, const double *U0, const
       off += dim;
     }
   }
-  double phi = cost, theta = 0.0, ipr = 0.0, icomp = 0.0;   // resetFilter (:2484-2519)
-  if (m > 0) ip_reductions(c, T.S.data(), T.Y.data(), T.G.data(), T.mu, cost, phi, theta, ipr, icomp);
+  double phi, theta, ipr, icomp;   // resetFilter (:2484-2519)
+  ip_reductions_t(c, kNoTerminal, T.S.data(), T.Y.data(), T.G.data(), nullptr, nullptr, nullptr, nullptr, nullptr, T.mu, cost, phi, theta, ipr, icomp);
   T.merit = T.phi = phi; T.inf_pr = ipr; T.inf_comp = icomp; T.inf_du = 0.0;
   T.filter_theta = std::max(theta, 1e-8);
   T.theta = std::max(T.filter_theta, std::max(o.ipddp_theta_0_floor, 1e-8));
@@ -320,8 +380,8 @@ Trial forward_ipddp(const Ctx &c, const Traj &T, const Gains &g, double alpha) {
     if (m > 0) c.pl->constraints(c.pl->user, x, u, t, r.G.data() + (size_t)t * m, nullptr, nullptr);
   }
   cost_new += c.pl->terminal_cost(c.pl->user, r.X.data() + (size_t)N * nx);
-  double phi_new = cost_new, theta_new = 0.0, ipr = 0.0, icomp = 0.0;
-  if (m > 0) ip_reductions(c, r.S.data(), r.Y.data(), r.G.data(), mu, cost_new, phi_new, theta_new, ipr, icomp);
+  double phi_new, theta_new, ipr, icomp;
+  ip_reductions_t(c, kNoTerminal, r.S.data(), r.Y.data(), r.G.data(), nullptr, nullptr, nullptr, nullptr, nullptr, mu, cost_new, phi_new, theta_new, ipr, icomp);
   if (!fin(phi_new) || !fin(theta_new) || !fin(ipr) || !fin(icomp)) return r;
   bool accept = false;
   if (m == 0) {   // :1785-1792
@@ -349,8 +409,8 @@ Trial forward_ipddp(const Ctx &c, const Traj &T, const Gains &g, double alpha) {
   return r;
 }
 
-// computeScaledDualInfeasibility (ipddp_solver.cpp:2725-2776): G_x of the last backward pass (kept per trajectory), Y current
-double scaled_inf_du(const Ctx &c, const Traj &T, const std::vector<double> &Gx) {
+// computeScaledDualInfeasibility (ipddp_solver.cpp:2725-2776): G_x of the last backward pass (the trajectory's slice of the batch stack), Y current
+double scaled_inf_du(const Ctx &c, const Traj &T, const double *Gx) {
   double v = T.inf_du;
   if (!c.o->ipddp_check_state_stationarity || c.m == 0) return v;
   double ss = 0.0;
@@ -368,6 +428,238 @@ double scaled_inf_du(const Ctx &c, const Traj &T, const std::vector<double> &Gx)
   return std::max(v, ss);
 }
 
+// ======================================================================================================================
+// The outer loop every route shares (cddp_solver_base.cpp:29-186): iteration head, one batch sweep on the GPU, the sweep-count replay and
+// the result records.  Each route fills the host stacks of its running trajectories, adds its own uploads (defects, terminal-equality
+// rows, control box) and runs BatchSweep::run; the forward passes and the updates stay per route.
+// ======================================================================================================================
+inline bool aborted(const cddp_hip_plugin *pl) { return pl->abort_flag && *pl->abort_flag != 0; }
+
+struct BatchSweep {
+  const Ctx &c;
+  const size_t B;
+  int rows = 0;   // path rows of the handle (0: the route's path constraints, if any, are folded or condensed on the host)
+  cddp_hip_stack_handle *h = nullptr;
+  // batch-major host stacks of the current iterates [b][t][...]: the LQ model, the dynamics Hessians (use_ilqr = false) and the path
+  // constraints (y, s, g, G_x, G_u with mc rows)
+  std::vector<double> fx, fu, lx, lu, lxx, luu, lux, VxN, VxxN, Fxx, Fuu, Fux, gy, gs, gg, gGx, gGu;
+  // results of the last sweep: gains, value function, dV, slack / dual gains and dX, per-trajectory scalars, ok flags
+  std::vector<double> Kb, kb, Vxb, Vxxb, dVb, kyb, Kyb, ksb, Ksb, dXb, s_reg, s_du, s_pr, s_comp, s_sn, s_apr, s_adu;
+  std::vector<double> regv, muv;
+  std::vector<int32_t> okv;
+  // K_u_ of each trajectory's LAST backward pass (the reference's solver object stops sweeping a problem when it ends; the batch keeps
+  // sweeping the others): the slice is kept at every sweep the trajectory still takes part in
+  std::vector<double> Kfin;
+
+  BatchSweep(const Ctx &ctx, int batch, int mc, bool hessians, bool keep_K) : c(ctx), B((size_t)batch) {
+    const size_t nx = c.nx, nu = c.nu, N = c.N, m = mc;
+    fx.resize(B * N * nx * nx); fu.resize(B * N * nx * nu); lx.resize(B * N * nx); lu.resize(B * N * nu); lxx.resize(B * N * nx * nx);
+    luu.resize(B * N * nu * nu); lux.resize(B * N * nu * nx); VxN.resize(B * nx); VxxN.resize(B * nx * nx);
+    if (hessians) { Fxx.resize(B * N * nx * nx * nx); Fuu.resize(B * N * nx * nu * nu); Fux.resize(B * N * nx * nu * nx); }
+    gy.resize(B * N * m); gs = gy; gg = gy; gGx.resize(B * N * m * nx); gGu.resize(B * N * m * nu);
+    Kb.resize(B * N * nu * nx); kb.resize(B * N * nu); Vxb.resize(B * (N + 1) * nx); Vxxb.resize(B * (N + 1) * nx * nx); dVb.resize(B * 2);
+    kyb.resize(B * N * m); ksb = kyb; Kyb.resize(B * N * m * nx); Ksb = Kyb; dXb.resize(B * (N + 1) * nx);
+    for (auto *v : {&s_reg, &s_du, &s_pr, &s_comp, &s_sn, &s_apr, &s_adu, &regv, &muv}) v->resize(B);
+    okv.resize(B);
+    if (keep_K) Kfin.resize(B * N * nu * nx);
+  }
+  ~BatchSweep() { if (h) cddp_hip_stacks_destroy(h); }
+  BatchSweep(const BatchSweep &) = delete;
+  BatchSweep &operator=(const BatchSweep &) = delete;
+  int open(int device, int handle_rows) { rows = handle_rows; return cddp_hip_stacks_create(device, (int)B, c.nx, c.nu, rows, c.N, &h); }
+
+  // upload -> backwardPass of the whole batch, incl. the "increase regularisation and retry" loop (cddp_solver_base.cpp:93-111) -> download;
+  // regularisation and barrier parameter (mu_floor where it is not positive) of every trajectory, running or not
+  template <class Tr> int run(int branch, const std::vector<Tr> &T, double mu_floor, bool hessians) {
+    for (size_t b = 0; b < B; ++b) {
+      regv[b] = T[b].done ? std::max(T[b].reg, c.o->reg_min_value) : T[b].reg;
+      muv[b] = (T[b].mu > 0.0) ? T[b].mu : mu_floor;
+    }
+    const StatClock gpu_clock;
+    int rc = cddp_hip_set_stacks(h, fx.data(), fu.data(), lx.data(), lu.data(), lxx.data(), luu.data(), lux.data(), VxN.data(), VxxN.data());
+    if (!rc && rows > 0) rc = cddp_hip_set_constraint_stacks(h, gy.data(), gs.data(), gg.data(), gGx.data(), gGu.data());
+    if (!rc && hessians) rc = cddp_hip_set_hessian_stacks(h, Fxx.data(), Fuu.data(), Fux.data());
+    if (!rc) rc = cddp_hip_stacks_backward(h, branch, c.o, regv.data(), rows > 0 ? muv.data() : nullptr, 1, okv.data());
+    if (!rc) rc = cddp_hip_stacks_get_gains(h, Kb.data(), kb.data(), Vxb.data(), Vxxb.data(), dVb.data());
+    if (!rc && rows > 0) rc = cddp_hip_stacks_get_constraint_gains(h, kyb.data(), Kyb.data(), ksb.data(), Ksb.data(), dXb.data());
+    if (!rc) rc = cddp_hip_stacks_get_scalars(h, s_reg.data(), s_du.data(), s_pr.data(), s_comp.data(), s_sn.data(), s_apr.data(), s_adu.data());
+    if (rc) return rc;
+    const size_t nK = (size_t)c.N * c.nu * c.nx;
+    if (!Kfin.empty()) for (size_t b = 0; b < B; ++b) if (!T[b].done) std::copy(Kb.begin() + b * nK, Kb.begin() + (b + 1) * nK, Kfin.begin() + b * nK);
+    g_last_stats.gpu_section_ms += gpu_clock.ms(); g_last_stats.kernel_ms += cddp_hip_stacks_last_kernel_ms(h); g_last_stats.sweeps += 1;
+    return 0;
+  }
+
+  // sweeps the retry loop ran for trajectory b: replay the schedule from the regularisation it started with; false when the schedule
+  // reached reg_max (the loop stops there: no sweep is run)
+  bool replay(TrajBase &t, size_t b) const {
+    int nb = 1; double r = t.reg;
+    while (r < s_reg[b] && nb < 64) { r = reg_increase(*c.o, r); ++nb; }
+    if (!okv[b] && nb > 1) --nb;
+    t.n_bwd += nb; t.reg = s_reg[b];
+    return okv[b] != 0;
+  }
+
+  // A = I + dt f_x, B = dt f_u (cddp_solver_base.cpp:319-394) and the cost derivatives (objective.hpp) of step s of trajectory b
+  void linearise(size_t b, int s, const double *x, const double *u, double *tfx, double *tfu) {
+    const int nx = c.nx, nu = c.nu;
+    const size_t bs = b * c.N + s;
+    c.pl->jacobians(c.pl->user, x, u, s * c.dt, tfx, tfu);
+    for (int i = 0; i < nx; ++i) for (int j = 0; j < nx; ++j) { double a = c.dt * tfx[i * nx + j]; if (i == j) a += 1.0; fx[(bs * nx + i) * nx + j] = a; }
+    for (int i = 0; i < nx * nu; ++i) fu[bs * nx * nu + i] = c.dt * tfu[i];
+    c.pl->running_cost_derivatives(c.pl->user, x, u, s, lx.data() + bs * nx, lu.data() + bs * nu, lxx.data() + bs * nx * nx, luu.data() + bs * nu * nu,
+                                   lux.data() + bs * nu * nx);
+  }
+  void scaled_hessians(size_t b, int s, const double *x, const double *u) {   // F_xx_[t][i] = dt f_xx[i] (cddp_solver_base.cpp:346-356)
+    const int nx = c.nx, nu = c.nu;
+    const size_t bs = b * c.N + s;
+    double *pxx = Fxx.data() + bs * nx * nx * nx, *puu = Fuu.data() + bs * nx * nu * nu, *pux = Fux.data() + bs * nx * nu * nx;
+    c.pl->hessians(c.pl->user, x, u, s * c.dt, pxx, puu, pux);
+    for (int e = 0; e < nx * nx * nx; ++e) pxx[e] = c.dt * pxx[e];
+    for (int e = 0; e < nx * nu * nu; ++e) puu[e] = c.dt * puu[e];
+    for (int e = 0; e < nx * nu * nx; ++e) pux[e] = c.dt * pux[e];
+  }
+};
+
+// head of an outer iteration (cddp_solver_base.cpp:77-90, whole elapsed milliseconds): 1 = run it; 0 = stop (every trajectory has ended, or
+// max_cpu_time is spent: the running ones end with MAX_CPU_TIME); < 0 = the caller's abort flag is set
+template <class Tr> int iteration_start(const Ctx &c, std::vector<Tr> &T, const StatClock &clock) {
+  bool any = false;
+  for (auto &t : T) any = any || !t.done;
+  if (!any) return 0;
+  if (aborted(c.pl)) return pfail(-50, "aborted by the caller (cddp_hip_plugin::abort_flag)");
+  if (c.o->max_cpu_time > 0.0) {
+    const double el_ms = (double)std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::steady_clock::now() - clock.t0).count();
+    if (el_ms > c.o->max_cpu_time * 1000.0) {
+      for (auto &t : T) if (!t.done) { t.iter += 1; t.status = CDDP_HIP_STATUS_MAX_CPU_TIME; t.done = true; }
+      return 0;
+    }
+  }
+  return 1;
+}
+
+// CDDPSolution fields (cddp_solver_base.cpp:161-171, ipddp_solver.cpp:2090-2097); feedback gains = K_u_ of the last sweep
+template <class Tr> void write_results(const Ctx &c, std::vector<Tr> &T, const BatchSweep &sw, const StatClock &clock, cddp_hip_result *results,
+                                       double *Xout, double *Uout, double *Kout) {
+  for (auto &t : T) if (!t.done) { t.status = CDDP_HIP_STATUS_MAX_ITERATIONS; t.done = true; }   // max_iterations <= 0
+  g_last_stats.total_ms = clock.ms();
+  if (Kout) std::copy(sw.Kfin.begin(), sw.Kfin.end(), Kout);
+  for (size_t b = 0; b < T.size(); ++b) {
+    const TrajBase &t = T[b];
+    cddp_hip_result &r = results[b];
+    std::memset(&r, 0, sizeof(r));
+    r.final_objective = t.cost; r.merit_function = t.merit; r.inf_pr = t.inf_pr; r.inf_du = t.inf_du; r.inf_comp = t.inf_comp;
+    r.barrier_mu = t.mu; r.regularization = t.reg; r.alpha_pr = t.alpha_pr; r.alpha_du = t.alpha_du; r.step_norm = t.step_norm;
+    r.iterations = t.iter; r.status = t.status; r.n_backward = t.n_bwd; r.n_forward = t.n_fwd;
+    if (Xout) std::copy(t.X.begin(), t.X.end(), Xout + b * (c.N + 1) * c.nx);
+    if (Uout) std::copy(t.U.begin(), t.U.end(), Uout + b * c.N * c.nu);
+  }
+}
+
+// performForwardPass (cddp_solver_base.cpp:248-317): the first successful trial, or (enable_parallel) the lowest merit among the successes
+template <class R, class F> bool line_search(const Ctx &c, TrajBase &t, R &best, F &&trial) {
+  const bool first_rule = !c.o->enable_parallel;
+  bool have = false;
+  int walked = 0;
+  for (double a : c.alphas) {
+    R r = trial(a);
+    ++walked;
+    if (!r.success) continue;
+    if (first_rule) { best = std::move(r); have = true; break; }
+    if (!have || r.merit < best.merit) { best = std::move(r); have = true; }
+  }
+  t.n_fwd += first_rule ? walked : (int)c.alphas.size();
+  return have;
+}
+
+// ---- IPDDP steps of the plain and the terminal route; has_barrier: path rows or terminal inequalities exist --------------------------
+bool ip_early_converged(const Ctx &c, const Traj &t, const double *Gx, bool has_barrier) {   // checkEarlyConvergence (ipddp_solver.cpp:925-958)
+  const cddp_hip_options &o = *c.o;
+  const double sdu = scaled_inf_du(c, t, Gx);
+  if (!has_barrier) return t.inf_pr < o.tolerance && sdu < o.tolerance;
+  const double tol = std::max(o.tolerance, o.ipddp_barrier_tol_mult * t.mu);
+  return t.inf_pr < tol && sdu < tol && t.inf_comp < tol && std::fabs(t.alpha_pr) * t.step_norm < o.tolerance * 10.0;
+}
+
+double ip_barrier_update(const Ctx &c, const Traj &t, const double *Gx, bool has_barrier) {   // updateBarrierParameters(true) (:2548-2660): the new mu
+  const cddp_hip_options &o = *c.o;
+  double mu = t.mu;
+  if (!has_barrier) return mu;
+  const double sdu = scaled_inf_du(c, t, Gx);
+  if (o.barrier_strategy == CDDP_HIP_BARRIER_ADAPTIVE) {
+    const double kkt = std::max(std::max(t.inf_pr, sdu), t.inf_comp);
+    const double threshold = std::max(o.barrier_mu_update_factor * mu, 2.0 * mu);
+    if (kkt <= threshold) {
+      double factor = o.barrier_mu_update_factor;
+      if (mu > 1e-20) {
+        const double ratio = kkt / std::max(mu, 1e-20);
+        if (ratio < 0.01) factor = 0.1 * o.barrier_mu_update_factor;
+        else if (ratio < 0.1) factor = 0.3 * o.barrier_mu_update_factor;
+        else if (ratio < 0.5) factor = 0.6 * o.barrier_mu_update_factor;
+      }
+      const double linear = factor * mu, superlinear = std::pow(mu, o.barrier_mu_update_power);
+      mu = std::max(std::min(linear, superlinear), std::max(o.barrier_mu_min_value, o.tolerance / 100.0));
+    }
+  } else {
+    const double kkt = std::max(std::max(t.inf_pr, sdu * o.ipddp_barrier_update_dual_weight), t.inf_comp);
+    if (kkt <= o.ipddp_mu_kappa_epsilon * mu) {
+      const double linear = o.barrier_mu_update_factor * mu, superlinear = std::pow(mu, o.barrier_mu_update_power);
+      mu = std::max(o.barrier_mu_min_value, std::min(linear, superlinear));
+    }
+  }
+  return mu;
+}
+
+// the filter after the barrier update (:2600-2660), from the merit terms of the accepted iterate at the new mu; a decrease of mu restarts the
+// filter, re-seeded with the iterate only when a terminal set exists (:2629-2637)
+void ip_filter_update(const cddp_hip_options &o, Traj &t, double mu_old, double phi, double theta, double ipr, double icomp, bool reseed) {
+  const double ftheta = std::max(theta, 1e-8);
+  if (t.mu < mu_old && t.mu > 0.0) { t.filter.clear(); if (reseed) filter_accept(t.filter, t.phi, ftheta); }
+  else { filter_accept(t.filter, t.phi, ftheta); if ((int)t.filter.size() > o.ipddp_max_filter_size) filter_prune(t.filter); }
+  t.inf_pr = ipr; t.inf_comp = icomp; t.merit = t.phi = phi; t.filter_theta = ftheta;
+  t.theta = std::max(ftheta, std::max(o.ipddp_theta_0_floor, 1e-8));
+}
+
+int ip_check_convergence(const Ctx &c, const Traj &t, const double *Gx, double dJ, bool has_barrier) {   // checkConvergence (:1953-2025)
+  const cddp_hip_options &o = *c.o;
+  const double sdu = scaled_inf_du(c, t, Gx);
+  const double pr = t.inf_pr, scomp = t.inf_comp, sn = t.step_norm;
+  if (!has_barrier) {
+    if (pr < o.tolerance && sdu < o.tolerance) return CDDP_HIP_STATUS_OPTIMAL;
+    if (o.acceptable_tolerance > 0.0) {
+      const double sq = std::sqrt(o.acceptable_tolerance);
+      bool acc = (pr < sq && sdu < sq && t.iter > 50);
+      if (dJ > 0.0) acc = acc || (dJ < o.acceptable_tolerance && t.iter > 50 && pr < sq && sdu < sq);
+      if (acc) return CDDP_HIP_STATUS_ACCEPTABLE;
+    }
+    return CDDP_HIP_STATUS_RUNNING;
+  }
+  const double tol = std::max(o.tolerance, o.ipddp_barrier_tol_mult * t.mu);
+  if (pr < tol && sdu < tol && scomp < tol && sn < o.tolerance * 10.0) return CDDP_HIP_STATUS_OPTIMAL;
+  if (o.acceptable_tolerance > 0.0) {
+    const double at = std::sqrt(o.acceptable_tolerance);
+    const double bat = std::max(o.barrier_mu_min_value * 100.0, o.tolerance / 10.0);
+    const bool akkt = pr < at && sdu < at && scomp < at, bpc = t.mu <= bat;
+    bool acc = akkt && bpc && t.iter > 10 && std::fabs(dJ) < o.acceptable_tolerance;
+    acc = acc || (akkt && bpc && t.iter >= 1 && sn < o.tolerance * 10.0 && pr < 1e-4);
+    if (acc) return CDDP_HIP_STATUS_ACCEPTABLE;
+  }
+  return CDDP_HIP_STATUS_RUNNING;
+}
+
+// handleForwardPassFailure (cddp_solver_base.cpp:206-218, ipddp_solver.cpp:2037-2082); twice: the second increase when a barrier and
+// terminal-equality rows coexist
+void ip_forward_failure(const Ctx &c, Traj &t, const double *Gx, bool has_barrier, bool twice) {
+  const cddp_hip_options &o = *c.o;
+  t.reg = reg_increase(o, t.reg);
+  if (twice) t.reg = reg_increase(o, t.reg);
+  if (t.reg < o.reg_max_value) return;
+  const double sdu = scaled_inf_du(c, t, Gx);
+  const double base = std::sqrt(std::max(o.acceptable_tolerance, o.tolerance));
+  const double at = has_barrier ? std::max(base, o.ipddp_barrier_tol_mult * t.mu) : base;
+  const bool acc = o.acceptable_tolerance > 0.0 && t.inf_pr < at && sdu < at && (!has_barrier || t.inf_comp < at);
+  t.status = acc ? CDDP_HIP_STATUS_ACCEPTABLE : CDDP_HIP_STATUS_REG_LIMIT; t.done = true;
+}
 
 // ======================================================================================================================
 // LogDDP (logddp_solver.cpp:43-707 on the CDDPSolverBase loop): single shooting; every path constraint enters through the relaxed
@@ -375,11 +667,9 @@ double scaled_inf_du(const Ctx &c, const Traj &T, const std::vector<double> &Gx)
 // derivative stacks here on the host; the GPU runs the unconstrained Riccati sweep of the batch (CDDP_HIP_STACKS_LOGDDP: Q_uu + reg I
 // symmetrised, LDLT, dV, inf_du = max |Q_u|).
 // ======================================================================================================================
-struct LTraj {
-  std::vector<double> X, U;
-  double cost = 0, merit = 0, violation = 0, inf_pr = 0, inf_du = kInf, alpha_pr = 1.0, reg = 0, mu = 0, dV0 = 0;
-  int iter = 0, status = CDDP_HIP_STATUS_RUNNING, n_bwd = 0, n_fwd = 0;
-  bool done = false;
+struct LTraj : TrajBase {
+  double violation = 0;
+  LTraj() { inf_du = kInf; }
 };
 
 void lg_beta(double z, double delta, double &b0, double &b1, double &b2) {   // calculate_beta_derivatives (barrier.hpp:274-296)
@@ -413,15 +703,12 @@ void lg_merit_terms(const Ctx &c, const double *X, const double *U, double mu, d
   }
 }
 
-inline bool aborted(const cddp_hip_plugin *pl) { return pl->abort_flag && *pl->abort_flag != 0; }
-
 int logddp_solve(const Ctx &c, int device, int batch, const double *x0, const double *U0, cddp_hip_result *results, double *Xout, double *Uout, double *Kout) {
   const cddp_hip_plugin *pl = c.pl; const cddp_hip_options &o = *c.o;
   const int nx = c.nx, nu = c.nu, m = c.m, N = c.N; const double dt = c.dt;
   const size_t B = (size_t)batch;
-  cddp_hip_stack_handle *sh = nullptr;
-  { int rc = cddp_hip_stacks_create(device, batch, nx, nu, 0, N, &sh); if (rc) return rc; }
-  struct Guard { cddp_hip_stack_handle *h; ~Guard() { if (h) cddp_hip_stacks_destroy(h); } } guard{sh};
+  BatchSweep sw(c, batch, 0, !o.use_ilqr, Kout != nullptr);
+  { int rc = sw.open(device, 0); if (rc) return rc; }
   std::vector<double> alphas;   // logddp_solver.cpp:171-177: the plain geometric ladder
   { double a = o.ls_initial_step_size; for (int i = 0; i < o.ls_max_iterations; ++i) { alphas.push_back(a); a *= o.ls_step_reduction_factor; } }
   const double delta = o.logddp_relaxed_delta;
@@ -441,44 +728,25 @@ int logddp_solve(const Ctx &c, int device, int batch, const double *x0, const do
     t.merit = t.cost + bar; t.violation = viol; t.inf_pr = viol;
   }
 
-  std::vector<double> fx(B * N * nx * nx), fu(B * N * nx * nu), lx(B * N * nx), lu(B * N * nu), lxx(B * N * nx * nx), luu(B * N * nu * nu),
-      lux(B * N * nu * nx), VxN(B * nx), VxxN(B * nx * nx), Fxx, Fuu, Fux;
-  if (!o.use_ilqr) { Fxx.resize(B * N * nx * nx * nx); Fuu.resize(B * N * nx * nu * nu); Fux.resize(B * N * nx * nu * nx); }
-  std::vector<double> Kb(B * N * nu * nx), kb(B * N * nu), Vxb(B * (N + 1) * nx), Vxxb(B * (N + 1) * nx * nx), dVb(B * 2);
-  // K_u_ of each trajectory's LAST backward pass (the reference's solver object stops sweeping a problem when it ends; the batch keeps
-  // sweeping the others): the slice is kept at every sweep the trajectory still takes part in
-  std::vector<double> Kfin(Kout ? B * N * nu * nx : 0, 0.0);
-  std::vector<double> regv(B), s_reg(B), s_du(B), s_pr(B), s_comp(B), s_sn(B), s_apr(B), s_adu(B);
-  std::vector<int32_t> okv(B);
   std::vector<double> tfx(nx * nx), tfu(nx * nu), g(std::max(m, 1)), Gx((size_t)std::max(m, 1) * nx), Gu((size_t)std::max(m, 1) * nu);
   std::vector<double> Cxx, Cuu, Cux;
   if (m > 0 && pl->constraint_hessians) { Cxx.resize((size_t)m * nx * nx); Cuu.resize((size_t)m * nu * nu); Cux.resize((size_t)m * nu * nx); }
   std::vector<double> Xn((size_t)(N + 1) * nx), Un((size_t)N * nu), Xb, Ub;
   const bool first_rule = !o.enable_parallel;
-  const auto wall0 = std::chrono::steady_clock::now();
+  const StatClock clock;
 
   for (int it = 1; it <= o.max_iterations; ++it) {
-    bool any = false;
-    for (auto &t : T) any = any || !t.done;
-    if (!any) break;
-    if (aborted(pl)) return pfail(-50, "aborted by the caller (cddp_hip_plugin::abort_flag)");
-    if (o.max_cpu_time > 0.0) {
-      const double el_ms = (double)std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::steady_clock::now() - wall0).count();
-      if (el_ms > o.max_cpu_time * 1000.0) { for (auto &t : T) if (!t.done) { t.iter += 1; t.status = CDDP_HIP_STATUS_MAX_CPU_TIME; t.done = true; } break; }
-    }
+    { const int go = iteration_start(c, T, clock); if (go < 0) return go; if (!go) break; }
     for (size_t b = 0; b < B; ++b) {
       LTraj &t = T[b];
-      regv[b] = t.done ? std::max(t.reg, o.reg_min_value) : t.reg;
       if (t.done) continue;
       t.iter += 1;
       for (int s = 0; s < N; ++s) {
         const double *x = t.X.data() + (size_t)s * nx, *u = t.U.data() + (size_t)s * nu;
         const size_t bs = b * N + s;
-        pl->jacobians(pl->user, x, u, s * dt, tfx.data(), tfu.data());
-        for (int i = 0; i < nx; ++i) for (int j = 0; j < nx; ++j) { double a = dt * tfx[i * nx + j]; if (i == j) a += 1.0; fx[(bs * nx + i) * nx + j] = a; }
-        for (int i = 0; i < nx * nu; ++i) fu[bs * nx * nu + i] = dt * tfu[i];
-        double *plx = lx.data() + bs * nx, *plu = lu.data() + bs * nu, *plxx = lxx.data() + bs * nx * nx, *pluu = luu.data() + bs * nu * nu, *plux = lux.data() + bs * nu * nx;
-        pl->running_cost_derivatives(pl->user, x, u, s, plx, plu, plxx, pluu, plux);
+        sw.linearise(b, s, x, u, tfx.data(), tfu.data());
+        double *plx = sw.lx.data() + bs * nx, *plu = sw.lu.data() + bs * nu, *plxx = sw.lxx.data() + bs * nx * nx, *pluu = sw.luu.data() + bs * nu * nu,
+               *plux = sw.lux.data() + bs * nu * nx;
         if (m > 0) {   // getGradients / getHessians of every constraint (barrier.hpp:95-213), scaled by the barrier coefficient, folded in
           pl->constraints(pl->user, x, u, s, g.data(), Gx.data(), Gu.data());
           if (!Cxx.empty()) {
@@ -501,34 +769,19 @@ int logddp_solve(const Ctx &c, int device, int batch, const double *x0, const do
             }
           }
         }
-        if (!o.use_ilqr) {
-          double *pxx = Fxx.data() + bs * nx * nx * nx, *puu = Fuu.data() + bs * nx * nu * nu, *pux = Fux.data() + bs * nx * nu * nx;
-          pl->hessians(pl->user, x, u, s * dt, pxx, puu, pux);
-          for (int e = 0; e < nx * nx * nx; ++e) pxx[e] = dt * pxx[e];
-          for (int e = 0; e < nx * nu * nu; ++e) puu[e] = dt * puu[e];
-          for (int e = 0; e < nx * nu * nx; ++e) pux[e] = dt * pux[e];
-        }
+        if (!o.use_ilqr) sw.scaled_hessians(b, s, x, u);
       }
-      pl->terminal_cost_derivatives(pl->user, t.X.data() + (size_t)N * nx, VxN.data() + b * nx, VxxN.data() + b * nx * nx);
+      pl->terminal_cost_derivatives(pl->user, t.X.data() + (size_t)N * nx, sw.VxN.data() + b * nx, sw.VxxN.data() + b * nx * nx);
     }
-    { int rc = cddp_hip_set_stacks(sh, fx.data(), fu.data(), lx.data(), lu.data(), lxx.data(), luu.data(), lux.data(), VxN.data(), VxxN.data()); if (rc) return rc; }
-    if (!o.use_ilqr) { int rc = cddp_hip_set_hessian_stacks(sh, Fxx.data(), Fuu.data(), Fux.data()); if (rc) return rc; }
-    { int rc = cddp_hip_stacks_backward(sh, CDDP_HIP_STACKS_LOGDDP, c.o, regv.data(), nullptr, 1, okv.data()); if (rc) return rc; }
-    { int rc = cddp_hip_stacks_get_gains(sh, Kb.data(), kb.data(), Vxb.data(), Vxxb.data(), dVb.data()); if (rc) return rc; }
-    if (Kout) for (size_t b = 0; b < B; ++b) if (!T[b].done) std::copy(Kb.begin() + b * N * nu * nx, Kb.begin() + (b + 1) * N * nu * nx, Kfin.begin() + b * N * nu * nx);
-    { int rc = cddp_hip_stacks_get_scalars(sh, s_reg.data(), s_du.data(), s_pr.data(), s_comp.data(), s_sn.data(), s_apr.data(), s_adu.data()); if (rc) return rc; }
+    { int rc = sw.run(CDDP_HIP_STACKS_LOGDDP, T, 1.0, !o.use_ilqr); if (rc) return rc; }
 
     for (size_t b = 0; b < B; ++b) {
       LTraj &t = T[b];
       if (t.done) continue;
       if (aborted(pl)) return pfail(-50, "aborted by the caller (cddp_hip_plugin::abort_flag)");
-      { int nb = 1; double r = t.reg; while (r < s_reg[b] && nb < 64) { r = reg_increase(o, r); ++nb; }
-        if (!okv[b] && nb > 1) --nb;
-        t.n_bwd += nb; }
-      t.reg = s_reg[b];
-      if (!okv[b]) { t.status = CDDP_HIP_STATUS_REG_LIMIT_CONVERGED; t.done = true; continue; }   // handleBackwardPassRegularizationLimit (:216-222)
-      t.dV0 = dVb[b * 2]; t.inf_du = s_du[b];
-      const double *K = Kb.data() + b * N * nu * nx, *k = kb.data() + b * N * nu;
+      if (!sw.replay(t, b)) { t.status = CDDP_HIP_STATUS_REG_LIMIT_CONVERGED; t.done = true; continue; }   // handleBackwardPassRegularizationLimit (:216-222)
+      t.dV0 = sw.dVb[b * 2]; t.inf_du = sw.s_du[b];
+      const double *K = sw.Kb.data() + b * N * nu * nx, *k = sw.kb.data() + b * N * nu;
       // ---- performForwardPass over forwardPass(alpha) (:594-707)
       bool have = false; double best_cost = 0, best_merit = kInf, best_viol = 0, best_alpha = 0; int walked = 0;
       for (double a : alphas) {
@@ -580,17 +833,9 @@ int logddp_solve(const Ctx &c, int device, int batch, const double *x0, const do
       if (it == o.max_iterations) { t.status = CDDP_HIP_STATUS_MAX_ITERATIONS; t.done = true; }
     }
   }
-  for (auto &t : T) if (!t.done) { t.status = CDDP_HIP_STATUS_MAX_ITERATIONS; t.done = true; }
-  if (Kout) std::copy(Kfin.begin(), Kfin.end(), Kout);
-  for (size_t b = 0; b < B; ++b) {   // CDDPSolution (+ populateSolverSpecificSolution :286-291)
-    const LTraj &t = T[b];
-    cddp_hip_result &r = results[b];
-    std::memset(&r, 0, sizeof(r));
-    r.final_objective = t.cost; r.merit_function = t.merit; r.inf_pr = t.violation; r.inf_du = t.inf_du; r.inf_comp = kInf;
-    r.barrier_mu = t.mu; r.regularization = t.reg; r.alpha_pr = t.alpha_pr; r.alpha_du = 0.0;
-    r.iterations = t.iter; r.status = t.status; r.n_backward = t.n_bwd; r.n_forward = t.n_fwd;
-    if (Xout) std::copy(t.X.begin(), t.X.end(), Xout + b * (N + 1) * nx);
-    if (Uout) std::copy(t.U.begin(), t.U.end(), Uout + b * N * nu);
+  write_results(c, T, sw, clock, results, Xout, Uout, Kout);
+  for (size_t b = 0; b < B; ++b) {   // populateSolverSpecificSolution (:286-291)
+    results[b].inf_pr = T[b].violation; results[b].inf_comp = kInf; results[b].alpha_du = 0.0;
   }
   return 0;
 }
@@ -604,13 +849,10 @@ int logddp_solve(const Ctx &c, int device, int batch, const double *x0, const do
 // convergence tests on the host.  use_ilqr = false: the costate-weighted dynamics Hessians and the dual-weighted constraint
 // Hessians (:1151-1163, 1279-1310) are folded into the cost-Hessian stacks (last-bit association difference against the reference's
 // "Q += ..." after the A^T V A products; the tests hold that case to 1e-9, not to equality).
-struct MTraj {
-  std::vector<double> X, U, F, Lam, S, Y, G;
+struct MTraj : TrajBase {
+  std::vector<double> F, Lam, S, Y, G;
   std::vector<std::pair<double, double>> filter;
-  double cost = kInf, merit = kInf, inf_pr = kInf, inf_du = kInf, inf_comp = kInf, step_norm = 0, alpha_pr = 1.0, alpha_du = 0.0, reg = 0, mu = 0;
-  double dV0 = 0, dV1 = 0;
-  int iter = 0, status = CDDP_HIP_STATUS_RUNNING, n_bwd = 0, n_fwd = 0;
-  bool done = false;
+  MTraj() { cost = merit = inf_pr = inf_du = inf_comp = kInf; alpha_du = 0.0; }
 };
 
 void ms_reset_filter(const Ctx &c, MTraj &t) {   // resetBarrierFilter :711-763
@@ -687,10 +929,9 @@ int msipddp_solve(const Ctx &c, int device, int batch, const double *x0, const d
     return pfail(-3, "MSIPDDP with path constraints is only defined for nu = 1 or nx = nu: the reference adds an (nx x nu) product to its (nu x nx) block Q_ux (msipddp_solver.cpp:1398); got nx = %d, nu = %d", nx, nu);
   if (o.msipddp_segment_length < 0) return pfail(-2, "MSIPDDP: ms_segment_length must be non-negative");
   if (!o.use_ilqr && m > 0 && !pl->constraint_hessians) return pfail(-3, "MSIPDDP with use_ilqr=false needs the constraint Hessian callback");
-  cddp_hip_stack_handle *sh = nullptr;
-  { int rc = cddp_hip_stacks_create(device, batch, nx, nu, m, N, &sh); if (rc) return rc; }
-  struct Guard { cddp_hip_stack_handle *h; ~Guard() { if (h) cddp_hip_stacks_destroy(h); } } guard{sh};
-  if (m == 0) { int rc = cddp_hip_stacks_factor_cache(sh, 1); if (rc) return rc; }
+  BatchSweep sw(c, batch, m, false, Kout != nullptr);
+  { int rc = sw.open(device, m); if (rc) return rc; }
+  if (m == 0) { int rc = cddp_hip_stacks_factor_cache(sw.h, 1); if (rc) return rc; }
   const int seg = o.msipddp_segment_length, rtype = o.msipddp_rollout_type;
   std::vector<double> alphas;
   { double a = o.ls_initial_step_size; for (int i = 0; i < o.ls_max_iterations; ++i) { alphas.push_back(a); a *= o.ls_step_reduction_factor; } }
@@ -745,17 +986,7 @@ int msipddp_solve(const Ctx &c, int device, int batch, const double *x0, const d
     ms_reset_filter(c, t);
   }
 
-  std::vector<double> fx(B * N * nx * nx), fu(B * N * nx * nu), lx(B * N * nx), lu(B * N * nu), lxx(B * N * nx * nx), luu(B * N * nu * nu),
-      lux(B * N * nu * nx), VxN(B * nx), VxxN(B * nx * nx), dfc(B * N * nx);
-  std::vector<double> ys(B * N * m), ss(B * N * m), gs(B * N * m), Gxs(B * N * m * nx), Gus(B * N * m * nu);
-  std::vector<double> Kb(B * N * nu * nx), kb(B * N * nu), Vxb(B * (N + 1) * nx), Vxxb(B * (N + 1) * nx * nx), dVb(B * 2);
-  // K_u_ of each trajectory's LAST backward pass (the reference's solver object stops sweeping a problem when it ends; the batch keeps
-  // sweeping the others): the slice is kept at every sweep the trajectory still takes part in
-  std::vector<double> Kfin(Kout ? B * N * nu * nx : 0, 0.0);
-  std::vector<double> kyb(B * N * m), Kyb(B * N * m * nx), ksb(B * N * m), Ksb(B * N * m * nx), dXb(m > 0 ? B * (N + 1) * nx : 0);
-  std::vector<double> regv(B), muv(B), s_reg(B), s_du(B), s_pr(B), s_comp(B), s_sn(B), s_apr(B), s_adu(B);
-  std::vector<int32_t> okv(B);
-  std::vector<double> tfx(nx * nx), tfu(nx * nu), Hxx, Huu, Hux, Cxx, Cuu, Cux, gtmp(std::max(m, 1));
+  std::vector<double> dfc(B * N * nx), tfx(nx * nx), tfu(nx * nu), Hxx, Huu, Hux, Cxx, Cuu, Cux, gtmp(std::max(m, 1));
   if (!o.use_ilqr) {
     Hxx.resize((size_t)nx * nx * nx); Huu.resize((size_t)nx * nu * nu); Hux.resize((size_t)nx * nu * nx);
     if (m > 0) { Cxx.resize((size_t)m * nx * nx); Cuu.resize((size_t)m * nu * nu); Cux.resize((size_t)m * nu * nx); }
@@ -763,38 +994,26 @@ int msipddp_solve(const Ctx &c, int device, int batch, const double *x0, const d
   std::vector<double> kl((size_t)N * nx), Kl((size_t)N * nx * nx), dxs((size_t)N * nx), Xn, Un, Fn, Ln, Sn, Yn, Gn, Yt, ynew(std::max(m, 1)), snew(std::max(m, 1));
   std::vector<double> Abuf((size_t)nx * nx), Bbuf((size_t)nx * nu), tmpx(nx);
   const bool first_rule = !o.enable_parallel;
-  const auto wall0 = std::chrono::steady_clock::now();
+  const StatClock clock;
 
   for (int it = 1; it <= o.max_iterations; ++it) {
-    bool any = false;
-    for (auto &t : T) any = any || !t.done;
-    if (!any) break;
-    if (aborted(pl)) return pfail(-50, "aborted by the caller (cddp_hip_plugin::abort_flag)");
-    if (o.max_cpu_time > 0.0) {
-      const double el_ms = (double)std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::steady_clock::now() - wall0).count();
-      if (el_ms > o.max_cpu_time * 1000.0) { for (auto &t : T) if (!t.done) { t.iter += 1; t.status = CDDP_HIP_STATUS_MAX_CPU_TIME; t.done = true; } break; }
-    }
+    { const int go = iteration_start(c, T, clock); if (go < 0) return go; if (!go) break; }
     // ---- derivative stacks of every running iterate (precomputeDynamicsDerivatives / precomputeConstraintGradients :846-1110)
     for (size_t b = 0; b < B; ++b) {
       MTraj &t = T[b];
-      regv[b] = t.done ? std::max(t.reg, o.reg_min_value) : t.reg;
-      muv[b] = (t.mu > 0.0) ? t.mu : 1e-8;
       if (t.done) continue;
       t.iter += 1;
       for (int s = 0; s < N; ++s) {
         const double *x = t.X.data() + (size_t)s * nx, *u = t.U.data() + (size_t)s * nu;
         const size_t bs = b * N + s;
         for (int i = 0; i < nx; ++i) dfc[bs * nx + i] = t.F[(size_t)s * nx + i] - t.X[(size_t)(s + 1) * nx + i];
-        pl->jacobians(pl->user, x, u, s * dt, tfx.data(), tfu.data());
-        for (int i = 0; i < nx; ++i) for (int j = 0; j < nx; ++j) { double a = dt * tfx[i * nx + j]; if (i == j) a += 1.0; fx[(bs * nx + i) * nx + j] = a; }
-        for (int i = 0; i < nx * nu; ++i) fu[bs * nx * nu + i] = dt * tfu[i];
-        double *plxx = lxx.data() + bs * nx * nx, *pluu = luu.data() + bs * nu * nu, *plux = lux.data() + bs * nu * nx;
-        pl->running_cost_derivatives(pl->user, x, u, s, lx.data() + bs * nx, lu.data() + bs * nu, plxx, pluu, plux);
+        sw.linearise(b, s, x, u, tfx.data(), tfu.data());
+        double *plxx = sw.lxx.data() + bs * nx * nx, *pluu = sw.luu.data() + bs * nu * nu, *plux = sw.lux.data() + bs * nu * nx;
         if (m > 0) {
-          std::copy(t.Y.begin() + (size_t)s * m, t.Y.begin() + (size_t)(s + 1) * m, ys.begin() + bs * m);
-          std::copy(t.S.begin() + (size_t)s * m, t.S.begin() + (size_t)(s + 1) * m, ss.begin() + bs * m);
-          std::copy(t.G.begin() + (size_t)s * m, t.G.begin() + (size_t)(s + 1) * m, gs.begin() + bs * m);
-          pl->constraints(pl->user, x, u, s, gtmp.data(), Gxs.data() + bs * m * nx, Gus.data() + bs * m * nu);
+          std::copy(t.Y.begin() + (size_t)s * m, t.Y.begin() + (size_t)(s + 1) * m, sw.gy.begin() + bs * m);
+          std::copy(t.S.begin() + (size_t)s * m, t.S.begin() + (size_t)(s + 1) * m, sw.gs.begin() + bs * m);
+          std::copy(t.G.begin() + (size_t)s * m, t.G.begin() + (size_t)(s + 1) * m, sw.gg.begin() + bs * m);
+          pl->constraints(pl->user, x, u, s, gtmp.data(), sw.gGx.data() + bs * m * nx, sw.gGu.data() + bs * m * nu);
         }
         if (!o.use_ilqr) {   // :1151-1163, 1279-1310, folded into the cost Hessians
           pl->hessians(pl->user, x, u, s * dt, Hxx.data(), Huu.data(), Hux.data());
@@ -816,32 +1035,22 @@ int msipddp_solve(const Ctx &c, int device, int batch, const double *x0, const d
           }
         }
       }
-      pl->terminal_cost_derivatives(pl->user, t.X.data() + (size_t)N * nx, VxN.data() + b * nx, VxxN.data() + b * nx * nx);
+      pl->terminal_cost_derivatives(pl->user, t.X.data() + (size_t)N * nx, sw.VxN.data() + b * nx, sw.VxxN.data() + b * nx * nx);
     }
-    { int rc = cddp_hip_set_stacks(sh, fx.data(), fu.data(), lx.data(), lu.data(), lxx.data(), luu.data(), lux.data(), VxN.data(), VxxN.data()); if (rc) return rc; }
-    { int rc = cddp_hip_set_defect_stack(sh, dfc.data()); if (rc) return rc; }
-    if (m > 0) { int rc = cddp_hip_set_constraint_stacks(sh, ys.data(), ss.data(), gs.data(), Gxs.data(), Gus.data()); if (rc) return rc; }
-    { int rc = cddp_hip_stacks_backward(sh, m > 0 ? CDDP_HIP_STACKS_MSIPDDP_PATH : CDDP_HIP_STACKS_MSIPDDP, c.o, regv.data(), m > 0 ? muv.data() : nullptr, 1, okv.data()); if (rc) return rc; }
-    { int rc = cddp_hip_stacks_get_gains(sh, Kb.data(), kb.data(), Vxb.data(), Vxxb.data(), dVb.data()); if (rc) return rc; }
-    if (Kout) for (size_t b = 0; b < B; ++b) if (!T[b].done) std::copy(Kb.begin() + b * N * nu * nx, Kb.begin() + (b + 1) * N * nu * nx, Kfin.begin() + b * N * nu * nx);
-    if (m > 0) { int rc = cddp_hip_stacks_get_constraint_gains(sh, kyb.data(), Kyb.data(), ksb.data(), Ksb.data(), dXb.data()); if (rc) return rc; }
-    { int rc = cddp_hip_stacks_get_scalars(sh, s_reg.data(), s_du.data(), s_pr.data(), s_comp.data(), s_sn.data(), s_apr.data(), s_adu.data()); if (rc) return rc; }
+    { int rc = cddp_hip_set_defect_stack(sw.h, dfc.data()); if (rc) return rc; }
+    { int rc = sw.run(m > 0 ? CDDP_HIP_STACKS_MSIPDDP_PATH : CDDP_HIP_STACKS_MSIPDDP, T, 1e-8, false); if (rc) return rc; }
 
     for (size_t b = 0; b < B; ++b) {
       MTraj &t = T[b];
       if (t.done) continue;
       if (aborted(pl)) return pfail(-50, "aborted by the caller (cddp_hip_plugin::abort_flag)");
-      { int nb = 1; double r = t.reg; while (r < s_reg[b] && nb < 64) { r = reg_increase(o, r); ++nb; }
-        if (!okv[b] && nb > 1) --nb;
-        t.n_bwd += nb; }
-      t.reg = s_reg[b];
-      if (!okv[b]) { t.status = CDDP_HIP_STATUS_REG_LIMIT; t.done = true; continue; }   // handleBackwardPassRegularizationLimit (base)
-      t.dV0 = dVb[b * 2]; t.dV1 = dVb[b * 2 + 1]; t.inf_du = s_du[b]; t.step_norm = s_sn[b];
+      if (!sw.replay(t, b)) { t.status = CDDP_HIP_STATUS_REG_LIMIT; t.done = true; continue; }   // handleBackwardPassRegularizationLimit (base)
+      t.dV0 = sw.dVb[b * 2]; t.dV1 = sw.dVb[b * 2 + 1]; t.inf_du = sw.s_du[b]; t.step_norm = sw.s_sn[b];
       double idef = 0.0;
       for (size_t e = 0; e < (size_t)N * nx; ++e) idef = std::max(idef, std::fabs(dfc[b * N * nx + e]));
-      if (m > 0) { t.inf_pr = std::max(s_pr[b], idef); t.inf_comp = s_comp[b]; } else { t.inf_pr = idef; t.inf_comp = 0.0; }
-      const double *K = Kb.data() + b * N * nu * nx, *k = kb.data() + b * N * nu, *Vx = Vxb.data() + b * (N + 1) * nx, *Vxx = Vxxb.data() + b * (N + 1) * nx * nx;
-      const double *ky = kyb.data() + b * N * m, *Ky = Kyb.data() + b * N * m * nx, *ks = ksb.data() + b * N * m, *Ks = Ksb.data() + b * N * m * nx;
+      if (m > 0) { t.inf_pr = std::max(sw.s_pr[b], idef); t.inf_comp = sw.s_comp[b]; } else { t.inf_pr = idef; t.inf_comp = 0.0; }
+      const double *K = sw.Kb.data() + b * N * nu * nx, *k = sw.kb.data() + b * N * nu, *Vx = sw.Vxb.data() + b * (N + 1) * nx, *Vxx = sw.Vxxb.data() + b * (N + 1) * nx * nx;
+      const double *ky = sw.kyb.data() + b * N * m, *Ky = sw.Kyb.data() + b * N * m * nx, *ks = sw.ksb.data() + b * N * m, *Ks = sw.Ksb.data() + b * N * m * nx;
       for (int s = 0; s < N; ++s) {   // k_lambda = -lambda + V_x + V_xx d, K_lambda = sym(V_xx) of step s + 1 (:1196-1198)
         const double *vx = Vx + (size_t)(s + 1) * nx, *vxx = Vxx + (size_t)(s + 1) * nx * nx, *d = dfc.data() + (b * N + s) * nx;
         for (int i = 0; i < nx; ++i) {
@@ -1033,18 +1242,8 @@ int msipddp_solve(const Ctx &c, int device, int batch, const double *x0, const d
       if (it == o.max_iterations) { t.status = CDDP_HIP_STATUS_MAX_ITERATIONS; t.done = true; }
     }
   }
-  for (auto &t : T) if (!t.done) { t.status = CDDP_HIP_STATUS_MAX_ITERATIONS; t.done = true; }
-  if (Kout) std::copy(Kfin.begin(), Kfin.end(), Kout);
-  for (size_t b = 0; b < B; ++b) {   // CDDPSolution + populateSolverSpecificSolution :406-413
-    const MTraj &t = T[b];
-    cddp_hip_result &r = results[b];
-    std::memset(&r, 0, sizeof(r));
-    r.final_objective = t.cost; r.merit_function = t.merit; r.inf_pr = t.inf_pr; r.inf_du = t.inf_du; r.inf_comp = t.inf_comp;
-    r.barrier_mu = t.mu; r.regularization = t.reg; r.alpha_pr = t.alpha_pr; r.alpha_du = t.alpha_du;
-    r.iterations = t.iter; r.status = t.status; r.n_backward = t.n_bwd; r.n_forward = t.n_fwd;
-    if (Xout) std::copy(t.X.begin(), t.X.end(), Xout + b * (N + 1) * nx);
-    if (Uout) std::copy(t.U.begin(), t.U.end(), Uout + b * N * nu);
-  }
+  write_results(c, T, sw, clock, results, Xout, Uout, Kout);
+  for (size_t b = 0; b < B; ++b) results[b].step_norm = 0.0;   // (populateSolverSpecificSolution :406-413 does not report it)
   return 0;
 }
 
@@ -1059,104 +1258,12 @@ int msipddp_solve(const Ctx &c, int device, int batch, const double *x0, const d
 // ======================================================================================================================
 constexpr double kEpsDual = 1e-10;   // EPS_DUAL ipddp_solver.cpp:37
 
-struct TermInfo {
-  const cddp_hip_plugin_terminal *tc = nullptr;
-  int nobj = 0, rows = 0, mT = 0, pT = 0;
-  int dim[CDDP_HIP_PLUGIN_MAX_CONSTRAINTS], eq[CDDP_HIP_PLUGIN_MAX_CONSTRAINTS], src[CDDP_HIP_PLUGIN_MAX_CONSTRAINTS], dst[CDDP_HIP_PLUGIN_MAX_CONSTRAINTS];
-  // evaluate -> (g_T rows of the inequality objects in object order | h_T rows of the equality objects in object order) (+ Jacobian rows)
-  void eval(void *user, int nx, const double *xN, double *gT, double *GTx, double *hT, double *HT, std::vector<double> &r, std::vector<double> &rx) const {
-    if (!tc || rows == 0) return;
-    r.assign((size_t)rows, 0.0); rx.assign((size_t)rows * nx, 0.0);
-    tc->evaluate(user, xN, r.data(), (GTx || HT) ? rx.data() : nullptr);
-    for (int s = 0; s < nobj; ++s)
-      for (int i = 0; i < dim[s]; ++i) {
-        if (eq[s]) { if (hT) hT[dst[s] + i] = r[src[s] + i]; if (HT) std::copy(rx.begin() + (size_t)(src[s] + i) * nx, rx.begin() + (size_t)(src[s] + i + 1) * nx, HT + (size_t)(dst[s] + i) * nx); }
-        else { if (gT) gT[dst[s] + i] = r[src[s] + i]; if (GTx) std::copy(rx.begin() + (size_t)(src[s] + i) * nx, rx.begin() + (size_t)(src[s] + i + 1) * nx, GTx + (size_t)(dst[s] + i) * nx); }
-      }
-  }
-};
-
 struct TTraj : Traj {
   std::vector<double> ST, YT, GT, dST, dYT, LamT, dLamT;              // terminal slack / dual / residual (mT), multipliers (pT)
   std::vector<double> ky, Ky, ks, Ks;                                  // path gains of the last sweep (host-formed in the terminal-equality branch)
-  std::vector<double> gGx;                                             // G_x of the last backward pass (computeScaledDualInfeasibility)
   double l_pr = 0.0, l_comp = 0.0;                                     // terminal (and, in the reduced-LQR branch, path) residual maxima of the last sweep
 };
 struct TTrial : Trial { std::vector<double> ST, YT, GT, LamT; };
-
-void repair_interior(const cddp_hip_options &o, double *s, double *y, int dim) {   // repairWarmstartInterior (:233-262), one constraint object
-  if (!o.ipddp_warmstart_repair || dim <= 0) return;
-  double mn = kInf, mny = kInf;
-  for (int i = 0; i < dim; ++i) { s[i] = std::max(s[i], o.ipddp_warmstart_s_min); mn = std::min(mn, s[i]); }
-  if (mn < o.ipddp_warmstart_s_min * o.ipddp_warmstart_interior_factor) for (int i = 0; i < dim; ++i) s[i] = s[i] * o.ipddp_warmstart_interior_factor;
-  for (int i = 0; i < dim; ++i) { y[i] = std::max(y[i], o.ipddp_warmstart_y_min); mny = std::min(mny, y[i]); }
-  if (mny < o.ipddp_warmstart_y_min * o.ipddp_warmstart_interior_factor) for (int i = 0; i < dim; ++i) y[i] = y[i] * o.ipddp_warmstart_interior_factor;
-}
-
-// computeTheta / computeBarrierMerit / computePrimalAndComplementarity with the terminal terms (ipddp_solver.cpp:2778-2937): path objects
-// (constraint-major, then t), then the terminal-inequality objects, then the stacked terminal-equality residual
-void ip_reductions_t(const Ctx &c, const TermInfo &ti, const double *S, const double *Y, const double *G, const double *ST, const double *YT, const double *GT,
-                     const double *LamT, const double *hT, double mu, double cost0, double &phi, double &theta, double &inf_pr, double &inf_comp) {
-  const int m = c.m, N = c.N;
-  const bool l2 = c.o->ipddp_theta_norm_l2 != 0;
-  double total = 0.0, max_entry = 0.0, ipr = 0.0, icomp = 0.0, mer = cost0;
-  int off = 0;
-  for (int s = 0; s < (m > 0 ? c.pl->n_constraints : 0); ++s) {
-    const int dim = c.pl->constraint_dims[s];
-    for (int t = 0; t < N; ++t) {
-      double n1 = 0.0, ninf = 0.0;
-      for (int i = 0; i < dim; ++i) {
-        const size_t j = (size_t)t * m + off + i;
-        const double r = G[j] + S[j];
-        n1 += l2 ? r * r : std::fabs(r);
-        ninf = std::max(ninf, std::fabs(r));
-      }
-      total += n1; max_entry = std::max(max_entry, ninf);
-    }
-    off += dim;
-  }
-  for (int s = 0; s < ti.nobj; ++s) if (!ti.eq[s]) {
-    double n1 = 0.0, ninf = 0.0;
-    for (int i = 0; i < ti.dim[s]; ++i) { const double r = GT[ti.dst[s] + i] + ST[ti.dst[s] + i]; n1 += l2 ? r * r : std::fabs(r); ninf = std::max(ninf, std::fabs(r)); }
-    total += n1; max_entry = std::max(max_entry, ninf);
-  }
-  if (ti.pT > 0) {
-    double n1 = 0.0, ninf = 0.0;
-    for (int i = 0; i < ti.pT; ++i) { n1 += l2 ? hT[i] * hT[i] : std::fabs(hT[i]); ninf = std::max(ninf, std::fabs(hT[i])); }
-    total += n1; max_entry = std::max(max_entry, ninf);
-  }
-  off = 0;
-  for (int s = 0; s < (m > 0 ? c.pl->n_constraints : 0); ++s) {
-    const int dim = c.pl->constraint_dims[s];
-    for (int t = 0; t < N; ++t) {
-      double ls = 0.0;
-      for (int i = 0; i < dim; ++i) ls += std::log(std::max(S[(size_t)t * m + off + i], kEpsSlack));
-      mer -= mu * ls;
-    }
-    off += dim;
-  }
-  for (int s = 0; s < ti.nobj; ++s) if (!ti.eq[s]) {
-    double ls = 0.0;
-    for (int i = 0; i < ti.dim[s]; ++i) ls += std::log(std::max(ST[ti.dst[s] + i], kEpsSlack));
-    mer -= mu * ls;
-  }
-  if (ti.pT > 0) { double dp = 0.0; for (int i = 0; i < ti.pT; ++i) dp += LamT[i] * hT[i]; mer += dp; }
-  off = 0;
-  for (int s = 0; s < (m > 0 ? c.pl->n_constraints : 0); ++s) {
-    const int dim = c.pl->constraint_dims[s];
-    for (int t = 0; t < N; ++t)
-      for (int i = 0; i < dim; ++i) {
-        const size_t j = (size_t)t * m + off + i;
-        ipr = std::max(ipr, std::fabs(G[j] + S[j])); icomp = std::max(icomp, std::fabs(Y[j] * S[j] - mu));
-      }
-    off += dim;
-  }
-  for (int i = 0; i < ti.mT; ++i) { ipr = std::max(ipr, std::fabs(GT[i] + ST[i])); icomp = std::max(icomp, std::fabs(YT[i] * ST[i] - mu)); }
-  for (int i = 0; i < ti.pT; ++i) ipr = std::max(ipr, std::fabs(hT[i]));
-  const double th = l2 ? std::sqrt(total) : total;
-  theta = std::max(th, max_entry);
-  phi = mer; inf_pr = ipr; inf_comp = icomp;
-}
 
 // resetFilter (:2484-2519)
 void reset_filter_t(const Ctx &c, const TermInfo &ti, TTraj &T, std::vector<double> &r, std::vector<double> &rx) {
@@ -1338,55 +1445,32 @@ TTrial forward_ipddp_t(const Ctx &c, const TermInfo &ti, const TTraj &T, const G
 
 int ipddp_terminal_solve(const Ctx &c, const TermInfo &ti, int device, int batch, const double *x0, const double *U0, const double *X0,
                          cddp_hip_result *results, double *Xout, double *Uout, double *Kout, double *Tout) {
-  const cddp_hip_plugin *pl = c.pl; const cddp_hip_options &o = *c.o; const cddp_hip_options *opt = c.o;
-  const int nx = c.nx, nu = c.nu, m = c.m, N = c.N, mT = ti.mT, pT = ti.pT; const double dt = c.dt;
-  const bool hti = mT > 0, hte = pT > 0, no_barrier = (m == 0 && !hti);
+  const cddp_hip_plugin *pl = c.pl; const cddp_hip_options &o = *c.o;
+  const int nx = c.nx, nu = c.nu, m = c.m, N = c.N, mT = ti.mT, pT = ti.pT;
+  const bool hti = mT > 0, hte = pT > 0, has_barrier = (m > 0 || hti);
   const size_t B = (size_t)batch;
   // terminal-equality rows: the reduced LQR takes the path constraints condensed (handle with m = 0); otherwise the ordinary sweeps
-  cddp_hip_stack_handle *sh = nullptr;
-  { int rc = cddp_hip_stacks_create(device, batch, nx, nu, hte ? 0 : m, N, &sh); if (rc) return rc; }
-  struct Guard { cddp_hip_stack_handle *h; ~Guard() { if (h) cddp_hip_stacks_destroy(h); } } guard{sh};
+  BatchSweep sw(c, batch, m, !o.use_ilqr, Kout != nullptr);
+  { int rc = sw.open(device, hte ? 0 : m); if (rc) return rc; }
   std::vector<TTraj> T(B);
-  const int n_threads = host_threads((int)B);
-  par_for(B, n_threads, [&](size_t b) { initialize_t(c, ti, T[b], x0 + b * nx, U0 ? U0 + b * N * nu : nullptr, X0 ? X0 + b * (N + 1) * nx : nullptr); });
+  par_for(B, c.threads, [&](size_t b) { initialize_t(c, ti, T[b], x0 + b * nx, U0 ? U0 + b * N * nu : nullptr, X0 ? X0 + b * (N + 1) * nx : nullptr); });
 
-  std::vector<double> fx(B * N * nx * nx), fu(B * N * nx * nu), lx(B * N * nx), lu(B * N * nu), lxx(B * N * nx * nx), luu(B * N * nu * nu),
-      lux(B * N * nu * nx), VxN(B * nx), VxxN(B * nx * nx);
-  std::vector<double> gy, gs, gg, gGx, gGu, Fxx, Fuu, Fux;
-  if (m > 0) { gy.resize(B * N * m); gs = gy; gg = gy; gGx.resize(B * N * m * nx); gGu.resize(B * N * m * nu); }
-  if (!o.use_ilqr) { Fxx.resize(B * N * nx * nx * nx); Fuu.resize(B * N * nx * nu * nu); Fux.resize(B * N * nx * nu * nx); }
-  std::vector<double> Kb(B * N * nu * nx), kb(B * N * nu), Vxb(B * (N + 1) * nx), Vxxb(B * (N + 1) * nx * nx), dVb(B * 2);
-  std::vector<double> Kfin(Kout ? B * N * nu * nx : 0, 0.0);
-  std::vector<double> kyb, Kyb, ksb, Ksb, dXb(B * (N + 1) * nx, 0.0);
-  if (m > 0) { kyb.resize(B * N * m); ksb = kyb; Kyb.resize(B * N * m * nx); Ksb = Kyb; }
   std::vector<double> GTxb(B * (size_t)std::max(mT, 1) * nx, 0.0), HTb(B * (size_t)std::max(pT, 1) * nx, 0.0), bTb(B * (size_t)std::max(pT, 1), 0.0),
       lamb(B * (size_t)std::max(pT, 1), 0.0), floorb(B, 0.0), dlamb(B * (size_t)std::max(pT, 1), 0.0);
-  std::vector<double> regv(B), muv(B), s_reg(B), s_du(B), s_pr(B), s_comp(B), s_sn(B), s_apr(B), s_adu(B);
-  std::vector<int32_t> okv(B);
-  const bool first_rule = !o.enable_parallel;
   std::atomic<bool> abort_seen{false};
-  const auto wall0 = std::chrono::steady_clock::now();
+  const StatClock clock;
 
   for (int it = 1; it <= o.max_iterations; ++it) {
-    bool any = false;
-    for (auto &t : T) any = any || !t.done;
-    if (!any) break;
-    if (aborted(pl)) return pfail(-50, "aborted by the caller (cddp_hip_plugin::abort_flag)");
-    if (o.max_cpu_time > 0.0) {
-      const double el_ms = (double)std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::steady_clock::now() - wall0).count();
-      if (el_ms > o.max_cpu_time * 1000.0) { for (auto &t : T) if (!t.done) { t.iter += 1; t.status = CDDP_HIP_STATUS_MAX_CPU_TIME; t.done = true; } break; }
-    }
+    { const int go = iteration_start(c, T, clock); if (go < 0) return go; if (!go) break; }
     // ---- host: derivatives, terminal value, LQ model
     auto fill = [&](size_t b) {
       TTraj &t = T[b];
-      regv[b] = t.done ? std::max(t.reg, o.reg_min_value) : t.reg;
-      muv[b] = (t.mu > 0.0) ? t.mu : 1.0;
       floorb[b] = std::max(1e-10, o.ipddp_jacobian_regularization_value * std::pow(std::max(t.mu, 0.0), o.ipddp_jacobian_regularization_exponent));
       if (t.done) return;
       t.iter += 1;
       const double mu = t.mu, fl0 = std::max(mu * 1e-3, kEpsSlack);
       std::vector<double> tfx((size_t)nx * nx), tfu((size_t)nx * nu), r, rx, hT((size_t)std::max(pT, 1), 0.0);
-      double *Vx = VxN.data() + b * nx, *Vxx = VxxN.data() + b * nx * nx;
+      double *Vx = sw.VxN.data() + b * nx, *Vxx = sw.VxxN.data() + b * nx * nx;
       const double *xN = t.X.data() + (size_t)N * nx;
       pl->terminal_cost_derivatives(pl->user, xN, Vx, Vxx);
       { std::vector<double> S2((size_t)nx * nx); for (int i = 0; i < nx; ++i) for (int j = 0; j < nx; ++j) S2[i * nx + j] = 0.5 * (Vxx[i * nx + j] + Vxx[j * nx + i]); std::copy(S2.begin(), S2.end(), Vxx); }
@@ -1409,28 +1493,18 @@ int ipddp_terminal_solve(const Ctx &c, const TermInfo &ti, int device, int batch
       if (hte) {
         for (int i = 0; i < pT; ++i) { t.l_pr = std::max(t.l_pr, std::fabs(hT[i])); bTb[b * pT + i] = -hT[i]; lamb[b * pT + i] = t.LamT[i]; t.dLamT[i] = -hT[i]; }
       }
-      if (m > 0) t.gGx.assign((size_t)N * m * nx, 0.0);
       for (int s = 0; s < N; ++s) {
         const double *x = t.X.data() + (size_t)s * nx, *u = t.U.data() + (size_t)s * nu;
         const size_t bs = b * N + s;
-        pl->jacobians(pl->user, x, u, s * dt, tfx.data(), tfu.data());
-        for (int i = 0; i < nx; ++i) for (int j = 0; j < nx; ++j) { double a = dt * tfx[i * nx + j]; if (i == j) a += 1.0; fx[(bs * nx + i) * nx + j] = a; }
-        for (int i = 0; i < nx * nu; ++i) fu[bs * nx * nu + i] = dt * tfu[i];
-        double *q = lx.data() + bs * nx, *rr = lu.data() + bs * nu, *Q = lxx.data() + bs * nx * nx, *R = luu.data() + bs * nu * nu, *Mx = lux.data() + bs * nu * nx;
-        pl->running_cost_derivatives(pl->user, x, u, s, q, rr, Q, R, Mx);
-        if (!o.use_ilqr) {
-          double *pxx = Fxx.data() + bs * nx * nx * nx, *puu = Fuu.data() + bs * nx * nu * nu, *pux = Fux.data() + bs * nx * nu * nx;
-          pl->hessians(pl->user, x, u, s * dt, pxx, puu, pux);
-          for (int e = 0; e < nx * nx * nx; ++e) pxx[e] = dt * pxx[e];
-          for (int e = 0; e < nx * nu * nu; ++e) puu[e] = dt * puu[e];
-          for (int e = 0; e < nx * nu * nx; ++e) pux[e] = dt * pux[e];
-        }
+        sw.linearise(b, s, x, u, tfx.data(), tfu.data());
+        double *q = sw.lx.data() + bs * nx, *rr = sw.lu.data() + bs * nu, *Q = sw.lxx.data() + bs * nx * nx, *R = sw.luu.data() + bs * nu * nu,
+               *Mx = sw.lux.data() + bs * nu * nx;
+        if (!o.use_ilqr) sw.scaled_hessians(b, s, x, u);
         if (m > 0) {
-          pl->constraints(pl->user, x, u, s, gg.data() + bs * m, gGx.data() + bs * m * nx, gGu.data() + bs * m * nu);
-          std::copy(t.G.begin() + (size_t)s * m, t.G.begin() + (size_t)(s + 1) * m, gg.begin() + bs * m);
-          std::copy(t.S.begin() + (size_t)s * m, t.S.begin() + (size_t)(s + 1) * m, gs.begin() + bs * m);
-          std::copy(t.Y.begin() + (size_t)s * m, t.Y.begin() + (size_t)(s + 1) * m, gy.begin() + bs * m);
-          std::copy(gGx.begin() + bs * m * nx, gGx.begin() + (bs + 1) * m * nx, t.gGx.begin() + (size_t)s * m * nx);
+          pl->constraints(pl->user, x, u, s, sw.gg.data() + bs * m, sw.gGx.data() + bs * m * nx, sw.gGu.data() + bs * m * nu);
+          std::copy(t.G.begin() + (size_t)s * m, t.G.begin() + (size_t)(s + 1) * m, sw.gg.begin() + bs * m);
+          std::copy(t.S.begin() + (size_t)s * m, t.S.begin() + (size_t)(s + 1) * m, sw.gs.begin() + bs * m);
+          std::copy(t.Y.begin() + (size_t)s * m, t.Y.begin() + (size_t)(s + 1) * m, sw.gy.begin() + bs * m);
         }
         if (!hte) continue;
         // ---- LQ model of the reduced LQR (:1143-1247): Q = sym(l_xx), R = sym(l_uu), M = l_ux^T, (+ second-order terms weighed with the
@@ -1442,7 +1516,7 @@ int ipddp_terminal_solve(const Ctx &c, const TermInfo &ti, int device, int batch
         if (!o.use_ilqr) {
           const double *lam = t.Lam.data() + (size_t)(s + 1) * nx;
           bool lf = true; for (int i = 0; i < nx; ++i) lf = lf && fin(lam[i]);
-          const double *pxx = Fxx.data() + bs * nx * nx * nx, *puu = Fuu.data() + bs * nx * nu * nu, *pux = Fux.data() + bs * nx * nu * nx;
+          const double *pxx = sw.Fxx.data() + bs * nx * nx * nx, *puu = sw.Fuu.data() + bs * nx * nu * nu, *pux = sw.Fux.data() + bs * nx * nu * nx;
           for (int i = 0; i < nx; ++i) {
             const double li = lf ? lam[i] : 0.0;
             for (int e = 0; e < nx * nx; ++e) Qs[e] = Qs[e] + li * pxx[(size_t)i * nx * nx + e];
@@ -1454,7 +1528,8 @@ int ipddp_terminal_solve(const Ctx &c, const TermInfo &ti, int device, int batch
           for (int i = 0; i < nu; ++i) for (int j = 0; j < nu; ++j) Rs[i * nu + j] = 0.5 * (R2[i * nu + j] + R2[j * nu + i]);
         }
         if (m > 0) {
-          const double *y = gy.data() + bs * m, *sv = gs.data() + bs * m, *g = gg.data() + bs * m, *Qyx = gGx.data() + bs * m * nx, *Qyu = gGu.data() + bs * m * nu;
+          const double *y = sw.gy.data() + bs * m, *sv = sw.gs.data() + bs * m, *g = sw.gg.data() + bs * m, *Qyx = sw.gGx.data() + bs * m * nx,
+                       *Qyu = sw.gGu.data() + bs * m * nu;
           std::vector<double> YS(m), ypS(m);
           for (int i = 0; i < m; ++i) {
             const double ss = std::max(sv[i], fl0);
@@ -1475,37 +1550,23 @@ int ipddp_terminal_solve(const Ctx &c, const TermInfo &ti, int device, int batch
         std::copy(Qs.begin(), Qs.end(), Q); std::copy(Rs.begin(), Rs.end(), R); std::copy(Mm.begin(), Mm.end(), Mx);   // (the lux slot carries M as nx x nu)
       }
     };
-    par_for(B, n_threads, fill);
-    { int rc = cddp_hip_set_stacks(sh, fx.data(), fu.data(), lx.data(), lu.data(), lxx.data(), luu.data(), lux.data(), VxN.data(), VxxN.data()); if (rc) return rc; }
-    if (hte) {
-      { int rc = cddp_hip_set_terminal_equality(sh, pT, HTb.data(), bTb.data(), lamb.data(), floorb.data()); if (rc) return rc; }
-      { int rc = cddp_hip_stacks_backward(sh, CDDP_HIP_STACKS_IPDDP_TERM_EQ, opt, regv.data(), nullptr, 1, okv.data()); if (rc) return rc; }
-      { int rc = cddp_hip_stacks_get_terminal(sh, dlamb.data(), dXb.data()); if (rc) return rc; }
-    } else {
-      if (m > 0) { int rc = cddp_hip_set_constraint_stacks(sh, gy.data(), gs.data(), gg.data(), gGx.data(), gGu.data()); if (rc) return rc; }
-      if (!o.use_ilqr) { int rc = cddp_hip_set_hessian_stacks(sh, Fxx.data(), Fuu.data(), Fux.data()); if (rc) return rc; }
-      { int rc = cddp_hip_stacks_backward(sh, m > 0 ? CDDP_HIP_STACKS_IPDDP_PATH : CDDP_HIP_STACKS_IPDDP, opt, regv.data(), m > 0 ? muv.data() : nullptr, 1, okv.data()); if (rc) return rc; }
-      if (m > 0) { int rc = cddp_hip_stacks_get_constraint_gains(sh, kyb.data(), Kyb.data(), ksb.data(), Ksb.data(), dXb.data()); if (rc) return rc; }
-    }
-    { int rc = cddp_hip_stacks_get_gains(sh, Kb.data(), kb.data(), Vxb.data(), Vxxb.data(), dVb.data()); if (rc) return rc; }
-    { int rc = cddp_hip_stacks_get_scalars(sh, s_reg.data(), s_du.data(), s_pr.data(), s_comp.data(), s_sn.data(), s_apr.data(), s_adu.data()); if (rc) return rc; }
-    if (Kout) for (size_t b = 0; b < B; ++b) if (!T[b].done) std::copy(Kb.begin() + b * N * nu * nx, Kb.begin() + (b + 1) * N * nu * nx, Kfin.begin() + b * N * nu * nx);
+    par_for(B, c.threads, fill);
+    if (hte) { int rc = cddp_hip_set_terminal_equality(sw.h, pT, HTb.data(), bTb.data(), lamb.data(), floorb.data()); if (rc) return rc; }
+    const int branch = hte ? CDDP_HIP_STACKS_IPDDP_TERM_EQ : (m > 0 ? CDDP_HIP_STACKS_IPDDP_PATH : CDDP_HIP_STACKS_IPDDP);
+    { int rc = sw.run(branch, T, 1.0, !o.use_ilqr && !hte); if (rc) return rc; }
+    if (hte) { int rc = cddp_hip_stacks_get_terminal(sw.h, dlamb.data(), sw.dXb.data()); if (rc) return rc; }
 
     auto advance = [&](size_t b) {
       TTraj &t = T[b];
       if (t.done) return;
       if (aborted(pl)) { abort_seen.store(true); return; }
-      { int nb = 1; double r = t.reg; while (r < s_reg[b] && nb < 64) { r = reg_increase(o, r); ++nb; }
-        if (!okv[b] && nb > 1) --nb;
-        t.n_bwd += nb; }
-      t.reg = s_reg[b];
-      if (!okv[b]) { t.status = CDDP_HIP_STATUS_REG_LIMIT; t.done = true; return; }
+      if (!sw.replay(t, b)) { t.status = CDDP_HIP_STATUS_REG_LIMIT; t.done = true; return; }
       const double mu = t.mu, fl0 = std::max(mu * 1e-3, kEpsSlack);
       const double tau = std::max(o.barrier_min_fraction_to_boundary, 1.0 - mu);
-      const double *Kt = Kb.data() + b * N * nu * nx, *kt = kb.data() + b * N * nu;
-      double *dX = dXb.data() + b * (N + 1) * nx;
+      const double *Kt = sw.Kb.data() + b * N * nu * nx, *kt = sw.kb.data() + b * N * nu, *Gx = m > 0 ? sw.gGx.data() + b * N * m * nx : nullptr;
+      double *dX = sw.dXb.data() + b * (N + 1) * nx;
       double apr = 1.0, adu = 1.0;
-      t.inf_du = s_du[b]; t.step_norm = s_sn[b];
+      t.inf_du = sw.s_du[b]; t.step_norm = sw.s_sn[b];
       if (hte) {
         t.dV0 = 0.0; t.dV1 = 0.0;
         t.inf_pr = t.l_pr; t.inf_comp = t.l_comp;
@@ -1514,7 +1575,8 @@ int ipddp_terminal_solve(const Ctx &c, const TermInfo &ti, int device, int batch
           t.ky.assign((size_t)N * m, 0.0); t.ks = t.ky; t.Ky.assign((size_t)N * m * nx, 0.0); t.Ks = t.Ky;
           for (int s = 0; s < N; ++s) {
             const size_t bs = b * N + s;
-            const double *y = gy.data() + bs * m, *sv = gs.data() + bs * m, *g = gg.data() + bs * m, *Qyx = gGx.data() + bs * m * nx, *Qyu = gGu.data() + bs * m * nu;
+            const double *y = sw.gy.data() + bs * m, *sv = sw.gs.data() + bs * m, *g = sw.gg.data() + bs * m, *Qyx = sw.gGx.data() + bs * m * nx,
+                         *Qyu = sw.gGu.data() + bs * m * nu;
             for (int r2 = 0; r2 < m; ++r2) {
               const double ss = std::max(sv[r2], fl0), YSr = clampd(y[r2] / ss, 0.0, kMaxRatio);
               const double rp = g[r2] + sv[r2], rc = y[r2] * sv[r2] - mu, rhat = y[r2] * rp - rc;
@@ -1538,19 +1600,19 @@ int ipddp_terminal_solve(const Ctx &c, const TermInfo &ti, int device, int batch
           }
         }
       } else {
-        t.dV0 = dVb[b * 2]; t.dV1 = dVb[b * 2 + 1];
-        t.inf_pr = std::max((m > 0) ? s_pr[b] : 0.0, t.l_pr); t.inf_comp = std::max((m > 0) ? s_comp[b] : 0.0, t.l_comp);
+        t.dV0 = sw.dVb[b * 2]; t.dV1 = sw.dVb[b * 2 + 1];
+        t.inf_pr = std::max((m > 0) ? sw.s_pr[b] : 0.0, t.l_pr); t.inf_comp = std::max((m > 0) ? sw.s_comp[b] : 0.0, t.l_comp);
         if (m > 0) {
-          apr = s_apr[b]; adu = s_adu[b];
-          t.ky.assign(kyb.begin() + b * N * m, kyb.begin() + (b + 1) * N * m); t.ks.assign(ksb.begin() + b * N * m, ksb.begin() + (b + 1) * N * m);
-          t.Ky.assign(Kyb.begin() + b * N * m * nx, Kyb.begin() + (b + 1) * N * m * nx); t.Ks.assign(Ksb.begin() + b * N * m * nx, Ksb.begin() + (b + 1) * N * m * nx);
+          apr = sw.s_apr[b]; adu = sw.s_adu[b];
+          t.ky.assign(sw.kyb.begin() + b * N * m, sw.kyb.begin() + (b + 1) * N * m); t.ks.assign(sw.ksb.begin() + b * N * m, sw.ksb.begin() + (b + 1) * N * m);
+          t.Ky.assign(sw.Kyb.begin() + b * N * m * nx, sw.Kyb.begin() + (b + 1) * N * m * nx); t.Ks.assign(sw.Ksb.begin() + b * N * m * nx, sw.Ksb.begin() + (b + 1) * N * m * nx);
         } else {   // rolloutLinearPolicy on the host (:1511-1520): the unconstrained stack sweep does not form dX
           std::vector<double> dx(nx, 0.0), dxn(nx), du(nu);
           for (int s = 0; s < N; ++s) {
             std::copy(dx.begin(), dx.end(), dX + (size_t)s * nx);
             const size_t bs = b * N + s;
             for (int i = 0; i < nu; ++i) { double a = 0.0; for (int j = 0; j < nx; ++j) a += Kt[((size_t)s * nu + i) * nx + j] * dx[j]; du[i] = kt[(size_t)s * nu + i] + a; }
-            for (int i = 0; i < nx; ++i) { double a = 0.0, cc = 0.0; for (int j = 0; j < nx; ++j) a += fx[(bs * nx + i) * nx + j] * dx[j]; for (int j = 0; j < nu; ++j) cc += fu[(bs * nx + i) * nu + j] * du[j]; dxn[i] = (a + cc) + 0.0; }
+            for (int i = 0; i < nx; ++i) { double a = 0.0, cc = 0.0; for (int j = 0; j < nx; ++j) a += sw.fx[(bs * nx + i) * nx + j] * dx[j]; for (int j = 0; j < nu; ++j) cc += sw.fu[(bs * nx + i) * nu + j] * du[j]; dxn[i] = (a + cc) + 0.0; }
             dx = dxn;
           }
           std::copy(dx.begin(), dx.end(), dX + (size_t)N * nx);
@@ -1571,30 +1633,11 @@ int ipddp_terminal_solve(const Ctx &c, const TermInfo &ti, int device, int batch
       }
       t.apr_max = clampd(apr, 0.0, 1.0); t.adu_max = clampd(adu, 0.0, 1.0);
       Gains g;
-      g.K = Kt; g.k = kt; g.Vx = Vxb.data() + b * (N + 1) * nx; g.Vxx = Vxxb.data() + b * (N + 1) * nx * nx;
+      g.K = Kt; g.k = kt; g.Vx = sw.Vxb.data() + b * (N + 1) * nx; g.Vxx = sw.Vxxb.data() + b * (N + 1) * nx * nx;
       g.ky = t.ky.data(); g.Ky = t.Ky.data(); g.ks = t.ks.data(); g.Ks = t.Ks.data();
-      // ---- checkEarlyConvergence (:925-958)
-      bool conv = false;
-      {
-        const double sdu = scaled_inf_du(c, t, t.gGx);
-        if (no_barrier) conv = (t.inf_pr < o.tolerance && sdu < o.tolerance);
-        else {
-          const double tol = std::max(o.tolerance, o.ipddp_barrier_tol_mult * t.mu);
-          conv = (t.inf_pr < tol && sdu < tol && t.inf_comp < tol && std::fabs(t.alpha_pr) * t.step_norm < o.tolerance * 10.0);
-        }
-      }
-      if (conv) { t.status = CDDP_HIP_STATUS_OPTIMAL; t.done = true; return; }
-      TTrial best; bool have = false;
-      int walked = 0;
-      for (double a : c.alphas) {
-        TTrial r = forward_ipddp_t(c, ti, t, g, a, GTx);
-        ++walked;
-        if (!r.success) continue;
-        if (first_rule) { best = std::move(r); have = true; break; }
-        if (!have || r.merit < best.merit) { best = std::move(r); have = true; }
-      }
-      t.n_fwd += first_rule ? walked : (int)c.alphas.size();
-      if (have) {
+      if (ip_early_converged(c, t, Gx, has_barrier)) { t.status = CDDP_HIP_STATUS_OPTIMAL; t.done = true; return; }
+      TTrial best;
+      if (line_search(c, t, best, [&](double a) { return forward_ipddp_t(c, ti, t, g, a, GTx); })) {
         const double dJ = t.cost - best.cost;
         t.X.swap(best.X); t.U.swap(best.U); t.Lam.swap(best.Lam);
         t.cost = best.cost; t.merit = best.merit; t.alpha_pr = best.alpha_pr; t.alpha_du = best.alpha_du;
@@ -1602,103 +1645,139 @@ int ipddp_terminal_solve(const Ctx &c, const TermInfo &ti, int device, int batch
         if (hti) { t.ST = best.ST; t.YT = best.YT; t.GT = best.GT; }
         if (hte) t.LamT = best.LamT;
         t.inf_pr = best.inf_pr; t.inf_comp = best.inf_comp; t.phi = best.merit; t.filter_theta = best.theta; t.theta = best.theta;
-        // ---- updateBarrierParameters(true) (:2548-2660)
-        const double sdu = scaled_inf_du(c, t, t.gGx);
-        double mu2 = t.mu; const double mu_old = mu2;
-        if (!no_barrier) {
-          if (o.barrier_strategy == CDDP_HIP_BARRIER_ADAPTIVE) {
-            const double kkt = std::max(std::max(t.inf_pr, sdu), t.inf_comp);
-            const double threshold = std::max(o.barrier_mu_update_factor * mu2, 2.0 * mu2);
-            if (kkt <= threshold) {
-              double factor = o.barrier_mu_update_factor;
-              if (mu2 > 1e-20) {
-                const double ratio = kkt / std::max(mu2, 1e-20);
-                if (ratio < 0.01) factor = 0.1 * o.barrier_mu_update_factor;
-                else if (ratio < 0.1) factor = 0.3 * o.barrier_mu_update_factor;
-                else if (ratio < 0.5) factor = 0.6 * o.barrier_mu_update_factor;
-              }
-              const double linear = factor * mu2, superlinear = std::pow(mu2, o.barrier_mu_update_power);
-              mu2 = std::max(std::min(linear, superlinear), std::max(o.barrier_mu_min_value, o.tolerance / 100.0));
-            }
-          } else {
-            const double kkt = std::max(std::max(t.inf_pr, sdu * o.ipddp_barrier_update_dual_weight), t.inf_comp);
-            if (kkt <= o.ipddp_mu_kappa_epsilon * mu2) {
-              const double linear = o.barrier_mu_update_factor * mu2, superlinear = std::pow(mu2, o.barrier_mu_update_power);
-              mu2 = std::max(o.barrier_mu_min_value, std::min(linear, superlinear));
-            }
-          }
-        }
-        t.mu = mu2;
+        const double mu_old = t.mu;
+        t.mu = ip_barrier_update(c, t, Gx, has_barrier);
         std::vector<double> r, rx, hT((size_t)std::max(pT, 1), 0.0);
         if (hte) ti.eval(pl->user, nx, t.X.data() + (size_t)N * nx, nullptr, nullptr, hT.data(), nullptr, r, rx);
         double phi_n, theta_n, ipr, icomp;
-        ip_reductions_t(c, ti, t.S.data(), t.Y.data(), t.G.data(), t.ST.data(), t.YT.data(), t.GT.data(), t.LamT.data(), hT.data(), mu2, t.cost, phi_n, theta_n, ipr, icomp);
-        const double ftheta = std::max(theta_n, 1e-8);
-        const bool reset = (mu2 < mu_old) && (mu2 > 0.0);
-        if (reset) { t.filter.clear(); filter_accept(t.filter, t.phi, ftheta); }   // (:2629-2637: re-seeded because a terminal set exists)
-        else { filter_accept(t.filter, t.phi, ftheta); if ((int)t.filter.size() > o.ipddp_max_filter_size) filter_prune(t.filter); }
-        t.inf_pr = ipr; t.inf_comp = icomp; t.merit = t.phi = phi_n; t.filter_theta = ftheta;
-        t.theta = std::max(ftheta, std::max(o.ipddp_theta_0_floor, 1e-8));
+        ip_reductions_t(c, ti, t.S.data(), t.Y.data(), t.G.data(), t.ST.data(), t.YT.data(), t.GT.data(), t.LamT.data(), hT.data(), t.mu, t.cost, phi_n, theta_n, ipr, icomp);
+        ip_filter_update(o, t, mu_old, phi_n, theta_n, ipr, icomp, true);
         t.reg = reg_decrease(o, t.reg);
-        // ---- checkConvergence (:1953-2025)
-        const double sdu2 = scaled_inf_du(c, t, t.gGx);
-        const double pr = t.inf_pr, scomp = t.inf_comp, sn = t.step_norm;
-        int st = CDDP_HIP_STATUS_RUNNING; bool done = false;
-        if (no_barrier) {
-          if (pr < o.tolerance && sdu2 < o.tolerance) { st = CDDP_HIP_STATUS_OPTIMAL; done = true; }
-          else if (o.acceptable_tolerance > 0.0) {
-            const double sq = std::sqrt(o.acceptable_tolerance);
-            bool acc = (pr < sq && sdu2 < sq && t.iter > 50);
-            if (dJ > 0.0) acc = acc || (dJ < o.acceptable_tolerance && t.iter > 50 && pr < sq && sdu2 < sq);
-            if (acc) { st = CDDP_HIP_STATUS_ACCEPTABLE; done = true; }
-          }
-        } else {
-          const double tol = std::max(o.tolerance, o.ipddp_barrier_tol_mult * mu2);
-          if (pr < tol && sdu2 < tol && scomp < tol && sn < o.tolerance * 10.0) { st = CDDP_HIP_STATUS_OPTIMAL; done = true; }
-          else if (o.acceptable_tolerance > 0.0) {
-            const double at = std::sqrt(o.acceptable_tolerance);
-            const double bat = std::max(o.barrier_mu_min_value * 100.0, o.tolerance / 10.0);
-            const bool akkt = pr < at && sdu2 < at && scomp < at, bpc = mu2 <= bat;
-            bool acc = akkt && bpc && t.iter > 10 && std::fabs(dJ) < o.acceptable_tolerance;
-            acc = acc || (akkt && bpc && t.iter >= 1 && sn < o.tolerance * 10.0 && pr < 1e-4);
-            if (acc) { st = CDDP_HIP_STATUS_ACCEPTABLE; done = true; }
-          }
-        }
-        if (done) { t.status = st; t.done = true; }
+        const int st = ip_check_convergence(c, t, Gx, dJ, has_barrier);
+        if (st != CDDP_HIP_STATUS_RUNNING) { t.status = st; t.done = true; }
       } else {
-        // ---- handleForwardPassFailure (:2037-2082): a second increase when a barrier and terminal-equality rows coexist
-        t.reg = reg_increase(o, t.reg);
-        if (!no_barrier && hte) t.reg = reg_increase(o, t.reg);
-        if (t.reg >= o.reg_max_value) {
-          const double sdu = scaled_inf_du(c, t, t.gGx);
-          const double base = std::sqrt(std::max(o.acceptable_tolerance, o.tolerance));
-          const double at = no_barrier ? base : std::max(base, o.ipddp_barrier_tol_mult * t.mu);
-          const bool acc = o.acceptable_tolerance > 0.0 && t.inf_pr < at && sdu < at && (no_barrier || t.inf_comp < at);
-          t.status = acc ? CDDP_HIP_STATUS_ACCEPTABLE : CDDP_HIP_STATUS_REG_LIMIT; t.done = true;
-        }
+        ip_forward_failure(c, t, Gx, has_barrier, has_barrier && hte);
       }
       if (!t.done && it == o.max_iterations) { t.status = CDDP_HIP_STATUS_MAX_ITERATIONS; t.done = true; }
     };
-    par_for(B, n_threads, advance);
+    par_for(B, c.threads, advance);
     if (abort_seen.load() || aborted(pl)) return pfail(-50, "aborted by the caller (cddp_hip_plugin::abort_flag)");
   }
-  for (auto &t : T) if (!t.done) { t.status = CDDP_HIP_STATUS_MAX_ITERATIONS; t.done = true; }
-  if (Kout) std::copy(Kfin.begin(), Kfin.end(), Kout);
+  write_results(c, T, sw, clock, results, Xout, Uout, Kout);
   for (size_t b = 0; b < B; ++b) {
     const TTraj &t = T[b];
-    cddp_hip_result &r = results[b];
-    std::memset(&r, 0, sizeof(r));
-    r.final_objective = t.cost; r.merit_function = t.merit; r.inf_pr = t.inf_pr; r.inf_du = t.inf_du; r.inf_comp = t.inf_comp;
-    r.barrier_mu = t.mu; r.regularization = t.reg; r.alpha_pr = t.alpha_pr; r.alpha_du = t.alpha_du; r.step_norm = t.step_norm;
-    r.iterations = t.iter; r.status = t.status; r.n_backward = t.n_bwd; r.n_forward = t.n_fwd;
-    if (Xout) std::copy(t.X.begin(), t.X.end(), Xout + b * (N + 1) * nx);
-    if (Uout) std::copy(t.U.begin(), t.U.end(), Uout + b * N * nu);
     if (Tout) {   // [S_T (mT) | Y_T (mT) | Lambda_T (pT)] per trajectory
       double *o2 = Tout + b * (size_t)(2 * mT + pT);
       for (int i = 0; i < mT; ++i) { o2[i] = t.ST[i]; o2[mT + i] = t.YT[i]; }
       for (int i = 0; i < pT; ++i) o2[2 * mT + i] = t.LamT[i];
     }
   }
+  return 0;
+}
+
+// ======================================================================================================================
+// CLDDP and IPDDP without a terminal set: the per-trajectory work runs on c.threads host threads
+// ======================================================================================================================
+int ddp_solve(const Ctx &c, int device, int batch, const double *x0, const double *U0, const double *X0, cddp_hip_result *results,
+              double *Xout, double *Uout, double *Kout) {
+  const cddp_hip_plugin *pl = c.pl; const cddp_hip_options &o = *c.o;
+  const int nx = c.nx, nu = c.nu, m = c.m, N = c.N;
+  const size_t B = (size_t)batch;
+  BatchSweep sw(c, batch, m, !o.use_ilqr, Kout != nullptr);
+  { int rc = sw.open(device, m); if (rc) return rc; }
+  std::vector<Traj> T(B);
+  for (size_t b = 0; b < B; ++b)
+    initialize(c, T[b], x0 + b * nx, U0 ? U0 + b * N * nu : nullptr, X0 ? X0 + b * (N + 1) * nx : nullptr);
+  std::vector<double> Ubuf(B * N * nu);   // controls of the iterates (the CLDDP control box)
+  std::atomic<bool> abort_seen{false};
+  const StatClock clock;
+
+  for (int it = 1; it <= o.max_iterations; ++it) {
+    { const int go = iteration_start(c, T, clock); if (go < 0) return go; if (!go) break; }
+    // ---- precomputeDynamicsDerivatives / precomputeConstraintGradients on the host (cddp_solver_base.cpp:319-394,
+    //      ipddp_solver.cpp:2145-2250), cost derivatives (objective.hpp): the stacks of every running trajectory
+    auto fill_stacks = [&](size_t b) {   // (one host thread per trajectory when the caller allows it: cddp_hip_plugin_set_host_threads)
+      Traj &t = T[b];
+      if (t.done) return;
+      std::vector<double> tfx((size_t)nx * nx), tfu((size_t)nx * nu);
+      t.iter += 1;
+      for (int s = 0; s < N; ++s) {
+        const double *x = t.X.data() + (size_t)s * nx, *u = t.U.data() + (size_t)s * nu;
+        const size_t bs = b * N + s;
+        sw.linearise(b, s, x, u, tfx.data(), tfu.data());
+        if (m > 0) {
+          pl->constraints(pl->user, x, u, s, sw.gg.data() + bs * m, sw.gGx.data() + bs * m * nx, sw.gGu.data() + bs * m * nu);
+          // (g itself is the iterate's residual evaluated by the last accepted rollout; Jacobians are what is needed here)
+          std::copy(t.G.begin() + (size_t)s * m, t.G.begin() + (size_t)(s + 1) * m, sw.gg.begin() + bs * m);
+          std::copy(t.S.begin() + (size_t)s * m, t.S.begin() + (size_t)(s + 1) * m, sw.gs.begin() + bs * m);
+          std::copy(t.Y.begin() + (size_t)s * m, t.Y.begin() + (size_t)(s + 1) * m, sw.gy.begin() + bs * m);
+        }
+        if (!o.use_ilqr) sw.scaled_hessians(b, s, x, u);
+      }
+      pl->terminal_cost_derivatives(pl->user, t.X.data() + (size_t)N * nx, sw.VxN.data() + b * nx, sw.VxxN.data() + b * nx * nx);
+      std::copy(t.U.begin(), t.U.end(), Ubuf.begin() + b * N * nu);
+    };
+    par_for(B, c.threads, fill_stacks);
+    if (!c.ipddp() && pl->control_lower && pl->control_upper) {
+      int rc = cddp_hip_set_control_box(sw.h, pl->control_lower, pl->control_upper, Ubuf.data()); if (rc) return rc;
+    }
+    const int branch = !c.ipddp() ? CDDP_HIP_STACKS_CLDDP : (m > 0 ? CDDP_HIP_STACKS_IPDDP_PATH : CDDP_HIP_STACKS_IPDDP);
+    { int rc = sw.run(branch, T, 1.0, !o.use_ilqr && c.ipddp()); if (rc) return rc; }
+
+    auto advance = [&](size_t b) {
+      Traj &t = T[b];
+      if (t.done) return;
+      if (aborted(pl)) { abort_seen.store(true); return; }
+      if (!sw.replay(t, b)) { t.status = CDDP_HIP_STATUS_REG_LIMIT; t.done = true; return; }   // handleBackwardPassRegularizationLimit
+      t.dV0 = sw.dVb[b * 2]; t.dV1 = sw.dVb[b * 2 + 1]; t.inf_du = sw.s_du[b];
+      Gains g;
+      g.K = sw.Kb.data() + b * N * nu * nx; g.k = sw.kb.data() + b * N * nu; g.Vx = sw.Vxb.data() + b * (N + 1) * nx; g.Vxx = sw.Vxxb.data() + b * (N + 1) * nx * nx;
+      g.ky = g.Ky = g.ks = g.Ks = nullptr;
+      const double *Gx = (m > 0) ? sw.gGx.data() + b * N * m * nx : nullptr;
+      if (c.ipddp()) {
+        t.step_norm = sw.s_sn[b];
+        t.inf_pr = (m > 0) ? sw.s_pr[b] : 0.0; t.inf_comp = (m > 0) ? sw.s_comp[b] : 0.0;
+        t.apr_max = (m > 0) ? sw.s_apr[b] : 1.0; t.adu_max = (m > 0) ? sw.s_adu[b] : 1.0;
+        if (m > 0) { g.ky = sw.kyb.data() + b * N * m; g.ks = sw.ksb.data() + b * N * m; g.Ky = sw.Kyb.data() + b * N * m * nx; g.Ks = sw.Ksb.data() + b * N * m * nx; }
+      }
+      // ---- checkEarlyConvergence (clddp_solver.cpp:206-213 / ipddp_solver.cpp:925-958)
+      if (c.ipddp() ? ip_early_converged(c, t, Gx, m > 0) : t.inf_du < o.tolerance) { t.status = CDDP_HIP_STATUS_OPTIMAL; t.done = true; return; }
+      Trial best;
+      if (line_search(c, t, best, [&](double a) { return c.ipddp() ? forward_ipddp(c, t, g, a) : forward_clddp(c, t, g, a); })) {
+        // ---- applyForwardPassResult (cddp_solver_base.cpp:190-198, ipddp_solver.cpp:1878-1951)
+        const double dJ = t.cost - best.cost;
+        t.X.swap(best.X); t.U.swap(best.U);
+        t.cost = best.cost; t.merit = best.merit; t.alpha_pr = best.alpha_pr; t.alpha_du = c.ipddp() ? best.alpha_du : 1.0;
+        int st = CDDP_HIP_STATUS_RUNNING;
+        if (c.ipddp()) {
+          t.Lam.swap(best.Lam);
+          if (m > 0) { t.S.swap(best.S); t.Y.swap(best.Y); t.G.swap(best.G); }
+          t.inf_pr = best.inf_pr; t.inf_comp = best.inf_comp; t.phi = best.merit; t.filter_theta = best.theta; t.theta = best.theta;
+          const double mu_old = t.mu;
+          t.mu = ip_barrier_update(c, t, Gx, m > 0);
+          double phi, theta, ipr, icomp;
+          ip_reductions_t(c, kNoTerminal, t.S.data(), t.Y.data(), t.G.data(), nullptr, nullptr, nullptr, nullptr, nullptr, t.mu, t.cost, phi, theta, ipr, icomp);
+          ip_filter_update(o, t, mu_old, phi, theta, ipr, icomp, false);
+          t.reg = reg_decrease(o, t.reg);
+          st = ip_check_convergence(c, t, Gx, dJ, m > 0);
+        } else {
+          t.reg = reg_decrease(o, t.reg);
+          if (t.inf_du < o.tolerance) st = CDDP_HIP_STATUS_OPTIMAL;                                  // clddp_solver.cpp:264-277
+          else if (dJ > 0.0 && dJ < o.acceptable_tolerance) st = CDDP_HIP_STATUS_ACCEPTABLE;
+        }
+        if (st != CDDP_HIP_STATUS_RUNNING) { t.status = st; t.done = true; }
+      } else if (c.ipddp()) {
+        ip_forward_failure(c, t, Gx, m > 0, false);
+      } else {   // handleForwardPassFailure (cddp_solver_base.cpp:206-218)
+        t.reg = reg_increase(o, t.reg);
+        if (t.reg >= o.reg_max_value) { t.status = CDDP_HIP_STATUS_REG_LIMIT; t.done = true; }
+      }
+      if (!t.done && it == o.max_iterations) { t.status = CDDP_HIP_STATUS_MAX_ITERATIONS; t.done = true; }
+    };
+    par_for(B, c.threads, advance);
+    if (abort_seen.load() || aborted(pl)) return pfail(-50, "aborted by the caller (cddp_hip_plugin::abort_flag)");
+  }
+  write_results(c, T, sw, clock, results, Xout, Uout, Kout);
   return 0;
 }
 
@@ -1758,8 +1837,9 @@ static int plugin_solve_impl(const cddp_hip_plugin *pl, const cddp_hip_plugin_te
   if (!opt->use_ilqr && !pl->hessians) return pfail(-3, "use_ilqr=false needs the plug-in's Hessian callback");
 
   Ctx c; c.pl = pl; c.o = opt; c.solver = solver; c.nx = nx; c.nu = nu; c.m = m; c.N = N; c.dt = dt;
+  c.threads = (solver == CDDP_HIP_SOLVER_LOGDDP || solver == CDDP_HIP_SOLVER_MSIPDDP) ? 1 : host_threads(batch);
   { double al[CDDP_HIP_MAX_ALPHAS]; const int na = cddp_hip_build_alphas(opt, al, CDDP_HIP_MAX_ALPHAS); c.alphas.assign(al, al + na); }
-  const cddp_hip_options &o = *opt;
+  g_last_stats = PluginStats(); g_last_stats.threads = c.threads;
   // Terminal constraints: only IPDDP reads the terminal set (clddp / logddp / msipddp_solver.cpp never touch getTerminalConstraintSet)
   if (tc && tc->n_terminal > 0 && solver == CDDP_HIP_SOLVER_IPDDP) {
     if (tc->n_terminal > CDDP_HIP_PLUGIN_MAX_CONSTRAINTS || !tc->evaluate) return pfail(-2, "bad terminal-constraint description (%d objects)", tc->n_terminal);
@@ -1774,257 +1854,5 @@ static int plugin_solve_impl(const cddp_hip_plugin *pl, const cddp_hip_plugin_te
   }
   if (solver == CDDP_HIP_SOLVER_LOGDDP) return logddp_solve(c, device, batch, x0, U0, results, Xout, Uout, Kout);
   if (solver == CDDP_HIP_SOLVER_MSIPDDP) return msipddp_solve(c, device, batch, x0, U0, X0, results, Xout, Uout, Kout);
-
-  cddp_hip_stack_handle *sh = nullptr;
-  { int rc = cddp_hip_stacks_create(device, batch, nx, nu, m, N, &sh); if (rc) return rc; }
-  struct Guard { cddp_hip_stack_handle *h; ~Guard() { if (h) cddp_hip_stacks_destroy(h); } } guard{sh};
-
-  const size_t B = (size_t)batch;
-  std::vector<Traj> T(B);
-  for (size_t b = 0; b < B; ++b)
-    initialize(c, T[b], x0 + b * nx, U0 ? U0 + b * N * nu : nullptr, X0 ? X0 + b * (N + 1) * nx : nullptr);
-
-  // batch-major host stacks of the current iterates
-  std::vector<double> fx(B * N * nx * nx), fu(B * N * nx * nu), lx(B * N * nx), lu(B * N * nu), lxx(B * N * nx * nx), luu(B * N * nu * nu),
-      lux(B * N * nu * nx), VxN(B * nx), VxxN(B * nx * nx), Ubuf(B * N * nu);
-  std::vector<double> gy, gs, gg, gGx, gGu, Fxx, Fuu, Fux;
-  if (m > 0) { gy.resize(B * N * m); gs = gy; gg = gy; gGx.resize(B * N * m * nx); gGu.resize(B * N * m * nu); }
-  if (!o.use_ilqr) { Fxx.resize(B * N * nx * nx * nx); Fuu.resize(B * N * nx * nu * nu); Fux.resize(B * N * nx * nu * nx); }
-  std::vector<double> Kb(B * N * nu * nx), kb(B * N * nu), Vxb(B * (N + 1) * nx), Vxxb(B * (N + 1) * nx * nx), dVb(B * 2);
-  // K_u_ of each trajectory's LAST backward pass (the reference's solver object stops sweeping a problem when it ends; the batch keeps
-  // sweeping the others): the slice is kept at every sweep the trajectory still takes part in
-  std::vector<double> Kfin(Kout ? B * N * nu * nx : 0, 0.0);
-  std::vector<double> kyb, Kyb, ksb, Ksb, dXb;
-  if (m > 0) { kyb.resize(B * N * m); ksb = kyb; Kyb.resize(B * N * m * nx); Ksb = Kyb; dXb.resize(B * (N + 1) * nx); }
-  std::vector<double> regv(B), muv(B), s_reg(B), s_du(B), s_pr(B), s_comp(B), s_sn(B), s_apr(B), s_adu(B);
-  std::vector<int32_t> okv(B);
-  const bool first_rule = !o.enable_parallel;
-  std::atomic<bool> abort_seen{false};
-  const int n_threads = host_threads((int)B);
-  const StatClock total_clock;
-  g_last_stats = PluginStats(); g_last_stats.threads = n_threads;
-  const auto wall0 = std::chrono::steady_clock::now();
-
-  for (int it = 1; it <= o.max_iterations; ++it) {
-    bool any = false;
-    for (auto &t : T) any = any || !t.done;
-    if (!any) break;
-    if (aborted(pl)) return pfail(-50, "aborted by the caller (cddp_hip_plugin::abort_flag)");
-    if (o.max_cpu_time > 0.0) {   // cddp_solver_base.cpp:77-90 (whole elapsed milliseconds)
-      const double el_ms = (double)std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::steady_clock::now() - wall0).count();
-      if (el_ms > o.max_cpu_time * 1000.0) {
-        for (auto &t : T) if (!t.done) { t.iter += 1; t.status = CDDP_HIP_STATUS_MAX_CPU_TIME; t.done = true; }
-        break;
-      }
-    }
-    // ---- precomputeDynamicsDerivatives / precomputeConstraintGradients on the host (cddp_solver_base.cpp:319-394,
-    //      ipddp_solver.cpp:2145-2250), cost derivatives (objective.hpp): the stacks of every running trajectory
-    auto fill_stacks = [&](size_t b) {   // (one host thread per trajectory when the caller allows it: cddp_hip_plugin_set_host_threads)
-      Traj &t = T[b];
-      std::vector<double> tfx((size_t)nx * nx), tfu((size_t)nx * nu);
-      regv[b] = t.done ? std::max(t.reg, o.reg_min_value) : t.reg;
-      muv[b] = (t.mu > 0.0) ? t.mu : 1.0;
-      if (t.done) return;
-      t.iter += 1;
-      for (int s = 0; s < N; ++s) {
-        const double *x = t.X.data() + (size_t)s * nx, *u = t.U.data() + (size_t)s * nu;
-        const size_t bs = b * N + s;
-        pl->jacobians(pl->user, x, u, s * dt, tfx.data(), tfu.data());
-        for (int i = 0; i < nx; ++i)
-          for (int j = 0; j < nx; ++j) { double a = dt * tfx[i * nx + j]; if (i == j) a += 1.0; fx[(bs * nx + i) * nx + j] = a; }   // A = I + dt f_x
-        for (int i = 0; i < nx * nu; ++i) fu[bs * nx * nu + i] = dt * tfu[i];                                                      // B = dt f_u
-        pl->running_cost_derivatives(pl->user, x, u, s, lx.data() + bs * nx, lu.data() + bs * nu, lxx.data() + bs * nx * nx,
-                                     luu.data() + bs * nu * nu, lux.data() + bs * nu * nx);
-        if (m > 0) {
-          pl->constraints(pl->user, x, u, s, gg.data() + bs * m, gGx.data() + bs * m * nx, gGu.data() + bs * m * nu);
-          // (g itself is the iterate's residual evaluated by the last accepted rollout; Jacobians are what is needed here)
-          std::copy(t.G.begin() + (size_t)s * m, t.G.begin() + (size_t)(s + 1) * m, gg.begin() + bs * m);
-          std::copy(t.S.begin() + (size_t)s * m, t.S.begin() + (size_t)(s + 1) * m, gs.begin() + bs * m);
-          std::copy(t.Y.begin() + (size_t)s * m, t.Y.begin() + (size_t)(s + 1) * m, gy.begin() + bs * m);
-        }
-        if (!o.use_ilqr) {
-          double *pxx = Fxx.data() + bs * nx * nx * nx, *puu = Fuu.data() + bs * nx * nu * nu, *pux = Fux.data() + bs * nx * nu * nx;
-          pl->hessians(pl->user, x, u, s * dt, pxx, puu, pux);
-          for (int e = 0; e < nx * nx * nx; ++e) pxx[e] = dt * pxx[e];   // F_xx_[t][i] = dt f_xx[i] (cddp_solver_base.cpp:346-356)
-          for (int e = 0; e < nx * nu * nu; ++e) puu[e] = dt * puu[e];
-          for (int e = 0; e < nx * nu * nx; ++e) pux[e] = dt * pux[e];
-        }
-      }
-      pl->terminal_cost_derivatives(pl->user, t.X.data() + (size_t)N * nx, VxN.data() + b * nx, VxxN.data() + b * nx * nx);
-      std::copy(t.U.begin(), t.U.end(), Ubuf.begin() + b * N * nu);
-    };
-    par_for(B, n_threads, fill_stacks);
-    const StatClock gpu_clock;
-    { int rc = cddp_hip_set_stacks(sh, fx.data(), fu.data(), lx.data(), lu.data(), lxx.data(), luu.data(), lux.data(), VxN.data(), VxxN.data()); if (rc) return rc; }
-    if (m > 0) { int rc = cddp_hip_set_constraint_stacks(sh, gy.data(), gs.data(), gg.data(), gGx.data(), gGu.data()); if (rc) return rc; }
-    if (!o.use_ilqr && c.ipddp()) { int rc = cddp_hip_set_hessian_stacks(sh, Fxx.data(), Fuu.data(), Fux.data()); if (rc) return rc; }
-    if (!c.ipddp() && pl->control_lower && pl->control_upper) {
-      int rc = cddp_hip_set_control_box(sh, pl->control_lower, pl->control_upper, Ubuf.data()); if (rc) return rc;
-    }
-    // ---- backwardPass of the whole batch on the GPU, incl. the "increase regularisation and retry" loop (:93-111)
-    const int branch = !c.ipddp() ? CDDP_HIP_STACKS_CLDDP : (m > 0 ? CDDP_HIP_STACKS_IPDDP_PATH : CDDP_HIP_STACKS_IPDDP);
-    { int rc = cddp_hip_stacks_backward(sh, branch, opt, regv.data(), m > 0 ? muv.data() : nullptr, 1, okv.data()); if (rc) return rc; }
-    { int rc = cddp_hip_stacks_get_gains(sh, Kb.data(), kb.data(), Vxb.data(), Vxxb.data(), dVb.data()); if (rc) return rc; }
-    if (Kout) for (size_t b = 0; b < B; ++b) if (!T[b].done) std::copy(Kb.begin() + b * N * nu * nx, Kb.begin() + (b + 1) * N * nu * nx, Kfin.begin() + b * N * nu * nx);
-    if (m > 0) { int rc = cddp_hip_stacks_get_constraint_gains(sh, kyb.data(), Kyb.data(), ksb.data(), Ksb.data(), dXb.data()); if (rc) return rc; }
-    { int rc = cddp_hip_stacks_get_scalars(sh, s_reg.data(), s_du.data(), s_pr.data(), s_comp.data(), s_sn.data(), s_apr.data(), s_adu.data()); if (rc) return rc; }
-    g_last_stats.gpu_section_ms += gpu_clock.ms(); g_last_stats.kernel_ms += cddp_hip_stacks_last_kernel_ms(sh); g_last_stats.sweeps += 1;
-
-    auto advance = [&](size_t b) {
-      Traj &t = T[b];
-      if (t.done) return;
-      if (aborted(pl)) { abort_seen.store(true); return; }
-      // sweeps the retry loop ran: replay the schedule from the regularisation it started with
-      { int nb = 1; double r = t.reg; while (r < s_reg[b] && nb < 64) { r = reg_increase(o, r); ++nb; }
-        if (!okv[b] && nb > 1) --nb;   // the loop stops when the schedule reaches reg_max: no sweep is run there
-        t.n_bwd += nb; }
-      t.reg = s_reg[b];
-      if (!okv[b]) { t.status = CDDP_HIP_STATUS_REG_LIMIT; t.done = true; return; }   // handleBackwardPassRegularizationLimit
-      t.dV0 = dVb[b * 2]; t.dV1 = dVb[b * 2 + 1]; t.inf_du = s_du[b];
-      Gains g;
-      g.K = Kb.data() + b * N * nu * nx; g.k = kb.data() + b * N * nu; g.Vx = Vxb.data() + b * (N + 1) * nx; g.Vxx = Vxxb.data() + b * (N + 1) * nx * nx;
-      g.ky = g.Ky = g.ks = g.Ks = nullptr;
-      std::vector<double> Gx_t;
-      if (c.ipddp()) {
-        t.step_norm = s_sn[b];
-        t.inf_pr = (m > 0) ? s_pr[b] : 0.0; t.inf_comp = (m > 0) ? s_comp[b] : 0.0;
-        t.apr_max = (m > 0) ? s_apr[b] : 1.0; t.adu_max = (m > 0) ? s_adu[b] : 1.0;
-        if (m > 0) {
-          g.ky = kyb.data() + b * N * m; g.ks = ksb.data() + b * N * m; g.Ky = Kyb.data() + b * N * m * nx; g.Ks = Ksb.data() + b * N * m * nx;
-          Gx_t.assign(gGx.begin() + b * N * m * nx, gGx.begin() + (b + 1) * N * m * nx);
-        }
-      }
-      // ---- checkEarlyConvergence (clddp_solver.cpp:206-213 / ipddp_solver.cpp:925-958)
-      bool conv = false;
-      if (!c.ipddp()) conv = t.inf_du < o.tolerance;
-      else {
-        const double sdu = scaled_inf_du(c, t, Gx_t);
-        if (m == 0) conv = (t.inf_pr < o.tolerance && sdu < o.tolerance);
-        else {
-          const double tol = std::max(o.tolerance, o.ipddp_barrier_tol_mult * t.mu);
-          conv = (t.inf_pr < tol && sdu < tol && t.inf_comp < tol && std::fabs(t.alpha_pr) * t.step_norm < o.tolerance * 10.0);
-        }
-      }
-      if (conv) { t.status = CDDP_HIP_STATUS_OPTIMAL; t.done = true; return; }
-      // ---- performForwardPass (cddp_solver_base.cpp:248-317): first success, or lowest merit among the successes
-      Trial best; bool have = false;
-      int walked = 0;
-      for (double a : c.alphas) {
-        Trial r = c.ipddp() ? forward_ipddp(c, t, g, a) : forward_clddp(c, t, g, a);
-        ++walked;
-        if (!r.success) continue;
-        if (first_rule) { best = std::move(r); have = true; break; }
-        if (!have || r.merit < best.merit) { best = std::move(r); have = true; }
-      }
-      t.n_fwd += first_rule ? walked : (int)c.alphas.size();
-      if (have) {
-        // ---- applyForwardPassResult (cddp_solver_base.cpp:190-198, ipddp_solver.cpp:1878-1951)
-        const double dJ = t.cost - best.cost;
-        t.X.swap(best.X); t.U.swap(best.U);
-        t.cost = best.cost; t.merit = best.merit; t.alpha_pr = best.alpha_pr; t.alpha_du = c.ipddp() ? best.alpha_du : 1.0;
-        int st = CDDP_HIP_STATUS_RUNNING; bool done = false;
-        if (c.ipddp()) {
-          t.Lam.swap(best.Lam);
-          if (m > 0) { t.S.swap(best.S); t.Y.swap(best.Y); t.G.swap(best.G); }
-          t.inf_pr = best.inf_pr; t.inf_comp = best.inf_comp; t.phi = best.merit; t.filter_theta = best.theta; t.theta = best.theta;
-          // ---- updateBarrierParameters(true) (ipddp_solver.cpp:2548-2660)
-          const double sdu = scaled_inf_du(c, t, Gx_t);
-          double mu = t.mu; const double mu_old = mu;
-          if (m > 0) {
-            if (o.barrier_strategy == CDDP_HIP_BARRIER_ADAPTIVE) {
-              const double kkt = std::max(std::max(t.inf_pr, sdu), t.inf_comp);
-              const double threshold = std::max(o.barrier_mu_update_factor * mu, 2.0 * mu);
-              if (kkt <= threshold) {
-                double factor = o.barrier_mu_update_factor;
-                if (mu > 1e-20) {
-                  const double ratio = kkt / std::max(mu, 1e-20);
-                  if (ratio < 0.01) factor = 0.1 * o.barrier_mu_update_factor;
-                  else if (ratio < 0.1) factor = 0.3 * o.barrier_mu_update_factor;
-                  else if (ratio < 0.5) factor = 0.6 * o.barrier_mu_update_factor;
-                }
-                const double linear = factor * mu, superlinear = std::pow(mu, o.barrier_mu_update_power);
-                mu = std::max(std::min(linear, superlinear), std::max(o.barrier_mu_min_value, o.tolerance / 100.0));
-              }
-            } else {
-              const double kkt = std::max(std::max(t.inf_pr, sdu * o.ipddp_barrier_update_dual_weight), t.inf_comp);
-              if (kkt <= o.ipddp_mu_kappa_epsilon * mu) {
-                const double linear = o.barrier_mu_update_factor * mu, superlinear = std::pow(mu, o.barrier_mu_update_power);
-                mu = std::max(o.barrier_mu_min_value, std::min(linear, superlinear));
-              }
-            }
-          }
-          t.mu = mu;
-          double phi_n = t.cost, theta_n = 0.0, ipr = 0.0, icomp = 0.0;
-          if (m > 0) ip_reductions(c, t.S.data(), t.Y.data(), t.G.data(), mu, t.cost, phi_n, theta_n, ipr, icomp);
-          const double ftheta = std::max(theta_n, 1e-8);
-          const bool reset = (mu < mu_old) && (mu > 0.0);
-          if (reset) t.filter.clear();   // re-seeded only when terminal constraints exist (:2629-2637): none here
-          else { filter_accept(t.filter, t.phi, ftheta); if ((int)t.filter.size() > o.ipddp_max_filter_size) filter_prune(t.filter); }
-          t.inf_pr = ipr; t.inf_comp = icomp; t.merit = t.phi = phi_n; t.filter_theta = ftheta;
-          t.theta = std::max(ftheta, std::max(o.ipddp_theta_0_floor, 1e-8));
-          t.reg = reg_decrease(o, t.reg);
-          // ---- checkConvergence (ipddp_solver.cpp:1953-2025)
-          const double sdu2 = scaled_inf_du(c, t, Gx_t);
-          const double pr = t.inf_pr, scomp = t.inf_comp, sn = t.step_norm;
-          if (m == 0) {
-            if (pr < o.tolerance && sdu2 < o.tolerance) { st = CDDP_HIP_STATUS_OPTIMAL; done = true; }
-            else if (o.acceptable_tolerance > 0.0) {
-              const double sq = std::sqrt(o.acceptable_tolerance);
-              bool acc = (pr < sq && sdu2 < sq && t.iter > 50);
-              if (dJ > 0.0) acc = acc || (dJ < o.acceptable_tolerance && t.iter > 50 && pr < sq && sdu2 < sq);
-              if (acc) { st = CDDP_HIP_STATUS_ACCEPTABLE; done = true; }
-            }
-          } else {
-            const double tol = std::max(o.tolerance, o.ipddp_barrier_tol_mult * mu);
-            if (pr < tol && sdu2 < tol && scomp < tol && sn < o.tolerance * 10.0) { st = CDDP_HIP_STATUS_OPTIMAL; done = true; }
-            else if (o.acceptable_tolerance > 0.0) {
-              const double at = std::sqrt(o.acceptable_tolerance);
-              const double bat = std::max(o.barrier_mu_min_value * 100.0, o.tolerance / 10.0);
-              const bool akkt = pr < at && sdu2 < at && scomp < at, bpc = mu <= bat;
-              bool acc = akkt && bpc && t.iter > 10 && std::fabs(dJ) < o.acceptable_tolerance;
-              acc = acc || (akkt && bpc && t.iter >= 1 && sn < o.tolerance * 10.0 && pr < 1e-4);
-              if (acc) { st = CDDP_HIP_STATUS_ACCEPTABLE; done = true; }
-            }
-          }
-        } else {
-          t.reg = reg_decrease(o, t.reg);
-          if (t.inf_du < o.tolerance) { st = CDDP_HIP_STATUS_OPTIMAL; done = true; }                      // clddp_solver.cpp:264-277
-          else if (dJ > 0.0 && dJ < o.acceptable_tolerance) { st = CDDP_HIP_STATUS_ACCEPTABLE; done = true; }
-        }
-        if (done) { t.status = st; t.done = true; }
-      } else {
-        // ---- handleForwardPassFailure (cddp_solver_base.cpp:206-218, ipddp_solver.cpp:2037-2082)
-        t.reg = reg_increase(o, t.reg);
-        if (t.reg >= o.reg_max_value) {
-          int st = CDDP_HIP_STATUS_REG_LIMIT;
-          if (c.ipddp()) {
-            const double sdu = scaled_inf_du(c, t, Gx_t);
-            const double base = std::sqrt(std::max(o.acceptable_tolerance, o.tolerance));
-            const double at = (m == 0) ? base : std::max(base, o.ipddp_barrier_tol_mult * t.mu);
-            if (o.acceptable_tolerance > 0.0 && t.inf_pr < at && sdu < at && (m == 0 || t.inf_comp < at)) st = CDDP_HIP_STATUS_ACCEPTABLE;
-          }
-          t.status = st; t.done = true;
-        }
-      }
-      if (!t.done && it == o.max_iterations) { t.status = CDDP_HIP_STATUS_MAX_ITERATIONS; t.done = true; }
-    };
-    par_for(B, n_threads, advance);
-    if (abort_seen.load() || aborted(pl)) return pfail(-50, "aborted by the caller (cddp_hip_plugin::abort_flag)");
-  }
-  for (auto &t : T) if (!t.done) { t.status = CDDP_HIP_STATUS_MAX_ITERATIONS; t.done = true; }   // max_iterations <= 0
-  g_last_stats.total_ms = total_clock.ms();
-
-  // ---- CDDPSolution fields (cddp_solver_base.cpp:161-171, ipddp_solver.cpp:2090-2097); feedback gains = K_u_ of the last sweep
-  if (Kout) std::copy(Kfin.begin(), Kfin.end(), Kout);
-  for (size_t b = 0; b < B; ++b) {
-    const Traj &t = T[b];
-    cddp_hip_result &r = results[b];
-    std::memset(&r, 0, sizeof(r));
-    r.final_objective = t.cost; r.merit_function = t.merit; r.inf_pr = t.inf_pr; r.inf_du = t.inf_du; r.inf_comp = t.inf_comp;
-    r.barrier_mu = t.mu; r.regularization = t.reg; r.alpha_pr = t.alpha_pr; r.alpha_du = t.alpha_du; r.step_norm = t.step_norm;
-    r.iterations = t.iter; r.status = t.status; r.n_backward = t.n_bwd; r.n_forward = t.n_fwd;
-    if (Xout) std::copy(t.X.begin(), t.X.end(), Xout + b * (N + 1) * nx);
-    if (Uout) std::copy(t.U.begin(), t.U.end(), Uout + b * N * nu);
-  }
-  return 0;
+  return ddp_solve(c, device, batch, x0, U0, X0, results, Xout, Uout, Kout);
 }

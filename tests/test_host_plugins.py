@@ -451,6 +451,10 @@ def test_plugin_solve_with_terminal_constraints_against_the_twin(api, pycddp, ca
     assert sv._needs_host_plugins()
     sol = sv.solve(pycddp.SolverType.IPDDP)
     assert sol.route == "plugin"
+    import ctypes as C
+    sw, th = C.c_int(), C.c_int()   # cddp_hip_plugin_last_stats describes the terminal-constraint solve, too
+    assert api.load_hip().cddp_hip_plugin_last_stats(None, None, None, C.byref(sw), C.byref(th)) == 0
+    assert sw.value >= sol.iterations_completed and th.value >= 1
     tw = T.Twin(dict(solver="IPDDP", model=TwinQSS() if plant == "qss" else TwinDI(), integrator="euler", dt=dt, N=N, Q=Qs * np.eye(nx), R=Rs * np.eye(1),
                      Qf=Qfs * np.eye(nx), xref=list(goal), constraints=cons, terminal=term,
                      options=dict(max_iterations=40, tolerance=1e-6, acceptable_tolerance=1e-6, reg_initial_value=1e-6, mu_initial=1e-1, use_ilqr=use_ilqr)))

@@ -183,3 +183,7 @@ def test_logddp_with_a_python_plant(api, pycddp, oracle_built):
     orc = api.Oracle(p); orc.set_initial(np.array([np.pi, 0.0]), None); r = orc.solve()
     assert (s.status_message, s.iterations_completed) == (api.STATUS_STRINGS[r["status"]], r["iterations"])
     assert abs(s.final_objective - r["final_objective"]) < 1e-9
+    import ctypes as C
+    sw, th = C.c_int(), C.c_int()   # cddp_hip_plugin_last_stats describes the LogDDP solve, too
+    assert api.load_hip().cddp_hip_plugin_last_stats(None, None, None, C.byref(sw), C.byref(th)) == 0
+    assert sw.value >= s.iterations_completed and th.value >= 1

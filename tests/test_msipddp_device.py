@@ -359,7 +359,12 @@ def test_facade_solve_batch_runs_on_the_resident_kernels(api, oracle_built):
         assert one.route == "resident" and (one.status_message, one.iterations_completed) == (sols[b].status_message, sols[b].iterations_completed)
         assert one.final_objective == sols[b].final_objective and np.array_equal(np.stack(one.control_trajectory), np.stack(sols[b].control_trajectory))
     sv.msipddp_route = "plugin"; sv._X = None; sv._U = None
-    assert sv.solve(pycddp.SolverType.MSIPDDP).route == "plugin"
+    one = sv.solve(pycddp.SolverType.MSIPDDP)
+    assert one.route == "plugin"
+    import ctypes as C
+    sw, th = C.c_int(), C.c_int()   # cddp_hip_plugin_last_stats describes the MSIPDDP plug-in solve, too
+    assert api.load_hip().cddp_hip_plugin_last_stats(None, None, None, C.byref(sw), C.byref(th)) == 0
+    assert sw.value >= one.iterations_completed and th.value >= 1
     sv.msipddp_route = "auto"
     su = pycddp.CDDP(np.zeros(3), np.array([2.0, 2.0, 1.0]), 20, 0.03, o)
     su.set_dynamical_system(pycddp.Unicycle(0.03, "euler"))
