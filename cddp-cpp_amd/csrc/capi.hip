@@ -55,6 +55,7 @@ static __global__ void k_mark_cpu_time(DevBuf d) {
 
 int cddp_host_model_eval(int model, int integrator, double dt, const double *params, int nx, int nu, const double *x, const double *u, double *x_next,
                          double *fx, double *fu, double *fxx, double *fuu, double *fux, std::string &err);   // host_models.cpp
+int cddp_host_model_params(int model, int nx, int nu, const double *in, double *out, std::string &err);         // host_models.cpp
 
 namespace {
 
@@ -78,7 +79,7 @@ const std::vector<KernelSet> &registry() {
     std::vector<KernelSet> r;
     register_pendulum(r); register_cartpole(r); register_unicycle(r); register_lti(r);
     register_quadrotor(r); register_quad12(r); register_manipulator(r); register_manip7(r); register_terminal(r); register_statebox(r);
-    register_vehicles(r);
+    register_vehicles(r); register_spacecraft(r);
     return r;
   }();
   return v;
@@ -158,7 +159,15 @@ int pool_put(ProblemDev &P, int &top, const double *src, int n) {
 bool model_has_hessians(int model) {
   return model == CDDP_HIP_MODEL_PENDULUM || model == CDDP_HIP_MODEL_CARTPOLE || model == CDDP_HIP_MODEL_UNICYCLE || model == CDDP_HIP_MODEL_LTI ||
          model == CDDP_HIP_MODEL_BICYCLE || model == CDDP_HIP_MODEL_CAR || model == CDDP_HIP_MODEL_MANIPULATOR || model == CDDP_HIP_MODEL_HCW ||
-         model == CDDP_HIP_MODEL_QUADROTOR || model == CDDP_HIP_MODEL_QUADROTOR_EULER12 || model == CDDP_HIP_MODEL_MANIPULATOR7;   // round 4: blocked second-order duals
+         model == CDDP_HIP_MODEL_QUADROTOR || model == CDDP_HIP_MODEL_QUADROTOR_EULER12 || model == CDDP_HIP_MODEL_MANIPULATOR7 ||   // round 4: blocked second-order duals
+         model == CDDP_HIP_MODEL_EULER_ATTITUDE || model == CDDP_HIP_MODEL_QUATERNION_ATTITUDE || model == CDDP_HIP_MODEL_MRP_ATTITUDE ||
+         model == CDDP_HIP_MODEL_SPACECRAFT_LANDING2D;   // (SpacecraftTwobody: none -- the reference's cross Hessian throws)
+}
+
+// the refusal of options.use_ilqr = 0 for a plant without Hessian tensors
+int fail_no_hessians(int model) {
+  if (model == CDDP_HIP_MODEL_SPACECRAFT_TWOBODY) return fail(-3, "use_ilqr=false: %s", SpacecraftTwobodyModel::kNoHessMsg);
+  return fail(-3, "use_ilqr=false needs the plant's Hessian tensors, which model id %d does not have", model);
 }
 
 // cddp_hip_problem -> ProblemDev (constraints sorted by name as std::map iterates)
@@ -178,12 +187,14 @@ int flatten(const cddp_hip_problem *p, ProblemDev &P) {
   // is an endless loop on the reference's host and would be a wedged queue here
   if (!(p->options.reg_update_factor > 1.0) || !(p->options.reg_max_value > 0.0))
     return fail(-2, "regularization.update_factor must be > 1 and max_value > 0 (got %g, %g)", p->options.reg_update_factor, p->options.reg_max_value);
-  if (!p->options.use_ilqr && !model_has_hessians(p->model))
-    return fail(-3, "use_ilqr=false needs the plant's Hessian tensors, which model id %d does not have", p->model);
+  if (!p->options.use_ilqr && !model_has_hessians(p->model)) return fail_no_hessians(p->model);
   P.solver = p->solver; P.model = p->model; P.integrator = p->integrator;
   P.nx = p->nx; P.nu = p->nu; P.N = p->horizon; P.dt = p->dt; P.opt = p->options;
   P.ls_rule = p->options.enable_parallel ? CDDP_HIP_LS_BEST_MERIT : CDDP_HIP_LS_FIRST_SUCCESS;
-  for (int i = 0; i < CDDP_HIP_MAX_MODEL_PARAMS; ++i) P.mp[i] = p->model_params[i];
+  {
+    std::string err;
+    if (cddp_host_model_params(p->model, p->nx, p->nu, p->model_params, P.mp, err)) return fail(-2, "%s", err.c_str());
+  }
   if (p->model == CDDP_HIP_MODEL_CAR) P.mp[1] = p->dt;   // the car is a discrete plant: its step uses the timestep (car.cpp:24-60)
   if (p->model == CDDP_HIP_MODEL_LTI) {
     if (!p->lti_A || !p->lti_B) return fail(-2, "LTI model needs lti_A and lti_B");
@@ -335,7 +346,9 @@ int cddp_hip_model_eval(int model, int integrator, double dt, const double *mode
                         double *x_next, double *fx, double *fu, double *fxx, double *fuu, double *fux) {
   if (!model_params || !x || !u) return fail(-2, "cddp_hip_model_eval: null argument");
   std::string err;
-  const int rc = cddp_host_model_eval(model, integrator, dt, model_params, nx, nu, x, u, x_next, fx, fu, fxx, fuu, fux, err);
+  double mp[CDDP_HIP_MAX_MODEL_PARAMS];
+  if (cddp_host_model_params(model, nx, nu, model_params, mp, err)) return fail(-2, "cddp_hip_model_eval: %s", err.c_str());
+  const int rc = cddp_host_model_eval(model, integrator, dt, mp, nx, nu, x, u, x_next, fx, fu, fxx, fuu, fux, err);
   return rc == 0 ? 0 : fail(rc, "cddp_hip_model_eval: %s", err.c_str());
 }
 const char *cddp_hip_last_error(void) { return g_err.c_str(); }
@@ -704,8 +717,7 @@ static int in_set_options(Inner *h, const cddp_hip_options *opt) {
   if (!h || !opt) return fail(-1, "null argument");
   if (!(opt->reg_update_factor > 1.0) || !(opt->reg_max_value > 0.0))
     return fail(-2, "regularization.update_factor must be > 1 and max_value > 0 (got %g, %g)", opt->reg_update_factor, opt->reg_max_value);
-  if (!opt->use_ilqr && !model_has_hessians(h->P.model))
-    return fail(-3, "use_ilqr=false needs the plant's Hessian tensors, which model id %d does not have", h->P.model);
+  if (!opt->use_ilqr && !model_has_hessians(h->P.model)) return fail_no_hessians(h->P.model);
   HIPCHK(hipSetDevice(h->device));
   double al[CDDP_HIP_MAX_ALPHAS];
   const int na = cddp_hip_build_alphas(opt, al, CDDP_HIP_MAX_ALPHAS);

@@ -779,6 +779,262 @@ struct Manip7Model {
   }
 };
 
+// ================================================================================ spacecraft plants (nx <= 8)
+// Jacobian by forward-mode duals seeded in column blocks of BS variables: one evaluation of F per block of z = [x, u].  Forward mode
+// is component-wise in the seeds, so every column equals, bit for bit, the column of the full DualN<NX + NU> evaluation (ad_jacobian);
+// the point is the register file: 4 doubles per dual number instead of NX + NU + 1 keeps the attitude plants' derivative fill and
+// sweep kernels free of scratch.
+template <class F, int NX, int NU, int BS>
+DEV void ad_jacobian_blocked(const double *p, const double *x, const double *u, double *Fx, double *Fu) {
+  constexpr int NP = NX + NU, NBK = (NP + BS - 1) / BS;
+  typedef DualN<BS> D;
+#pragma unroll
+  for (int I = 0; I < NBK; ++I) {
+    D xs[NX], us[NU], xd[NX];
+#pragma unroll
+    for (int v = 0; v < NP; ++v) {
+      D z(v < NX ? x[v] : u[v - NX]);
+      if (v / BS == I) z.d[v - I * BS] = 1.0;
+      if (v < NX) xs[v] = z; else us[v - NX] = z;
+    }
+    F::template eval<D>(p, xs, us, xd);
+#pragma unroll
+    for (int i = 0; i < NX; ++i)
+#pragma unroll
+      for (int c = 0; c < BS; ++c) {
+        const int v = I * BS + c;
+        if (v < NX) Fx[i * NX + v] = xd[i].d[c];
+        else if (v < NP) Fu[i * NU + (v - NX)] = xd[i].d[c];
+      }
+  }
+}
+
+// Rigid-body rotational dynamics shared by the three attitude plants (euler_attitude.cpp:47-49 and its twins):
+//   d(omega)/dt = I^-1 (-skew(omega) (I omega) + tau),   I = p[0..8], I^-1 = p[9..17] (row-major; host_models.cpp fills I^-1 as Eigen's
+// fixed-size inverse does).  The zero entries of -skew(omega) are left out of the products (x + 0 * y == x for finite operands).
+template <class S>
+DEV void rigid_body_rates(const double *p, const S *w, const S *tau, S *wd) {
+  S h[3], v[3];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) h[i] = (S(p[3 * i]) * w[0] + S(p[3 * i + 1]) * w[1]) + S(p[3 * i + 2]) * w[2];
+  v[0] = (w[2] * h[1] - w[1] * h[2]) + tau[0];
+  v[1] = (w[0] * h[2] - w[2] * h[0]) + tau[1];
+  v[2] = (w[1] * h[0] - w[0] * h[1]) + tau[2];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) wd[i] = (S(p[9 + 3 * i]) * v[0] + S(p[9 + 3 * i + 1]) * v[1]) + S(p[9 + 3 * i + 2]) * v[2];
+}
+
+// ---------------------------------------------------------------------------- EulerAttitude (euler_attitude.cpp:33-52, .hpp:159-180)
+// State [psi, theta, phi, wx, wy, wz] (ZYX angles), control [tau_x, tau_y, tau_z].  Jacobians and Hessians: autodiff of the autodiff
+// expression (:54-76, :78-147), which is the value expression on duals.  The |cos theta| < 1e-9 guard replaces cos theta by a CONSTANT
+// +-1e-9 (zero derivative), as T(1e-9 * sign) does there; tan theta is not guarded.
+struct EulerAttitudeDyn {
+  template <class S>
+  DEV static void eval(const double *p, const S *x, const S *u, S *xd) {
+    const S theta = x[1], phi = x[2];
+    const S s_phi = dsin(phi), c_phi = dcos(phi);
+    const S c_theta = dcos(theta), tan_theta = dtan(theta);
+    S cos_theta_safe = c_theta;
+    if (fabs(dval(c_theta)) < 1e-9) cos_theta_safe = S(dval(c_theta) >= 0 ? 1e-9 : -1e-9);
+    xd[0] = (s_phi / cos_theta_safe) * x[4] + (c_phi / cos_theta_safe) * x[5];
+    xd[1] = c_phi * x[4] + (-s_phi) * x[5];
+    xd[2] = (x[3] + (s_phi * tan_theta) * x[4]) + (c_phi * tan_theta) * x[5];
+    rigid_body_rates<S>(p, x + 3, u, xd + 3);
+  }
+};
+struct EulerAttitudeModel {
+  static constexpr int ID = CDDP_HIP_MODEL_EULER_ATTITUDE, NX = 6, NU = 3;
+  static constexpr bool kDiscrete = false;
+#ifdef CDDP_HOST_MODELS
+  static constexpr bool kHasHess = true;
+  static constexpr bool kHessBlocked = false;
+  static void hess(const double *p, const double *x, const double *u, double *Fxx, double *Fuu, double *Fux) { ad_hessian<EulerAttitudeDyn, NX, NU>(p, x, u, 1.0, Fxx, Fuu, Fux); }
+#else
+  static constexpr bool kHasHess = false;   // device: the blocked contraction (Dual2N<9> per lane would be a 700-double frame)
+  static constexpr bool kHessBlocked = true;
+  typedef EulerAttitudeDyn HessDyn;
+  static constexpr double kHessDiv = 1.0;
+#endif
+  DEV static void f(const double *p, const double *x, const double *u, double *xd) { EulerAttitudeDyn::eval<double>(p, x, u, xd); }
+  DEV static void jac(const double *p, const double *x, const double *u, double *Fx, double *Fu) {
+    ad_jacobian_blocked<EulerAttitudeDyn, NX, NU, 3>(p, x, u, Fx, Fu);
+  }
+};
+
+// ---------------------------------------------------------------------------- QuaternionAttitude (quaternion_attitude.cpp:33-62, 159-183)
+// State [qw, qx, qy, qz, wx, wy, wz], control [tau_x, tau_y, tau_z].  The VALUE normalises q (|q| > 1e-9, else the identity); the
+// autodiff expression behind the Jacobians and Hessians does NOT -- so f_x is the derivative of the un-normalised kinematics.
+struct QuaternionAttitudeDyn {
+  template <class S>
+  DEV static void kin(const S *q, const S *w, S *qd) {   // (0.5 * Omega(omega)) q, zero entries left out
+    const S a0 = S(0.5) * w[0], a1 = S(0.5) * w[1], a2 = S(0.5) * w[2];
+    qd[0] = ((-a0) * q[1] + (-a1) * q[2]) + (-a2) * q[3];
+    qd[1] = (a0 * q[0] + a2 * q[2]) + (-a1) * q[3];
+    qd[2] = (a1 * q[0] + (-a2) * q[1]) + a0 * q[3];
+    qd[3] = (a2 * q[0] + a1 * q[1]) + (-a0) * q[2];
+  }
+  template <class S>
+  DEV static void eval(const double *p, const S *x, const S *u, S *xd) {   // the autodiff expression (:159-183)
+    kin<S>(x, x + 4, xd);
+    rigid_body_rates<S>(p, x + 4, u, xd + 4);
+  }
+};
+struct QuaternionAttitudeModel {
+  static constexpr int ID = CDDP_HIP_MODEL_QUATERNION_ATTITUDE, NX = 7, NU = 3;
+  static constexpr bool kDiscrete = false;
+#ifdef CDDP_HOST_MODELS
+  static constexpr bool kHasHess = true;
+  static constexpr bool kHessBlocked = false;
+  static void hess(const double *p, const double *x, const double *u, double *Fxx, double *Fuu, double *Fux) { ad_hessian<QuaternionAttitudeDyn, NX, NU>(p, x, u, 1.0, Fxx, Fuu, Fux); }
+#else
+  static constexpr bool kHasHess = false;
+  static constexpr bool kHessBlocked = true;
+  typedef QuaternionAttitudeDyn HessDyn;
+  static constexpr double kHessDiv = 1.0;
+#endif
+  DEV static void f(const double *p, const double *x, const double *u, double *xd) {   // :33-62
+    double q[4] = {x[0], x[1], x[2], x[3]};
+    const double nrm = sqrt(((q[0] * q[0] + q[1] * q[1]) + q[2] * q[2]) + q[3] * q[3]);
+    if (nrm > 1e-9) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) q[i] = q[i] / nrm;
+    } else {
+      q[0] = 1.0; q[1] = 0.0; q[2] = 0.0; q[3] = 0.0;
+    }
+    QuaternionAttitudeDyn::kin<double>(q, x + 4, xd);
+    rigid_body_rates<double>(p, x + 4, u, xd + 4);
+  }
+  DEV static void jac(const double *p, const double *x, const double *u, double *Fx, double *Fu) {
+    ad_jacobian_blocked<QuaternionAttitudeDyn, NX, NU, 4>(p, x, u, Fx, Fu);
+  }
+};
+
+// ---------------------------------------------------------------------------- MrpAttitude (mrp_attitude.cpp:31-98, .hpp:154+)
+// State [s1, s2, s3, wx, wy, wz] (modified Rodrigues parameters), control [tau_x, tau_y, tau_z];
+// d(sigma)/dt = (0.25 B(sigma)) omega, B = (1 - |sigma|^2) I + 2 skew(sigma) + 2 sigma sigma^T.  Every derivative is the base class's
+// autodiff of the autodiff expression (dynamical_system.cpp:100-217).
+struct MrpAttitudeDyn {
+  template <class S>
+  DEV static void eval(const double *p, const S *x, const S *u, S *xd) {
+    const S *s = x;
+    const S a = S(1.0) - ((s[0] * s[0] + s[1] * s[1]) + s[2] * s[2]);
+    S B[9];
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+      for (int j = 0; j < 3; ++j) B[3 * i + j] = (S(2.0) * s[i]) * s[j];
+    B[0] = a + B[0]; B[4] = a + B[4]; B[8] = a + B[8];
+    B[1] = S(2.0) * (-s[2]) + B[1]; B[2] = S(2.0) * s[1] + B[2];
+    B[3] = S(2.0) * s[2] + B[3];    B[5] = S(2.0) * (-s[0]) + B[5];
+    B[6] = S(2.0) * (-s[1]) + B[6]; B[7] = S(2.0) * s[0] + B[7];
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+      xd[i] = ((S(0.25) * B[3 * i]) * x[3] + (S(0.25) * B[3 * i + 1]) * x[4]) + (S(0.25) * B[3 * i + 2]) * x[5];
+    rigid_body_rates<S>(p, x + 3, u, xd + 3);
+  }
+};
+struct MrpAttitudeModel {
+  static constexpr int ID = CDDP_HIP_MODEL_MRP_ATTITUDE, NX = 6, NU = 3;
+  static constexpr bool kDiscrete = false;
+#ifdef CDDP_HOST_MODELS
+  static constexpr bool kHasHess = true;
+  static constexpr bool kHessBlocked = false;
+  static void hess(const double *p, const double *x, const double *u, double *Fxx, double *Fuu, double *Fux) { ad_hessian<MrpAttitudeDyn, NX, NU>(p, x, u, 1.0, Fxx, Fuu, Fux); }
+#else
+  static constexpr bool kHasHess = false;
+  static constexpr bool kHessBlocked = true;
+  typedef MrpAttitudeDyn HessDyn;
+  static constexpr double kHessDiv = 1.0;
+#endif
+  DEV static void f(const double *p, const double *x, const double *u, double *xd) { MrpAttitudeDyn::eval<double>(p, x, u, xd); }
+  DEV static void jac(const double *p, const double *x, const double *u, double *Fx, double *Fu) {
+    ad_jacobian_blocked<MrpAttitudeDyn, NX, NU, 3>(p, x, u, Fx, Fu);
+  }
+};
+
+// central finite differences of the continuous dynamics, h = 2e-5 (helper.hpp:95-119, as the manipulator's Jacobians)
+template <class Model>
+DEV void fd_jacobian(const double *p, const double *x, const double *u, double *Fx, double *Fu) {
+  constexpr int NX = Model::NX, NU = Model::NU;
+  const double h = 2e-5;
+  double xp[NX], up[NU], fp[NX], fm[NX];
+#pragma unroll
+  for (int i = 0; i < NX; ++i) xp[i] = x[i];
+#pragma unroll
+  for (int i = 0; i < NU; ++i) up[i] = u[i];
+  for (int i = 0; i < NX; ++i) {
+    xp[i] = x[i] + h; Model::f(p, xp, u, fp);
+    xp[i] = x[i] - h; Model::f(p, xp, u, fm);
+    for (int r = 0; r < NX; ++r) Fx[r * NX + i] = (fp[r] - fm[r]) / (2.0 * h);
+    xp[i] = x[i];
+  }
+  for (int i = 0; i < NU; ++i) {
+    up[i] = u[i] + h; Model::f(p, x, up, fp);
+    up[i] = u[i] - h; Model::f(p, x, up, fm);
+    for (int r = 0; r < NX; ++r) Fu[r * NU + i] = (fp[r] - fm[r]) / (2.0 * h);
+    up[i] = u[i];
+  }
+}
+
+// ---------------------------------------------------------------------------- SpacecraftTwobody (spacecraft_twobody.cpp:15-74)
+// State [x, y, z, vx, vy, vz], control [ux, uy, uz]; params: mu, mass.  Jacobians: central FD.  State / control Hessians are zero
+// overrides, but the plant has no autodiff expression, so the base class's cross Hessian throws: full DDP is refused for it.
+struct SpacecraftTwobodyModel {
+  static constexpr int ID = CDDP_HIP_MODEL_SPACECRAFT_TWOBODY, NX = 6, NU = 3;
+  static constexpr bool kDiscrete = false;
+  static constexpr bool kHasHess = false;
+  static constexpr bool kHessBlocked = false;
+  // what the reference raises on use_ilqr = false (dynamical_system.hpp:54-60, reached through getCrossHessian)
+  static constexpr const char *kNoHessMsg = "getContinuousDynamicsAutodiff must be overridden in the derived class to use Autodiff-based derivatives.";
+  DEV static void f(const double *p, const double *x, const double *u, double *xd) {
+    const double mu = p[0], mass = p[1];
+    const double r = sqrt((x[0] * x[0] + x[1] * x[1]) + x[2] * x[2]);
+    const double r3 = (r * r) * r;
+    xd[0] = x[3]; xd[1] = x[4]; xd[2] = x[5];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) xd[3 + i] = ((-mu) * x[i]) / r3 + u[i] / mass;
+  }
+  DEV static void jac(const double *p, const double *x, const double *u, double *Fx, double *Fu) { fd_jacobian<SpacecraftTwobodyModel>(p, x, u, Fx, Fu); }
+};
+
+// ---------------------------------------------------------------------------- SpacecraftLanding2D (spacecraft_landing2d.cpp:20-112)
+// State in the header's order (spacecraft_landing2d.hpp:159-165): [x, x_dot, y, y_dot, theta, theta_dot]; control [thrust fraction,
+// gimbal angle]; params: mass, length, width, min_thrust, max_thrust, max_gimble; gravity 9.81, inertia (1/12) m L^2.  Jacobians:
+// central FD (:81-98).  State / control Hessians: zero overrides (:100-110).  Cross Hessian: the base-class autodiff default on the
+// autodiff expression (:112+), which differs from the value -- thrust = u0 (no max_thrust factor) -- in closed form:
+//   d2(u0 sin(u1 + th) / m) / du0 dth = cos(u1 + th) / m,   / du1 dth = -u0 sin(u1 + th) / m
+//   d2(u0 cos(u1 + th) / m) / du0 dth = -sin(u1 + th) / m,  / du1 dth = -u0 cos(u1 + th) / m     (theta_dot row: no theta)
+struct SpacecraftLanding2DModel {
+  static constexpr int ID = CDDP_HIP_MODEL_SPACECRAFT_LANDING2D, NX = 6, NU = 2;
+  static constexpr bool kDiscrete = false;
+  static constexpr bool kHasHess = true;
+  static constexpr bool kHessBlocked = false;
+  DEV static void f(const double *p, const double *x, const double *u, double *xd) {
+    const double mass = p[0], length = p[1], max_thrust = p[4];
+    const double inertia = (1.0 / 12.0) * mass * length * length;
+    const double total_angle = u[1] + x[4];
+    const double thrust = max_thrust * u[0];
+    double s, c; plant_sincos(total_angle, &s, &c);
+    const double T = -length / 2.0 * thrust * plant_sin(u[1]);
+    xd[0] = x[1]; xd[2] = x[3]; xd[4] = x[5];
+    xd[1] = (thrust * s) / mass;
+    xd[3] = (thrust * c) / mass - 9.81;
+    xd[5] = T / inertia;
+  }
+  DEV static void jac(const double *p, const double *x, const double *u, double *Fx, double *Fu) { fd_jacobian<SpacecraftLanding2DModel>(p, x, u, Fx, Fu); }
+  DEV static void hess(const double *p, const double *x, const double *u, double *Fxx, double *Fuu, double *Fux) {
+    for (int i = 0; i < NX * NX * NX; ++i) Fxx[i] = 0.0;
+    for (int i = 0; i < NX * NU * NU; ++i) Fuu[i] = 0.0;
+    for (int i = 0; i < NX * NU * NX; ++i) Fux[i] = 0.0;
+    const double mass = p[0];
+    double s, c; plant_sincos(u[1] + x[4], &s, &c);
+    Fux[(1 * NU + 0) * NX + 4] = c / mass;
+    Fux[(1 * NU + 1) * NX + 4] = -(u[0] * s) / mass;
+    Fux[(3 * NU + 0) * NX + 4] = -s / mass;
+    Fux[(3 * NU + 1) * NX + 4] = -(u[0] * c) / mass;
+  }
+};
+
 // ---- explicit integrators (dynamical_system.cpp:28-83) --------------------------------------
 // Loop-invariant integrator constants held in registers (SGPRs) by the serial kernels: the step size products
 // and the plant parameters would otherwise be re-fetched through dependent scalar loads -- and dt/6 re-divided --

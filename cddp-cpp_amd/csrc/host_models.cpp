@@ -13,6 +13,7 @@
 #define DEV inline
 #include "dev_models.hpp"
 
+#include <cmath>
 #include <string>
 
 namespace {
@@ -46,6 +47,40 @@ int eval(int integrator, double dt, const double *params, int nx, int nu, const 
 }
 }  // namespace
 
+// C++ linkage, called by capi.hip from both flatten() (device descriptor) and cddp_hip_model_eval: the parameter block the plants read.
+// Checks the dimensions of the spacecraft plants and, for the attitude plants, appends I^-1 to the inertia matrix (p[9..17]) as Eigen's
+// fixed-size 3 x 3 inverse() computes it in their constructors: cofactors times 1 / det.
+int cddp_host_model_params(int model, int nx, int nu, const double *in, double *out, std::string &err) {
+  for (int i = 0; i < CDDP_HIP_MAX_MODEL_PARAMS; ++i) out[i] = in[i];
+  static const struct { int model, nx, nu; const char *name; } dims[] = {
+      {CDDP_HIP_MODEL_EULER_ATTITUDE, 6, 3, "EulerAttitude"}, {CDDP_HIP_MODEL_QUATERNION_ATTITUDE, 7, 3, "QuaternionAttitude"},
+      {CDDP_HIP_MODEL_MRP_ATTITUDE, 6, 3, "MrpAttitude"}, {CDDP_HIP_MODEL_SPACECRAFT_TWOBODY, 6, 3, "SpacecraftTwobody"},
+      {CDDP_HIP_MODEL_SPACECRAFT_LANDING2D, 6, 2, "SpacecraftLanding2D"}};
+  for (const auto &d : dims) {
+    if (d.model != model) continue;
+    if (nx != d.nx || nu != d.nu) {
+      err = std::string(d.name) + " has nx = " + std::to_string(d.nx) + ", nu = " + std::to_string(d.nu) + " (got nx = " + std::to_string(nx) +
+            ", nu = " + std::to_string(nu) + ")";
+      return -2;
+    }
+  }
+  if (model == CDDP_HIP_MODEL_EULER_ATTITUDE || model == CDDP_HIP_MODEL_QUATERNION_ATTITUDE || model == CDDP_HIP_MODEL_MRP_ATTITUDE) {
+    const double *M = in;
+    double C[9];
+    for (int i = 0; i < 3; ++i)
+      for (int j = 0; j < 3; ++j) {
+        const int i1 = (i + 1) % 3, i2 = (i + 2) % 3, j1 = (j + 1) % 3, j2 = (j + 2) % 3;
+        C[3 * i + j] = M[3 * i1 + j1] * M[3 * i2 + j2] - M[3 * i1 + j2] * M[3 * i2 + j1];
+      }
+    const double det = (M[0] * C[0] + M[1] * C[1]) + M[2] * C[2];
+    const double invdet = 1.0 / det;
+    if (det == 0.0 || !std::isfinite(invdet)) { err = "the inertia matrix is singular (det = " + std::to_string(det) + "): it has no inverse"; return -2; }
+    for (int i = 0; i < 3; ++i)
+      for (int j = 0; j < 3; ++j) out[9 + 3 * i + j] = C[3 * j + i] * invdet;
+  }
+  return 0;
+}
+
 // C++ linkage: called from capi.hip (cddp_hip_model_eval), which owns the error string
 int cddp_host_model_eval(int model, int integrator, double dt, const double *params, int nx, int nu, const double *x, const double *u, double *x_next,
                          double *fx, double *fu, double *fxx, double *fuu, double *fux, std::string &err) {
@@ -60,6 +95,13 @@ int cddp_host_model_eval(int model, int integrator, double dt, const double *par
     case CDDP_HIP_MODEL_MANIPULATOR7: return eval<Manip7Model>(integrator, dt, params, nx, nu, x, u, x_next, fx, fu, fxx, fuu, fux, err);
     case CDDP_HIP_MODEL_BICYCLE: return eval<BicycleModel>(integrator, dt, params, nx, nu, x, u, x_next, fx, fu, fxx, fuu, fux, err);
     case CDDP_HIP_MODEL_HCW: return eval<HCWModel>(integrator, dt, params, nx, nu, x, u, x_next, fx, fu, fxx, fuu, fux, err);
+    case CDDP_HIP_MODEL_EULER_ATTITUDE: return eval<EulerAttitudeModel>(integrator, dt, params, nx, nu, x, u, x_next, fx, fu, fxx, fuu, fux, err);
+    case CDDP_HIP_MODEL_QUATERNION_ATTITUDE: return eval<QuaternionAttitudeModel>(integrator, dt, params, nx, nu, x, u, x_next, fx, fu, fxx, fuu, fux, err);
+    case CDDP_HIP_MODEL_MRP_ATTITUDE: return eval<MrpAttitudeModel>(integrator, dt, params, nx, nu, x, u, x_next, fx, fu, fxx, fuu, fux, err);
+    case CDDP_HIP_MODEL_SPACECRAFT_TWOBODY:
+      if (fxx || fuu || fux) { err = SpacecraftTwobodyModel::kNoHessMsg; return -3; }
+      return eval<SpacecraftTwobodyModel>(integrator, dt, params, nx, nu, x, u, x_next, fx, fu, fxx, fuu, fux, err);
+    case CDDP_HIP_MODEL_SPACECRAFT_LANDING2D: return eval<SpacecraftLanding2DModel>(integrator, dt, params, nx, nu, x, u, x_next, fx, fu, fxx, fuu, fux, err);
     case CDDP_HIP_MODEL_CAR: {   // a discrete plant: its step needs the timestep, which travels as params[1] (as in the device descriptor)
       double pc[CDDP_HIP_MAX_MODEL_PARAMS];
       for (int i = 0; i < CDDP_HIP_MAX_MODEL_PARAMS; ++i) pc[i] = params[i];

@@ -449,5 +449,6 @@ void register_manipulator(std::vector<KernelSet> &);
 void register_manip7(std::vector<KernelSet> &);
 void register_terminal(std::vector<KernelSet> &);
 void register_statebox(std::vector<KernelSet> &);
+void register_spacecraft(std::vector<KernelSet> &);
 
 }  // namespace cddp_dev

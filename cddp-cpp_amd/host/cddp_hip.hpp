@@ -265,6 +265,24 @@ struct Bicycle : DynamicalSystem {    // bicycle.hpp: (timestep, wheelbase, inte
 struct Car : DynamicalSystem {        // car.hpp: (timestep, wheelbase, integration_type); a DISCRETE plant (car.cpp:24-60); control [delta, a]
   Car(double dt = 0.03, double wheelbase = 2.0, std::string integ = "euler") : DynamicalSystem(CDDP_HIP_MODEL_CAR, 4, 2, dt, integ) { params = {wheelbase}; }
 };
+// rigid-body attitude plants: (timestep, inertia_matrix, integration_type = "euler"); control [tau_x, tau_y, tau_z]; the library appends I^-1
+struct EulerAttitude : DynamicalSystem {       // euler_attitude.hpp: state [psi, theta, phi, wx, wy, wz]
+  EulerAttitude(double dt, const Matrix &inertia, std::string integ = "euler") : DynamicalSystem(CDDP_HIP_MODEL_EULER_ATTITUDE, 6, 3, dt, integ) { params = inertia.a; }
+};
+struct QuaternionAttitude : DynamicalSystem {  // quaternion_attitude.hpp: state [qw, qx, qy, qz, wx, wy, wz]
+  QuaternionAttitude(double dt, const Matrix &inertia, std::string integ = "euler") : DynamicalSystem(CDDP_HIP_MODEL_QUATERNION_ATTITUDE, 7, 3, dt, integ) { params = inertia.a; }
+};
+struct MrpAttitude : DynamicalSystem {         // mrp_attitude.hpp: state [s1, s2, s3, wx, wy, wz]
+  MrpAttitude(double dt, const Matrix &inertia, std::string integ = "euler") : DynamicalSystem(CDDP_HIP_MODEL_MRP_ATTITUDE, 6, 3, dt, integ) { params = inertia.a; }
+};
+struct SpacecraftTwobody : DynamicalSystem {   // spacecraft_twobody.hpp:28: (timestep, mu, mass); always Euler
+  SpacecraftTwobody(double dt, double mu, double mass) : DynamicalSystem(CDDP_HIP_MODEL_SPACECRAFT_TWOBODY, 6, 3, dt, "euler") { params = {mu, mass}; }
+};
+struct SpacecraftLanding2D : DynamicalSystem { // spacecraft_landing2d.hpp:38-45; state [x, x_dot, y, y_dot, theta, theta_dot], control [thrust, gimbal]
+  SpacecraftLanding2D(double dt = 0.1, std::string integ = "rk4", double mass = 100000.0, double length = 50.0, double width = 10.0,
+                      double min_thrust = 880000.0, double max_thrust = 2210000.0, double max_gimble = 0.349066)
+      : DynamicalSystem(CDDP_HIP_MODEL_SPACECRAFT_LANDING2D, 6, 2, dt, integ) { params = {mass, length, width, min_thrust, max_thrust, max_gimble}; }
+};
 struct Manipulator : DynamicalSystem {
   Manipulator(double dt, std::string integ = "rk4") : DynamicalSystem(CDDP_HIP_MODEL_MANIPULATOR, 6, 3, dt, integ) {}
 };

@@ -21,6 +21,8 @@ NAME_LEN = 48
 MODEL_PENDULUM, MODEL_CARTPOLE, MODEL_UNICYCLE, MODEL_LTI = 0, 1, 2, 3
 MODEL_QUADROTOR, MODEL_MANIPULATOR, MODEL_QUADROTOR_EULER12, MODEL_MANIPULATOR7 = 4, 5, 6, 7
 MODEL_BICYCLE, MODEL_CAR, MODEL_HCW = 8, 9, 10
+MODEL_EULER_ATTITUDE, MODEL_QUATERNION_ATTITUDE, MODEL_MRP_ATTITUDE = 11, 12, 13
+MODEL_SPACECRAFT_TWOBODY, MODEL_SPACECRAFT_LANDING2D = 14, 15
 EULER, HEUN, RK3, RK4 = 0, 1, 2, 3
 SOLVER_CLDDP, SOLVER_IPDDP, SOLVER_LOGDDP, SOLVER_MSIPDDP = 0, 1, 2, 3
 CON_CONTROL_BOX, CON_STATE_BOX, CON_BALL, CON_LINEAR = 0, 1, 2, 3
@@ -527,6 +529,67 @@ def manipulator7_problem(solver=SOLVER_IPDDP, horizon=150, terminal_equality=Tru
     if terminal_equality:
         p.add_terminal_equality("TerminalEquality", goal)
     p.x0 = np.zeros(14)
+    return p
+
+
+# ---- spacecraft plants (src/dynamics_model/{euler,quaternion,mrp}_attitude.cpp, spacecraft_twobody.cpp, spacecraft_landing2d.cpp)
+ATTITUDE_INERTIA = ((1.0, 0.1, 0.0), (0.1, 1.5, 0.05), (0.0, 0.05, 2.0))   # a full (non-diagonal) inertia: every entry of I^-1 matters
+_ATTITUDE = {"euler": (MODEL_EULER_ATTITUDE, 6), "quaternion": (MODEL_QUATERNION_ATTITUDE, 7), "mrp": (MODEL_MRP_ATTITUDE, 6)}
+
+
+def attitude_problem(kind="euler", solver=SOLVER_IPDDP, horizon=60, constrained=True, integrator=None, inertia=ATTITUDE_INERTIA):
+    """Rest-to-rest slew of a rigid body to the identity attitude, torque box +-1.  kind: "euler" (ZYX angles), "quaternion"
+    ([qw, qx, qy, qz]) or "mrp"; the three start from the same rotation (yaw 0.3, pitch -0.2, roll 0.4).  model_params: the inertia
+    matrix, row-major (the library appends its inverse)."""
+    model, nx = _ATTITUDE[kind]
+    o = default_options(); o.max_iterations = 60; o.tolerance = 1e-5; o.acceptable_tolerance = 1e-6
+    dt = 0.1
+    ypr = (0.3, -0.2, 0.4)
+    cy, sy, cp, sp, cr, sr = (f(0.5 * a) for a in ypr for f in (np.cos, np.sin))
+    q = np.array([cr * cp * cy + sr * sp * sy, sr * cp * cy - cr * sp * sy, cr * sp * cy + sr * cp * sy, cr * cp * sy - sr * sp * cy])
+    att = {"euler": np.array(ypr), "quaternion": q, "mrp": q[1:] / (1.0 + q[0])}[kind]
+    goal = np.zeros(nx)
+    if kind == "quaternion":
+        goal[0] = 1.0
+    Qf = np.diag([100.0] * (nx - 3) + [10.0] * 3)
+    p = Problem(solver, model, RK4 if integrator is None else integrator, nx, 3, horizon, dt, np.zeros((nx, nx)), 0.1 * np.eye(3), Qf, goal,
+                model_params=np.asarray(inertia, dtype=np.float64).reshape(9), options=o)
+    if constrained:
+        p.add_control_box("ControlConstraint", -np.ones(3), np.ones(3))
+    p.x0 = np.concatenate([att, [0.0, 0.0, 0.0]])
+    return p
+
+
+def twobody_problem(solver=SOLVER_IPDDP, horizon=60, constrained=True, integrator=None):
+    """Orbit correction about a central body in canonical units (mu = 1, mass 1, circular orbit of radius 1): from a perturbed state to
+    the circular orbit's state at t = N dt, thrust box +-0.2."""
+    o = default_options(); o.max_iterations = 40; o.tolerance = 1e-5; o.acceptable_tolerance = 1e-6
+    dt = 0.05
+    T = horizon * dt
+    goal = np.array([np.cos(T), np.sin(T), 0.0, -np.sin(T), np.cos(T), 0.0])
+    p = Problem(solver, MODEL_SPACECRAFT_TWOBODY, EULER if integrator is None else integrator, 6, 3, horizon, dt, np.zeros((6, 6)), np.eye(3),
+                100.0 * np.eye(6), goal, model_params=[1.0, 1.0], options=o)
+    if constrained:
+        p.add_control_box("ControlConstraint", -0.2 * np.ones(3), 0.2 * np.ones(3))
+    p.x0 = np.array([1.02, -0.01, 0.01, 0.0, 0.98, 0.02])
+    return p
+
+
+LANDING2D_PARAMS = (100000.0, 50.0, 10.0, 880000.0, 2210000.0, 0.349066)   # spacecraft_landing2d.hpp:38-45 defaults
+
+
+def landing2d_problem(solver=SOLVER_IPDDP, horizon=80, constrained=True, integrator=None):
+    """Powered descent of the planar lander (state [x, x_dot, y, y_dot, theta, theta_dot], control [thrust fraction, gimbal angle]) to rest
+    at the origin; box: thrust fraction in [min_thrust / max_thrust, 1], gimbal within +-max_gimble; starts from hover thrust."""
+    o = default_options(); o.max_iterations = 60; o.tolerance = 1e-4; o.acceptable_tolerance = 1e-6
+    dt = 0.1
+    mass, _, _, tmin, tmax, gmax = LANDING2D_PARAMS
+    p = Problem(solver, MODEL_SPACECRAFT_LANDING2D, RK4 if integrator is None else integrator, 6, 2, horizon, dt, np.zeros((6, 6)),
+                np.diag([1.0, 1.0]), np.diag([1e-2, 1e-1, 1e-2, 1e-1, 10.0, 10.0]), np.zeros(6), model_params=LANDING2D_PARAMS, options=o)
+    if constrained:
+        p.add_control_box("ControlConstraint", [tmin / tmax, -gmax], [1.0, gmax])
+    p.x0 = np.array([20.0, -2.0, 150.0, -15.0, 0.05, 0.0])
+    p.U0_const = np.array([9.81 * mass / tmax, 0.0])
     return p
 
 

@@ -253,6 +253,44 @@ class Car(_BuiltinPlant):           # bind_dynamics.cpp:148-150: (timestep, whee
         super().__init__(4, 2, timestep, integration_type); self.params = [wheelbase]
 
 
+class _AttitudePlant(_BuiltinPlant):   # bind_dynamics.cpp:243-258: (timestep, inertia_matrix, integration_type = "euler")
+    _id, _nx = None, None
+    def __init__(self, timestep, inertia_matrix, integration_type="euler"):
+        self.model = getattr(_api(), self._id)
+        J = np.asarray(inertia_matrix, dtype=np.float64)
+        if J.shape != (3, 3):
+            raise ValueError("inertia_matrix must be 3 x 3")
+        super().__init__(self._nx, 3, timestep, integration_type)
+        self.inertia_matrix = J
+        self.params = list(J.reshape(9))     # the library appends I^-1 (cofactors / det, Eigen's fixed-size inverse)
+
+
+class EulerAttitude(_AttitudePlant):      # euler_attitude.cpp: state [psi, theta, phi, wx, wy, wz], control [tau_x, tau_y, tau_z]
+    _id, _nx = "MODEL_EULER_ATTITUDE", 6
+
+
+class QuaternionAttitude(_AttitudePlant):   # quaternion_attitude.cpp: state [qw, qx, qy, qz, wx, wy, wz]
+    _id, _nx = "MODEL_QUATERNION_ATTITUDE", 7
+
+
+class MrpAttitude(_AttitudePlant):        # mrp_attitude.cpp: state [s1, s2, s3, wx, wy, wz]
+    _id, _nx = "MODEL_MRP_ATTITUDE", 6
+
+
+class SpacecraftTwobody(_BuiltinPlant):   # bind_dynamics.cpp:227-230: (timestep, mu, mass); always Euler (spacecraft_twobody.cpp:12-13)
+    def __init__(self, timestep, mu, mass):
+        self.model = _api().MODEL_SPACECRAFT_TWOBODY
+        super().__init__(6, 3, timestep, "euler"); self.params = [mu, mass]
+
+
+class SpacecraftLanding2D(_BuiltinPlant):   # bind_dynamics.cpp:218-225; state [x, x_dot, y, y_dot, theta, theta_dot]
+    def __init__(self, timestep=0.1, integration_type="rk4", mass=100000.0, length=50.0, width=10.0, min_thrust=880000.0,
+                 max_thrust=2210000.0, max_gimble=0.349066):
+        self.model = _api().MODEL_SPACECRAFT_LANDING2D
+        super().__init__(6, 2, timestep, integration_type)
+        self.params = [mass, length, width, min_thrust, max_thrust, max_gimble]
+
+
 class Manipulator(_BuiltinPlant):  # :189-191
     def __init__(self, timestep, integration_type="rk4"):
         self.model = _api().MODEL_MANIPULATOR

@@ -42,7 +42,8 @@ extern "C" {
 
 /* Built-in plants with device-side dynamics + derivatives
  * (reference src/dynamics_model/{pendulum,cartpole,unicycle,lti_system,quadrotor,
- *  manipulator}.cpp).  model_params layout is documented per entry. */
+ *  manipulator,bicycle,car,spacecraft_linear,euler_attitude,quaternion_attitude,mrp_attitude,
+ *  spacecraft_twobody,spacecraft_landing2d}.cpp).  model_params layout is documented per entry. */
 enum cddp_hip_model {
   CDDP_HIP_MODEL_PENDULUM = 0,   /* params: length, mass, damping, gravity                     */
   CDDP_HIP_MODEL_CARTPOLE = 1,   /* params: cart_mass, pole_mass, pole_length, gravity, damping */
@@ -54,8 +55,20 @@ enum cddp_hip_model {
   CDDP_HIP_MODEL_MANIPULATOR7 = 7,      /* SYNTHETIC nx=14/nu=7 (BASELINE config 5 shape)       */
   CDDP_HIP_MODEL_BICYCLE = 8,    /* kinematic bicycle [x,y,theta,v] / [a,delta] (bicycle.cpp); params: wheelbase            */
   CDDP_HIP_MODEL_CAR = 9,        /* DISCRETE car [x,y,theta,v] / [delta,a] (car.cpp:24-60, h = dt); params: wheelbase      */
-  CDDP_HIP_MODEL_HCW = 10        /* Hill-Clohessy-Wiltshire relative motion [x,y,z,vx,vy,vz] / [Fx,Fy,Fz] (spacecraft_linear.cpp:24-120);
+  CDDP_HIP_MODEL_HCW = 10,       /* Hill-Clohessy-Wiltshire relative motion [x,y,z,vx,vy,vz] / [Fx,Fy,Fz] (spacecraft_linear.cpp:24-120);
                                     params: mean_motion, mass                                                                  */
+  /* rigid-body attitude plants, control [tau_x, tau_y, tau_z]; params [0..8]: the inertia matrix, row-major.  The library fills
+     [9..17] with its inverse itself (cofactors times 1 / det, as Eigen's fixed-size inverse) and refuses a singular matrix. */
+  CDDP_HIP_MODEL_EULER_ATTITUDE = 11,      /* nx=6 [psi,theta,phi,wx,wy,wz] ZYX angles (euler_attitude.cpp)                  */
+  CDDP_HIP_MODEL_QUATERNION_ATTITUDE = 12, /* nx=7 [qw,qx,qy,qz,wx,wy,wz]; the step normalises q, the Jacobians do not
+                                              (quaternion_attitude.cpp)                                                      */
+  CDDP_HIP_MODEL_MRP_ATTITUDE = 13,        /* nx=6 [s1,s2,s3,wx,wy,wz] modified Rodrigues parameters (mrp_attitude.cpp)       */
+  CDDP_HIP_MODEL_SPACECRAFT_TWOBODY = 14,  /* nx=6 [x,y,z,vx,vy,vz] / [ux,uy,uz] point mass about a central body
+                                              (spacecraft_twobody.cpp); params: mu, mass.  Central-FD Jacobians; no full DDP
+                                              (use_ilqr = 0 is refused: the reference's cross Hessian throws)               */
+  CDDP_HIP_MODEL_SPACECRAFT_LANDING2D = 15 /* nx=6 [x,x_dot,y,y_dot,theta,theta_dot] / [thrust fraction, gimbal angle]
+                                              (spacecraft_landing2d.cpp); params: mass, length, width, min_thrust,
+                                              max_thrust, max_gimble (gravity 9.81, inertia mass * length^2 / 12)          */
 };
 
 /* reference src/cddp_core/dynamical_system.cpp:28-83 */

@@ -33,11 +33,16 @@
 #include "dynamics_model/bicycle.hpp"
 #include "dynamics_model/car.hpp"
 #include "dynamics_model/cartpole.hpp"
+#include "dynamics_model/euler_attitude.hpp"
 #include "dynamics_model/lti_system.hpp"
 #include "dynamics_model/manipulator.hpp"
+#include "dynamics_model/mrp_attitude.hpp"
 #include "dynamics_model/pendulum.hpp"
 #include "dynamics_model/quadrotor.hpp"
+#include "dynamics_model/quaternion_attitude.hpp"
+#include "dynamics_model/spacecraft_landing2d.hpp"
 #include "dynamics_model/spacecraft_linear.hpp"
+#include "dynamics_model/spacecraft_twobody.hpp"
 #include "dynamics_model/unicycle.hpp"
 
 #include "cddp_hip.h"   // this repository: include/cddp_hip.h
@@ -137,6 +142,12 @@ bool describeModel(const DynamicalSystem &s, ModelDesc &m) {
     m.id = CDDP_HIP_MODEL_LTI; m.lti_A = rowMajor(p.getA()); m.lti_B = rowMajor(p.getB());
     return true;
   }
+  if (typeid(s) == typeid(SpacecraftLanding2D)) {   // public getters (spacecraft_landing2d.hpp:138-145)
+    const auto &p = static_cast<const SpacecraftLanding2D &>(s);
+    m.id = CDDP_HIP_MODEL_SPACECRAFT_LANDING2D;
+    m.params = {p.getMass(), p.getLength(), p.getWidth(), p.getMinThrust(), p.getMaxThrust(), p.getMaxGimble()};
+    return true;
+  }
 #ifdef CDDP_HIP_REFERENCE_HAS_GETTERS
   if (typeid(s) == typeid(Quadrotor)) {
     const auto &p = static_cast<const Quadrotor &>(s);
@@ -148,6 +159,22 @@ bool describeModel(const DynamicalSystem &s, ModelDesc &m) {
   if (typeid(s) == typeid(Bicycle)) { m.id = CDDP_HIP_MODEL_BICYCLE; m.params = {static_cast<const Bicycle &>(s).getWheelbase()}; return true; }
   if (typeid(s) == typeid(Car)) { m.id = CDDP_HIP_MODEL_CAR; m.params = {static_cast<const Car &>(s).getWheelbase()}; return true; }
   if (typeid(s) == typeid(HCW)) { const auto &p = static_cast<const HCW &>(s); m.id = CDDP_HIP_MODEL_HCW; m.params = {p.getMeanMotion(), p.getMass()}; return true; }
+  {   // the attitude plants: the inertia matrix, row-major (the library appends its inverse)
+    int id = -1; const Eigen::Matrix3d *I = nullptr;
+    if (typeid(s) == typeid(EulerAttitude)) { id = CDDP_HIP_MODEL_EULER_ATTITUDE; I = &static_cast<const EulerAttitude &>(s).getInertia(); }
+    if (typeid(s) == typeid(QuaternionAttitude)) { id = CDDP_HIP_MODEL_QUATERNION_ATTITUDE; I = &static_cast<const QuaternionAttitude &>(s).getInertia(); }
+    if (typeid(s) == typeid(MrpAttitude)) { id = CDDP_HIP_MODEL_MRP_ATTITUDE; I = &static_cast<const MrpAttitude &>(s).getInertia(); }
+    if (I) {
+      m.id = id; m.params.clear();
+      for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) m.params.push_back((*I)(r, c));
+      return true;
+    }
+  }
+  if (typeid(s) == typeid(SpacecraftTwobody)) {
+    const auto &p = static_cast<const SpacecraftTwobody &>(s);
+    m.id = CDDP_HIP_MODEL_SPACECRAFT_TWOBODY; m.params = {p.getMu(), p.getMass()};
+    return true;
+  }
 #endif
   return false;
 }
