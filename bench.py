@@ -8,7 +8,12 @@ batch 4096 random x0 per GPU, solved with the interior-point core (IPDDP, the no
 region.  One process per GPU; ranks shard independent trajectories (weak scaling) and exchange a
 single RCCL all-gather of the 16-byte {cost, iterations, status} records per step.
 
+A plain run only sets up, warms up, times the steps, writes --dump-outputs and prints the line.  `--full` adds what the
+headline figure does not need: the other workloads and configurations, the stack-fed, plug-in and MPC lines, and the CPU
+baseline (each after and outside the headline's timed region).
+
     python bench.py --gpus 1 --steps 5 --warmup 1
+    python bench.py --gpus 1 --steps 5 --warmup 1 --full
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 """
@@ -350,8 +355,8 @@ def roofline_block(api, p, m, B, workload, solver, st, prof, stats, sweep_domina
     }
 
 
-# The other BASELINE configurations (per-GPU shares) and the BoxQP core, measured AFTER the headline loop and outside its
-# timed region, so that the driver's record carries them too: (workload, solver, label)
+# The other BASELINE configurations (per-GPU shares) and the BoxQP core, measured by `bench.py --full` AFTER the headline loop and
+# outside its timed region: (workload, solver, label)
 OTHER_WORKLOADS = [
     ("cartpole", "clddp", "C2 cart-pole CLDDP (BoxQP core), B=4096"),
     ("cartpole", "logddp", "f4: cart-pole LogDDP resident on the device (relaxed log barrier of the control box), B=4096"),
@@ -441,7 +446,7 @@ def measure_other(api, workload, solver, label, steps=3, warmup=1, device=0, wor
         hs.close()
 
 
-# BASELINE configs [3] and [4] are quoted on 8 GPUs: with more than one rank they are measured too (strong scaling, 2 steps each)
+# BASELINE configs [3] and [4] are quoted on 8 GPUs: under torchrun `--full` measures them too (strong scaling, 2 steps each)
 MULTI_RANK_WORKLOADS = [
     ("quadrotor", "ipddp", "C4: quadrotor nx=12 N=400, global batch 16384 over the ranks (BASELINE config[3])"),
     ("manip7", "ipddp", "C5: 7-joint arm nx=14 nu=7 N=150 terminal equality, 16 alphas, global batch 32768 over the ranks (BASELINE config[4])"),
@@ -468,7 +473,7 @@ STACKFED_SHAPES = [
     (12, 4, 8, 400, "C4-share shape", (2048, 4096)),
     (14, 7, 14, 150, "C5-share shape", (3072, 4096)),
 ]
-# `bench.py --stackfed`: longer curves (tens of GB of stacks for the nx >= 12 shapes: minutes of host-side tiling and upload, not part of the default line)
+# `bench.py --stackfed`: longer curves (tens of GB of stacks for the nx >= 12 shapes: minutes of host-side tiling and upload, not part of the --full line)
 STACKFED_SHAPES_FULL = [
     (4, 1, 2, 100, "C2 shape", (4096, 16384, 65536, 131072, 262144)),
     (3, 2, 5, 200, "C3 shape", (8192, 32768, 65536, 131072)),
@@ -712,9 +717,12 @@ def main():
     ap.add_argument("--batch", type=int, default=0, help="trajectories per GPU (default: the BASELINE config's per-GPU batch of the workload)")
     ap.add_argument("--solver", default="ipddp", choices=["ipddp", "clddp", "logddp", "msipddp"])
     ap.add_argument("--workload", default="cartpole", choices=["cartpole", "cartpole_unc", "unicycle", "pendulum", "quadrotor", "manip7"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline line's timed steps, also measure the other workloads / configurations, the stack-fed, plug-in and MPC "
+                         "lines and the CPU baseline (off: only what the headline figure needs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-other-workloads", action="store_true",
-                    help="skip the short C2-CLDDP / C3 / C4-share / C5-share measurements appended to the default (C2-IPDDP, 1 GPU) line")
+                    help="with --full: skip the short C2-CLDDP / C3 / C4-share / C5-share measurements appended to the default (C2-IPDDP, 1 GPU) line")
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"],
                     help="weak: --batch trajectories per GPU; strong: a fixed global batch (--global-batch or the BASELINE config's) over all GPUs")
     ap.add_argument("--global-batch", type=int, default=0)
@@ -887,7 +895,8 @@ def main():
         out["config"]["rccl_ranks"] = n_rccl
     hs.close()
     headline = args.workload == "cartpole" and args.solver == "ipddp" and args.batch in (0, 4096) and args.scaling == "weak"
-    if world == 1 and dist is None and not args.no_other_workloads and headline:
+    others = args.full and not args.no_other_workloads and headline
+    if world == 1 and dist is None and others:
         # the other BASELINE configurations, 3 steps each, after and outside the headline's timed region
         out["other_workloads"] = []
         for wl, sv, label in OTHER_WORKLOADS:
@@ -910,7 +919,7 @@ def main():
                 out["other_workloads"].append(measure_mpc(api, 8, device=local_rank, workload=wl))
             except Exception as e:
                 out["other_workloads"].append({"workload": "MPC re-solves (%s)" % wl, "error": "%s: %s" % (type(e).__name__, e)})
-    elif dist is not None and not args.no_other_workloads and headline:
+    elif dist is not None and others:
         # under torchrun (any world size, 1 included): configs [3] / [4] with the batch partitioned over the ranks and the same
         # single collective -- every rank takes part, rank 0 keeps the lines
         out["other_workloads"] = []
@@ -928,7 +937,7 @@ def main():
                 out["other_workloads"].append({"workload": label, "error": "%s: %s" % (type(e).__name__, e)})
     if comm is not None:
         api.comm_destroy(comm)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(api, p, x0, U0)
     elif rank == 0:
         out["cpu_baseline"] = None

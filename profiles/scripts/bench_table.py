@@ -1,4 +1,4 @@
-"""The measurement table of DESIGN.md section 4 from one bench line.  usage: python profiles/scripts/bench_table.py profiles/r06_bench_cartpole_ipddp.json"""
+"""The measurement table of DESIGN.md section 4 from one `bench.py --full` line.  usage: python profiles/scripts/bench_table.py profiles/r06_bench_cartpole_ipddp.json"""
 import json, sys
 d = json.load(open(sys.argv[1]))
 

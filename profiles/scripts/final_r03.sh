@@ -4,7 +4,7 @@
 # and the 1-GPU batch curve of the headline workload.
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 O=gpurun_out/final_r03; mkdir -p $O; rm -rf $O/*
-python bench.py --steps 10 --warmup 2 > $O/bench_cartpole_ipddp.json 2> $O/bench.err
+python bench.py --full --steps 10 --warmup 2 > $O/bench_cartpole_ipddp.json 2> $O/bench.err
 rocprofv3 --kernel-trace --stats -d $O/trace -o r -- python bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-other-workloads > $O/trace.log 2>&1
 for set in FETCH_SIZE WRITE_SIZE "SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_INSTS_SALU"; do
   tag=$(echo $set | tr ' ' '_' | cut -c1-30)

@@ -101,10 +101,22 @@ def test_bench_plain_and_torchrun_single_gpu_agree():
     assert a["config"]["collective"].startswith("none") and b["config"]["collective"].startswith("ncclAllGather")
 
 
+def test_bench_plain_line_is_lean():
+    """A plain run measures the headline alone: no other workloads, no CPU baseline; the headline fields are all there."""
+    out = _run_bench(["--gpus", "1", "--steps", "2", "--warmup", "1"])
+    assert out.returncode == 0, out.stderr[-2000:]
+    j = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
+    assert "other_workloads" not in j and j["cpu_baseline"] is None
+    assert j["metric"] == "trajectories_per_sec" and j["unit"] == "trajectories/s" and j["higher_is_better"] is True and j["dtype"] == "f64"
+    assert j["steps"] == 2 and j["warmup"] == 1 and j["ms_per_step"] > 0
+    assert abs(j["value"] - 4096 * 1e3 / j["ms_per_step"]) <= 1e-6 * j["value"]
+    assert j["config"]["batch_per_gpu"] == 4096 and j["solve"]["gathered_records"] == 4096 and j["roofline"]["frac"] > 0
+
+
 def test_bench_default_line_carries_other_workloads():
-    """the default single-GPU line also measures C2-CLDDP, C3 and the C4 / C5 per-GPU shares (3 steps each,
-    outside the headline's timed region) so that the driver's record has them."""
-    out = _run_bench(["--gpus", "1", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"])
+    """the default single-GPU line with --full also measures C2-CLDDP, C3 and the C4 / C5 per-GPU shares (3 steps
+    each, outside the headline's timed region)."""
+    out = _run_bench(["--gpus", "1", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline"])
     assert out.returncode == 0, out.stderr[-2000:]
     j = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
     ow = j["other_workloads"]
@@ -127,10 +139,10 @@ def test_bench_default_line_carries_other_workloads():
 
 
 def test_bench_torchrun_line_carries_c4_c5_and_rccl_rank_count():
-    """under torch.distributed.run the headline line is followed by BASELINE configs [3] / [4] (quadrotor,
-    7-joint arm) measured through the same partition + all-gather path; with one rank it is the 8-GPU share on a size-1
+    """under torch.distributed.run with --full the headline line is followed by BASELINE configs [3] / [4]
+    (quadrotor, 7-joint arm) measured through the same partition + all-gather path; with one rank it is the 8-GPU share on a size-1
     communicator -- the code path a world of 8 takes -- and the line reports the rank count RCCL itself sees."""
-    out = _run_bench(["--gpus", "1", "--steps", "1", "--warmup", "0", "--no-cpu-baseline"], torchrun=True, port="29547")
+    out = _run_bench(["--gpus", "1", "--steps", "1", "--warmup", "0", "--full", "--no-cpu-baseline"], torchrun=True, port="29547")
     assert out.returncode == 0, out.stderr[-2000:]
     j = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
     assert j["config"]["rccl_ranks"] == 1 and j["config"]["collective"].startswith("ncclAllGather")
