@@ -107,6 +107,8 @@ struct Inner {
   ProblemDev P;
   DevBuf d;
   const KernelSet *ks = nullptr;
+  const Knobs *knob = nullptr;   // the handle's switches (cddp_hip_handle::knob)
+  Route route;                   // the kernel route (resolve_route); route.t4 is d.t4
   int device = 0;
   hipStream_t stream = nullptr;
   bool own_stream = false;
@@ -128,9 +130,6 @@ struct Inner {
   double *d_head = nullptr, *h_head = nullptr; size_t head_cap = 0;   // cddp_hip_get_plan_head staging (device, pinned host)
   int *h_poll = nullptr;                         // pinned host words of the solve loop's polls, two slots of kPollWords: [0] running count, [1..] alpha histogram
   std::map<unsigned long long, hipGraphExec_t> graphs;   // CDDP_HIP_GRAPH=1: captured iteration windows by (ladder shape, length, last flag)
-  std::map<unsigned long long, int> graph_launches;
-  int last_t4 = 0;               // layout of the A / B stacks the last derivative fill wrote (launch.hpp::t4_layout at that launch)
-  unsigned env_sig = 0;          // kernel-selection environment the cached graphs were captured under (CDDP_HIP_SWEEP / T4 / K4_NA / COOP_H)
 };
 
 namespace {
@@ -413,11 +412,10 @@ static bool parse_cu_spec(const std::string &t, CuSpec *o) {
   return true;
 }
 // the spec of group `gi` from CDDP_HIP_CUMASK (false: no partition requested / malformed -> plain streams)
-static bool cu_spec_for_group(int gi, CuSpec *o) {
-  const char *e = std::getenv("CDDP_HIP_CUMASK");
-  if (!e || !e[0]) return false;
+static bool cu_spec_for_group(const Knobs &knob, int gi, CuSpec *o) {
+  if (knob.cumask.empty()) return false;
   std::vector<std::string> parts;
-  { std::string t(e); size_t i = 0; for (;;) { size_t j = t.find('|', i); parts.push_back(t.substr(i, j == std::string::npos ? j : j - i)); if (j == std::string::npos) break; i = j + 1; } }
+  { const std::string &t = knob.cumask; size_t i = 0; for (;;) { size_t j = t.find('|', i); parts.push_back(t.substr(i, j == std::string::npos ? j : j - i)); if (j == std::string::npos) break; i = j + 1; } }
   const std::string &t = parts[std::min((size_t)gi, parts.size() - 1)];
   CuSpec sp;
   if (!parse_cu_spec(t, &sp)) { std::fprintf(stderr, "[cddp_hip] CDDP_HIP_CUMASK: cannot parse '%s' -- ignored\n", t.c_str()); return false; }
@@ -450,13 +448,17 @@ static hipError_t make_stream(hipStream_t *s, int device, int lo, int hi, unsign
 }
 static int in_destroy(Inner *h);
 
-static int in_create(const cddp_hip_problem *problem, int batch, int device, Inner **out, const CuSpec *cu = nullptr) {
+// the kernel route of a group (launch.hpp::Route): fixed by the switches read at create, the solver, the buffers and use_ilqr
+static void resolve_route(Inner *h) { h->route = h->ks->route(h->d, h->P.solver, *h->knob); h->d.t4 = h->route.t4; }
+
+static int in_create(const cddp_hip_problem *problem, int batch, int device, const Knobs &knob, const CuSpec *cu, Inner **out) {
   if (!problem || !out) return fail(-1, "null argument");
   if (batch <= 0) return fail(-1, "batch must be positive");
   int ndev = cddp_hip_device_count();
   if (ndev <= 0) return fail(-20, "no HIP device available: the cddp_hip solver core has no CPU fallback");
   if (device < 0 || device >= ndev) return fail(-1, "device %d out of range (%d devices)", device, ndev);
   Inner *h = new Inner();
+  h->knob = &knob;
   int rc = flatten(problem, h->P);
   if (rc) { delete h; return rc; }
   for (const KernelSet &k : registry()) if (k.matches(h->P)) { h->ks = &k; break; }
@@ -507,10 +509,8 @@ static int in_create(const cddp_hip_problem *problem, int batch, int device, Inn
   d.B = B; d.Bp = Bp; d.NB = Bp / 64; d.N = N; d.n_alphas = P.n_alphas; d.n_slots = P.n_alphas + 1;
   d.ladder_sorted = ladder_strictly_decreasing(P.alphas, P.n_alphas);
   d.ddp = P.opt.use_ilqr ? 0 : 1;
-  { const char *e = std::getenv("CDDP_HIP_TEST_FAIL_COSTATE"); d.fail_costate_mask = e ? std::atoi(e) : 0;   // test hook, DevBuf::fail_costate_mask
-    if (d.fail_costate_mask) std::fprintf(stderr, "[cddp_hip] TEST HOOK active: CDDP_HIP_TEST_FAIL_COSTATE=%d discards line-search trials -- results are not the solver's\n", d.fail_costate_mask); }
-  { const char *e = std::getenv("CDDP_HIP_XCD_MAP"); d.xcd_map = (e && e[0] == '0') ? 0 : 1; }
-  d.t4 = 0;   // set per launch by launch.hpp::derivs / backward (kernels.hpp::GT)
+  d.fail_costate_mask = knob.fail_costate;   // test hook
+  d.xcd_map = knob.xcd_map ? 1 : 0;
   d.hist_batch = P.opt.return_iteration_info ? std::min(B, 64) : 0;
   d.hist_cap = std::max(P.opt.max_iterations, 0) + 1;
   d.planeX = (size_t)(N + 1) * nx * Bp; d.planeU = (size_t)N * nu * Bp; d.planeM = (size_t)N * (m > 0 ? m : 0) * Bp;
@@ -533,7 +533,7 @@ static int in_create(const cddp_hip_problem *problem, int batch, int device, Inn
   }
   DA(d.A, (size_t)N * nx * nx * Bp); DA(d.Bm, (size_t)N * nx * nu * Bp);
   DA(d.K, (size_t)N * nu * nx * Bp); DA(d.k, (size_t)N * nu * Bp);
-  if (ip && nx > 8) DA(d.Kt, (size_t)N * (nu * nx + nu) * Bp);   // G = 16 sweeps (launch.hpp::t4_layout)
+  if (ip && nx > 8) DA(d.Kt, (size_t)N * (nu * nx + nu) * Bp);   // G = 16 sweeps (launch.hpp::Launcher::route, Route::t4)
   DA(d.Vx, (size_t)(N + 1) * nx * Bp); DA(d.Vxx, (size_t)(N + 1) * nx * nx * Bp);
   if (ip && h->ks->cst_size > 0) { DA(d.cst, (size_t)N * h->ks->cst_size * Bp); DA(d.dX, (size_t)N * nx * Bp); DA(d.ys, (size_t)N * (m > 0 ? m : 1) * Bp); }
   if (ip && m > 0) { DA(d.ks, (size_t)N * m * Bp); DA(d.ky, (size_t)N * m * Bp); DA(d.Ks, (size_t)N * m * nx * Bp); DA(d.Ky, (size_t)N * m * nx * Bp); }
@@ -583,6 +583,7 @@ static int in_create(const cddp_hip_problem *problem, int batch, int device, Inn
   hipMemcpyAsync(h->dP, &h->P, sizeof(ProblemDev), hipMemcpyHostToDevice, h->stream);
   d.P = h->dP;
   d.launched = h->d_launched;
+  resolve_route(h);
   e = hipStreamSynchronize(h->stream);
   if (e != hipSuccess) { const int rc_ = fail(-10, "device initialisation failed: %s", hipGetErrorString(e)); in_destroy(h); return rc_; }
   *out = h;
@@ -730,6 +731,8 @@ static int in_set_options(Inner *h, const cddp_hip_options *opt) {
     return fail(-3, "return_iteration_info is fixed at create time (the history buffers are sized by cddp_hip_create)");
   h->P.opt = *opt;
   h->d.ddp = opt->use_ilqr ? 0 : 1;
+  resolve_route(h);   // (full DDP takes other sweeps) -- and captured windows, which bake in the route and the DevBuf, are dropped
+  for (auto &kv : h->graphs) hipGraphExecDestroy(kv.second); h->graphs.clear();
   for (int i = 0; i < na; ++i) h->P.alphas[i] = al[i];
   h->d.ladder_sorted = ladder_strictly_decreasing(al, na);
   h->P.ls_rule = opt->enable_parallel ? CDDP_HIP_LS_BEST_MERIT : CDDP_HIP_LS_FIRST_SUCCESS;
@@ -815,9 +818,8 @@ static int in_backward(Inner *h, int32_t *ok) {
   if (!h) return fail(-1, "null handle");
   HIPCHK(hipSetDevice(h->device));
   if (!h->initialized) { int rc = in_initialize(h); if (rc) return rc; }
-  h->last_t4 = h->ks->t4_layout(h->d);
-  h->ks->derivs(h->d, 1, h->stream);
-  h->ks->backward(h->d, h->P.solver, 1, 0, h->stream);
+  h->ks->derivs(h->d, h->route, 1, h->stream);
+  h->ks->backward(h->d, h->route, h->P.solver, 1, 0, h->stream);
   HIPCHK(hipGetLastError());
   if (ok) HIPCHK(hipMemcpyAsync(ok, h->d.bwd_ok, sizeof(int) * h->d.B, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
@@ -834,8 +836,8 @@ static int in_forward(Inner *h, const double *alphas, int n_alphas, cddp_hip_tri
   HIPCHK(hipMemcpyAsync(h->dP, &tmp, sizeof(ProblemDev), hipMemcpyHostToDevice, h->stream));
   DevBuf dcall = h->d;   // (the caller's ladder may be any set of step sizes)
   dcall.ladder_sorted = ladder_strictly_decreasing(tmp.alphas, h->d.n_alphas);
-  h->ks->forward(dcall, h->P.solver, 0, n_alphas, PH_FWD1, 1, 0, h->stream);
-  h->ks->costate(dcall, h->P.solver, 0, n_alphas, PH_FWD1, 1, 0, h->stream);
+  h->ks->forward(dcall, h->route, h->P.solver, 0, n_alphas, PH_FWD1, 1, 0, h->stream);
+  h->ks->costate(dcall, h->route, h->P.solver, 0, n_alphas, PH_FWD1, 1, 0, h->stream);
   HIPCHK(hipGetLastError());
   const DevBuf &d = h->d;
   const size_t n = (size_t)n_alphas * d.Bp;
@@ -878,7 +880,7 @@ struct SolveRun {
   int k1 = 1, k_cap = 1, k_cap2 = 1;
   long waves_all = 0, per_alpha_waves = 1, two_stage_max_waves = 768;
   std::vector<int> hist_now, hist_prev;
-  // Polls are double-buffered (round 5): behind a poll the host enqueues run_ahead() more iterations (default 1; none behind the two early polls that settle the ladder shape) BEFORE it waits for
+  // Polls are double-buffered (round 5): behind a poll the host enqueues Knobs::run_ahead more iterations (default 1; none behind the two early polls that settle the ladder shape) BEFORE it waits for
   // the poll's words, so the group's queue does not drain while the host wakes up and enqueues (the poll only decides the ladder
   // shape and whether anything is still running; surplus iterations after the last trajectory finished are launches whose every
   // lane exits on its phase check).  A whole window ahead (4) lags the ladder adaptation of converging solves by a window and costs
@@ -887,7 +889,6 @@ struct SolveRun {
   hipEvent_t poll_evs[2] = {nullptr, nullptr};
   int win_enq = 0, win_dig = 0, win_it[2] = {0, 0};
   int outstanding() const { return win_enq - win_dig; }
-  static int run_ahead() { static const int v = [] { const char *e = std::getenv("CDDP_HIP_RUNAHEAD"); const int n = e ? std::atoi(e) : 1; return (n >= 0 && n <= 16) ? n : 1; }(); return v; }
   bool ran_ahead = false;
   int post_poll(hipStream_t s) {
     const int slot = win_enq & 1;
@@ -915,8 +916,7 @@ struct SolveRun {
     // CDDP_HIP_EVENT_FENCE=1 restores the default flags (A/B: profiles/r04_graph_ab.md)
     if (ev_used == h->ev_pool.size()) {
       hipEvent_t e;
-      static const bool fence = [] { const char *v = std::getenv("CDDP_HIP_EVENT_FENCE"); return v && v[0] == '1'; }();
-      if ((fence ? hipEventCreate(&e) : hipEventCreateWithFlags(&e, hipEventDisableSystemFence)) != hipSuccess) return;
+      if ((h->knob->event_fence ? hipEventCreate(&e) : hipEventCreateWithFlags(&e, hipEventDisableSystemFence)) != hipSuccess) return;
       h->ev_pool.push_back(e);
     }
     const size_t slot = (size_t)6 * (size_t)(outer - 1) + (size_t)point;
@@ -956,7 +956,7 @@ struct SolveRun {
       if (waves_all <= 2048) { one_stage = true; }
       else { one_stage = false; k1 = k_cap2; }
     } else {
-      one_stage = false; k1 = std::max(1, std::min(kq + ladder_margin(), k_cap));   // + 1: the histogram drifts between polls (CDDP_HIP_LS_MARGIN)
+      one_stage = false; k1 = std::max(1, std::min(kq + h->knob->ls_margin, k_cap));   // + 1: the histogram drifts between polls (CDDP_HIP_LS_MARGIN)
       // A chip that the whole ladder fills at most twice (one-stage territory) gains from a short first stage only what the
       // smaller launch saves over the rollout's latency floor (C2: 291 -> ~200 us at five step sizes), and loses a full second
       // rollout + costate + update (~235 us) whenever ONE trajectory walks past k1: kept only for a first stage of at most 768
@@ -967,12 +967,13 @@ struct SolveRun {
       // half of the ladder saves next to nothing over the whole ladder, while ONE trajectory past k1 costs a second full chain -- and
       // the histogram of such solves drifts towards smaller steps from window to window (resident LogDDP, cart-pole: k1 = 6 ... 10 of 11
       // during iterations 4 - 15; 34.3 -> 32.7 ms per solve with the whole ladder at once, profiles/r04_ladder_small.md).  Heavier plants keep the
-      // short first stage (C4 share, 704 wavefronts: 955 ms adaptive against 985 ms with the whole ladder at once).  "Half" became "a third" after a sweep (ladder_frac).
+      // short first stage (C4 share, 704 wavefronts: 955 ms adaptive against 985 ms with the whole ladder at once).  "Half" became "a third" after a sweep (CDDP_HIP_LS_SMALL_FRAC;
+      // 2 / 3 / 4 / 11 -> C2-CLDDP 30.55 / 30.33 / 30.29 / 30.3 ms, pendulum MSIPDDP 15.2 / 15.0 / 15.05 / 17.3).
       // (the two-role rollouts of LogDDP / MSIPDDP, round 5, put two wavefronts per (tile, alpha) in the launch: the same ladders, twice the count)
       const long small_cap = (h->P.solver == CDDP_HIP_SOLVER_LOGDDP || h->P.solver == CDDP_HIP_SOLVER_MSIPDDP) ? 2048 : 1024;
-      if (waves_all <= small_cap && h->P.nx <= 8 && ladder_frac() * k1 > na) one_stage = true;
+      if (waves_all <= small_cap && h->P.nx <= 8 && h->knob->ls_small_frac * k1 > na) one_stage = true;
     }
-    if (std::getenv("CDDP_HIP_DEBUG_LADDER")) {
+    if (h->knob->debug_ladder) {
       std::fprintf(stderr, "[ladder] it=%d total=%ld kq=%d -> %s k1=%d hist:", outer, total, kq, one_stage ? "one" : "two", k1);
       for (int a = 0; a <= na; ++a) std::fprintf(stderr, " %ld", hd[a]);
       std::fprintf(stderr, "\n");
@@ -991,7 +992,7 @@ struct SolveRun {
     // Class timing: up to six mark points per outer iteration (0 start, 1 after the sweep, 2 after rollout stage 1,
     // 3 after update 1, 4 after rollout stage 2, 5 after update 2).  Every event costs ~5 us of queue time, so only
     // the points the selected detail needs are recorded (cddp_hip_set_timing_detail): 2 per iteration by default.
-    { const char *e = std::getenv("CDDP_HIP_GRAPH"); use_graph = e && e[0] == '1'; }
+    use_graph = h->knob->graph;
     if (use_graph && conc > 1) {   // captured kernel nodes do not carry a stream's CU mask: the static partition is lost in replay (experiment switch; results unchanged)
       static bool said = false;
       if (!said) { said = true; std::fprintf(stderr, "[cddp_hip] CDDP_HIP_GRAPH=1: graph replay does not keep the CU-masked streams' partition; the tile groups share the whole chip\n"); }
@@ -1012,18 +1013,16 @@ struct SolveRun {
     // per iteration; the first-success rule is then applied to the recorded trials, so results are unchanged.
     // (the two-role rollout of the path-constrained layouts runs two wavefronts per tile and alpha; with several tile
     // groups in flight the chip is shared: the group's wavefront count is scaled by the number of groups)
-    waves_all = (long)conc * (long)((d.B + 63) / 64) * na * (((P.solver == CDDP_HIP_SOLVER_IPDDP && (ks->cst_size > 0 || (d.te_cst && P.m > 0))) || P.solver == CDDP_HIP_SOLVER_MSIPDDP || P.solver == CDDP_HIP_SOLVER_LOGDDP) ? 2 : 1);   // (layouts with two consumer waves, KernelSet::k4_waves = 3, keep the count the ladder rules were tuned with: their third wave is light)
+    waves_all = (long)conc * (long)((d.B + 63) / 64) * na * (((P.solver == CDDP_HIP_SOLVER_IPDDP && (ks->cst_size > 0 || (d.te_cst && P.m > 0))) || P.solver == CDDP_HIP_SOLVER_MSIPDDP || P.solver == CDDP_HIP_SOLVER_LOGDDP) ? 2 : 1);   // (layouts with two consumer waves keep the count the ladder rules were tuned with: their third wave is light)
     // CDDP_HIP_LS_STAGES=2 forces the two-stage ladder (alpha_0 first, the rest only for trajectories that need it)
     // regardless of the fill heuristic -- same selected trials; used by the tests to cover both launch shapes.
-    const char *ls_env = std::getenv("CDDP_HIP_LS_STAGES");
-    const bool force_two = ls_env && ls_env[0] == '2', force_one = ls_env && ls_env[0] == '1';
+    const bool force_two = h->knob->ls_stages == '2', force_one = h->knob->ls_stages == '1';
     const long per_alpha = std::max(1L, waves_all / std::max(1, na));
     per_alpha_waves = per_alpha;
-    { const char *e = std::getenv("CDDP_HIP_LS_TWO_MAX_WAVES"); two_stage_max_waves = e ? std::atol(e) : 768; }
+    two_stage_max_waves = h->knob->ls_two_max_waves;
     k_cap = (int)std::max(1L, std::min((long)na - 1, 1024 / per_alpha));    // one wavefront per SIMD
     k_cap2 = (int)std::max(1L, std::min((long)na - 1, 2048 / per_alpha));   // two (a ladder that is needed almost whole)
-    const char *kf_env = std::getenv("CDDP_HIP_LS_FIRST");
-    const int k_forced = kf_env ? std::atoi(kf_env) : 0;
+    const int k_forced = h->knob->ls_first;
     pinned = !first_rule || na == 1 || force_one || force_two || (k_forced >= 1 && k_forced < na);
     one_stage = !first_rule || na == 1 || force_one || (waves_all <= 2048 && !force_two);
     k1 = force_two ? 1 : k_cap2;
@@ -1031,7 +1030,7 @@ struct SolveRun {
     hist_now.assign(na + 1, 0); hist_prev.assign(na + 1, 0);
     HIPCHK(hipMemsetAsync(d.win_hist, 0, sizeof(int) * (CDDP_HIP_MAX_ALPHAS + 1), s));
     wall0 = std::chrono::steady_clock::now();
-    if (max_it <= 0) { ks->update(d, 2, 0, 1, 1, s); ++launches; done = true; }
+    if (max_it <= 0) { ks->update(d, h->route, 2, 0, 1, 1, s); ++launches; done = true; }
     return 0;
   }
 
@@ -1041,54 +1040,48 @@ struct SolveRun {
     const DevBuf &d = h->d;
     hipStream_t s = h->stream;
     const KernelSet *ks = h->ks;
+    const Route &r = h->route;
     // CU-partitioned streams (CuPlan): the rollout on its own stream, ordered against the main stream by two events per launch
     hipStream_t sf = h->cu.fwd ? h->cu.fwd : s;
     auto to_fwd = [&](int k) { if (sf != s) { order_check(hipEventRecord(h->cu.ev[k], s)); order_check(hipStreamWaitEvent(sf, h->cu.ev[k], 0)); } };
     auto from_fwd = [&](int k) { if (sf != s) { order_check(hipEventRecord(h->cu.ev[k], sf)); order_check(hipStreamWaitEvent(s, h->cu.ev[k], 0)); } };
     two_stage_marks = !one_stage;
     mark(0);
-    h->last_t4 = ks->t4_layout(d);   // the layout this fill writes (cddp_hip_get_linearization reads it back with the same rule's answer)
-    ks->derivs(d, 0, s);
+    ks->derivs(d, r, 0, s);
     tl_sweep_hop = h->cu.sweep ? &h->cu.hop : nullptr;
-    ks->backward(d, P.solver, 0, 1, s);
+    ks->backward(d, r, P.solver, 0, 1, s);
     tl_sweep_hop = nullptr;
     mark(1);
     to_fwd(0);
     if (fwd_wait) hipStreamWaitEvent(sf, fwd_wait, 0);
     if (one_stage) {
-      ks->forward(d, P.solver, 0, na, PH_FWD1, 0, first_rule ? 1 : 0, sf);
+      ks->forward(d, r, P.solver, 0, na, PH_FWD1, 0, first_rule ? 1 : 0, sf);
       if (fwd_done) hipEventRecord(fwd_done, sf);
       from_fwd(1);
       mark(2);
-      ks->costate(d, P.solver, 0, na, PH_FWD1, 0, first_rule ? 1 : 2, s);   // best-merit rule: the candidate winner's costate only (k_costate)
-      ks->update(d, 1, na, last, 1, s);
+      ks->costate(d, r, P.solver, 0, na, PH_FWD1, 0, first_rule ? 1 : 2, s);   // best-merit rule: the candidate winner's costate only (k_costate)
+      ks->update(d, r, 1, na, last, 1, s);
       mark(3);
       launches += 4;
     } else {
-      ks->forward(d, P.solver, 0, k1, PH_FWD1, 0, 1, sf);
+      ks->forward(d, r, P.solver, 0, k1, PH_FWD1, 0, 1, sf);
       from_fwd(1);
       mark(2);
-      ks->costate(d, P.solver, 0, k1, PH_FWD1, 0, 1, s);
-      ks->update(d, 1, k1, last, 0, s);
+      ks->costate(d, r, P.solver, 0, k1, PH_FWD1, 0, 1, s);
+      ks->update(d, r, 1, k1, last, 0, s);
       mark(3);
       to_fwd(2);
-      ks->forward(d, P.solver, k1, na - k1, PH_FWD2, 0, 1, sf);
+      ks->forward(d, r, P.solver, k1, na - k1, PH_FWD2, 0, 1, sf);
       if (fwd_done) hipEventRecord(fwd_done, sf);
       from_fwd(3);
       mark(4);
-      ks->costate(d, P.solver, k1, na - k1, PH_FWD2, 0, 1, s);
-      ks->update(d, 2, na, last, 1, s);
+      ks->costate(d, r, P.solver, k1, na - k1, PH_FWD2, 0, 1, s);
+      ks->update(d, r, 2, na, last, 1, s);
       mark(5);
       launches += 6;
     }
   }
-  static int ladder_frac() { static const int v = [] { const char *e = std::getenv("CDDP_HIP_LS_SMALL_FRAC"); const int n = e ? std::atoi(e) : 3; return n >= 1 ? n : 3; }(); return v; }   // "more than 1 / frac of the ladder" in the rule above (CDDP_HIP_LS_SMALL_FRAC; 2 / 3 / 4 / 11 -> C2-CLDDP 30.55 / 30.33 / 30.29 / 30.3 ms, pendulum MSIPDDP 15.2 / 15.0 / 15.05 / 17.3)
-  static int ladder_margin() { static const int v = [] { const char *e = std::getenv("CDDP_HIP_LS_MARGIN"); const int n = e ? std::atoi(e) : 1; return (n >= 0 && n <= 8) ? n : 1; }(); return v; }
-  static int poll_every() {   // CDDP_HIP_POLL_EVERY=n (experiment): iterations between two "anything still running?" polls (default 4)
-    static const int v = [] { const char *e = std::getenv("CDDP_HIP_POLL_EVERY"); const int n = e ? std::atoi(e) : 4; return n >= 1 ? n : 4; }();
-    return v;
-  }
-  static bool polled_iteration(int it, int max_it, bool pinned) { return it % poll_every() == 0 || it == max_it || (it <= 2 && !pinned); }
+  bool polled_iteration(int i) const { return i % h->knob->poll_every == 0 || i == max_it || (i <= 2 && !pinned); }
 
   // CDDP_HIP_GRAPH=1 (experiment): the iterations between two polls are captured ONCE per (ladder shape, window
   // length, last-iteration flag) into a hipGraph and replayed with one hipGraphLaunch -- every kernel argument of an iteration is
@@ -1098,20 +1091,10 @@ struct SolveRun {
   int advance_graph() {
     const hipStream_t s = h->stream;
     int w = 0;
-    while (it + w < max_it) { ++w; if (polled_iteration(it + w, max_it, pinned)) break; }
+    while (it + w < max_it) { ++w; if (polled_iteration(it + w)) break; }
     if (w == 0) { done = true; return 0; }
     const int last = (it + w == max_it) ? 1 : 0;
     const unsigned long long key = ((unsigned long long)(one_stage ? 0 : k1) << 16) | ((unsigned long long)w << 4) | (unsigned long long)last;
-    {   // a captured window bakes in the kernels launch.hpp selected from the environment: drop the cache when that selection changed
-      unsigned sig = 2166136261u;
-      for (const char *v : {"CDDP_HIP_SWEEP", "CDDP_HIP_T4", "CDDP_HIP_K4_NA", "CDDP_HIP_COOP_H", "CDDP_HIP_COOP_W", "CDDP_HIP_MS_ROLLOUT", "CDDP_HIP_LG_ROLLOUT",
-                            "CDDP_HIP_K4_CONSUMERS", "CDDP_HIP_SWEEP_ROLES"}) {   // every variable launch.hpp reads per launch
-        const char *e = std::getenv(v);
-        for (const char *c = e ? e : "-"; *c; ++c) sig = (sig ^ (unsigned char)*c) * 16777619u;
-        sig = (sig ^ 0xffu) * 16777619u;
-      }
-      if (sig != h->env_sig) { for (auto &kv : h->graphs) hipGraphExecDestroy(kv.second); h->graphs.clear(); h->graph_launches.clear(); h->env_sig = sig; }
-    }
     auto f = h->graphs.find(key);
     if (f == h->graphs.end()) {
       hipGraph_t g = nullptr; hipGraphExec_t ge = nullptr;
@@ -1123,7 +1106,6 @@ struct SolveRun {
       hipGraphDestroy(g);
       launches = launches0;
       f = h->graphs.emplace(key, ge).first;
-      h->graph_launches.emplace(key, 0);
     }
     { const int l0 = launches; for (int j = 0; j < w; ++j) launches += one_stage ? 4 : 6; (void)l0; }
     HIPCHK(hipGraphLaunch(f->second, s));
@@ -1140,7 +1122,6 @@ struct SolveRun {
     const DevBuf &d = h->d;
     hipStream_t s = h->stream;
     if (use_graph && !(P.opt.max_cpu_time > 0.0)) return advance_graph();
-    constexpr int kPollEvery = 4;
     while (it < max_it) {
       ++it;
       if (P.opt.max_cpu_time > 0.0) {   // cddp_solver_base.cpp:77-90 (host clock, like the reference; the queue is drained first)
@@ -1157,9 +1138,9 @@ struct SolveRun {
       const int last = (it == max_it) ? 1 : 0;
       enqueue_iteration(last);
       // The "anything still running?" poll drains the group's queue (host round trip + an empty pipeline for the next
-      // launches), so it is made every kPollEvery iterations; the up-to-3 surplus iterations after the last
+      // launches), so it is made every Knobs::poll_every (4) iterations; the up-to-3 surplus iterations after the last
       // trajectory finished are launches whose every lane exits on its phase check.
-      if (polled_iteration(it, max_it, pinned)) {   // every kPollEvery iterations, the last one, and two early polls: the ladder statistics settle the shape
+      if (polled_iteration(it)) {   // every poll_every iterations, the last one, and two early polls: the ladder statistics settle the shape
         { int rc = post_poll(s); if (rc) return rc; }
         return 1;   // a poll is pending
       }
@@ -1170,7 +1151,7 @@ struct SolveRun {
   }
 
   int complete_poll() {   // digests the OLDEST outstanding poll
-    const int kPollEvery = poll_every();
+    const int kPollEvery = h->knob->poll_every;
     if (outstanding() <= 0) return 0;
     const int slot = win_dig & 1;
     HIPCHK(hipEventSynchronize(poll_evs[slot]));
@@ -1323,9 +1304,7 @@ static int in_get_linearization(Inner *h, double *A, double *Bm) {
   HIPCHK(hipStreamSynchronize(h->stream));
   const DevBuf &d = h->d;
   std::vector<double> buf;
-  // the layout the LAST derivative fill wrote (recorded at that launch: the environment may have been switched since)
-  const bool t4 = h->P.solver == CDDP_HIP_SOLVER_IPDDP && h->last_t4 != 0;
-  auto conv = t4 ? &from_t4 : &from_soa;
+  auto conv = h->route.t4 ? &from_t4 : &from_soa;   // the handle's stack layout (0 for every solver but IPDDP)
   if (A) { int rc = fetch(h, d.A, (size_t)d.N * h->P.nx * h->P.nx * d.Bp, buf); if (rc) return rc; conv(buf.data(), A, d.B, d.Bp, d.N, h->P.nx * h->P.nx); }
   if (Bm) { int rc = fetch(h, d.Bm, (size_t)d.N * h->P.nx * h->P.nu * d.Bp, buf); if (rc) return rc; conv(buf.data(), Bm, d.B, d.Bp, d.N, h->P.nx * h->P.nu); }
   return 0;
@@ -1448,11 +1427,11 @@ static int in_write_gather_records_device(Inner *h, void *device_ptr) {
 }  // extern "C" (reopened below)
 
 struct cddp_hip_handle {
+  Knobs knob;                // the switches, read when the handle is created (knobs.hpp); every group reads this copy
   std::vector<Inner *> g;
   std::vector<int> b0;       // first trajectory of each group
   int B = 0, device = 0;
   int conc = 1;              // groups in flight at once in cddp_hip_solve (pick_groups)
-  bool pingpong = false;     // two groups, rollouts alternating (CDDP_HIP_PINGPONG=1 with CDDP_HIP_GROUPS=2)
   hipEvent_t ev_pp[2] = {nullptr, nullptr};
   int nx = 0, nu = 0, N = 0, m = 0, mT = 0, pT = 0;
   hipStream_t user_stream = nullptr;   // cddp_hip_set_stream: work is ordered after / before this stream's work
@@ -1480,23 +1459,19 @@ namespace {
 //    C3 81.5 -> 78.9, C4 share 955 -> 916, C5 share 1041 -> 992; CLDDP + 1.4 %, LogDDP 0, MSIPDDP - 4 %: not partitioned), while the
 //    same two groups WITHOUT masks lose 3 - 5 % (their wavefronts share SIMDs) and any split that moves one kernel class to another
 //    stream pays ~20 us of cross-stream events per iteration.  *part = slices (1 = no masks); CDDP_HIP_PARTITION=n overrides (1 = off).
-int pick_groups(int batch, int n_alphas, int solver, int *conc, int *part) {
+int pick_groups(const Knobs &knob, int batch, int n_alphas, int solver, int *conc, int *part) {
   const int tiles = (batch + 63) / 64;
-  const char *e = std::getenv("CDDP_HIP_GROUPS");
-  int n = e ? std::atoi(e) : 0;
+  int n = knob.groups;
   *part = 1;
   if (n > 0) { n = std::max(1, std::min(n, tiles)); *conc = n; return n; }
   *conc = 1;
   int chunk_tiles = std::max(16, 2816 / (2 * std::max(1, n_alphas)));     // 128 tiles (8192 trajectories) at 11 step sizes
-  bool chunking = true;
-  if (const char *c = std::getenv("CDDP_HIP_CHUNK")) {
-    const int v = std::atoi(c);
-    if (v <= 0) chunking = false; else chunk_tiles = std::max(1, (v + 63) / 64);
-  }
+  const bool chunking = knob.chunking;
+  if (knob.chunk > 0) chunk_tiles = std::max(1, (knob.chunk + 63) / 64);
   const int chunks = chunking ? std::max(1, (tiles + chunk_tiles - 1) / chunk_tiles) : 1;
   int np = (solver == CDDP_HIP_SOLVER_IPDDP || solver == CDDP_HIP_SOLVER_CLDDP) ? 2 : 1;
-  if (const char *c = std::getenv("CDDP_HIP_PARTITION")) { const int v = std::atoi(c); if (v >= 1 && v <= 16 && 256 % v == 0) np = v; }
-  if (std::getenv("CDDP_HIP_CUMASK")) np = 1;                              // an explicit plan (experiments) replaces the default one
+  if (knob.partition && 256 % knob.partition == 0) np = knob.partition;
+  if (knob.cumask_set) np = 1;                              // an explicit plan (experiments) replaces the default one
   if (np > 1 && tiles / chunks >= 16 * np) { *conc = np; *part = np; return chunks * np; }
   return chunks;
 }
@@ -1529,10 +1504,11 @@ int cddp_hip_create(const cddp_hip_problem *problem, int batch, int device, cddp
   int conc = 1, part = 1;
   double ladder[CDDP_HIP_MAX_ALPHAS];
   const int n_ladder = cddp_hip_build_alphas(&problem->options, ladder, CDDP_HIP_MAX_ALPHAS);   // the real ladder length (it can stop early at ls_min_step_size)
-  const int tiles = (batch + 63) / 64, ng = pick_groups(batch, n_ladder, problem->solver, &conc, &part);
   cddp_hip_handle *h = new cddp_hip_handle();
+  const Knobs &knob = h->knob;
+  if (knob.fail_costate) std::fprintf(stderr, "[cddp_hip] TEST HOOK active: CDDP_HIP_TEST_FAIL_COSTATE=%d discards line-search trials -- results are not the solver's\n", knob.fail_costate);
+  const int tiles = (batch + 63) / 64, ng = pick_groups(knob, batch, n_ladder, problem->solver, &conc, &part);
   h->B = batch; h->device = device; h->conc = conc;
-  { const char *e = std::getenv("CDDP_HIP_PINGPONG"); h->pingpong = e && e[0] == '1'; }
   int t0 = 0;
   for (int k = 0; k < ng; ++k) {
     const int nt = tiles / ng + (k < tiles % ng ? 1 : 0);          // whole tiles per group, sizes differ by at most one tile
@@ -1541,14 +1517,14 @@ int cddp_hip_create(const cddp_hip_problem *problem, int batch, int device, cddp
     if (last <= first) continue;
     Inner *q = nullptr;
     CuSpec cus;
-    bool have_cu = cu_spec_for_group(k, &cus);
+    bool have_cu = cu_spec_for_group(knob, k, &cus);
     if (!have_cu && part > 1) {
       // slice k of `part` equal slices of the CU-mask bits of THIS device (bit i = XCC i % 8, so a multiple of 8 bits is the same number of
       // CUs on every XCD); a device or partition mode too small for two CUs per XCD and slice runs unpartitioned
       const int w = device_cu_count(device) / part / 8 * 8;
       if (w >= 16) { cus.lo[0] = (k % part) * w; cus.hi[0] = cus.lo[0] + w; have_cu = true; }
     }
-    int rc = in_create(problem, last - first, device, &q, have_cu ? &cus : nullptr);
+    int rc = in_create(problem, last - first, device, knob, have_cu ? &cus : nullptr, &q);
     if (rc) { for (Inner *p : h->g) in_destroy(p); delete h; return rc; }
     h->g.push_back(q); h->b0.push_back(first);
   }
@@ -1687,7 +1663,7 @@ int cddp_hip_solve(cddp_hip_handle *h, cddp_hip_stats *stats) {
   // The whole-handle time is the span from group 0's begin to an end event group 0's stream records after it has waited for
   // every other group's end.
   const int conc = std::max(1, std::min(h->conc, ng));
-  if (h->pingpong && ng == 2) {
+  if (h->knob.pingpong && ng == 2) {   // two groups, rollouts alternating (CDDP_HIP_PINGPONG=1 with CDDP_HIP_GROUPS=2)
     // two half-batch groups in lockstep, one iteration each in turn; rollouts serialised A1 B1 A2 B2 ... by events (SolveRun::fwd_wait)
     if (!h->ev_pp[0]) for (int k = 0; k < 2; ++k) HIPCHK(hipEventCreateWithFlags(&h->ev_pp[k], hipEventDisableTiming));
     for (int k = 0; k < 2; ++k) { int rc = run[k].begin(h->g[k], stats != nullptr, 1); if (rc) return rc; run[k].fwd_wait = h->ev_pp[1 - k]; run[k].fwd_done = h->ev_pp[k]; }
@@ -1706,13 +1682,13 @@ int cddp_hip_solve(cddp_hip_handle *h, cddp_hip_stats *stats) {
     const int top = std::min(ng, base + conc);
     for (int k = base; k < top; ++k) { int rc = run[k].begin(h->g[k], stats != nullptr, conc); if (rc) return rc; run[k].wall0 = solve_t0; }   // ONE max_cpu_time clock per solve, shared by successive chunks
     // each pass, per group: no poll outstanding -> enqueue iterations up to the next polled one; one outstanding and not yet run
-    // ahead -> enqueue run_ahead() more iterations behind it; otherwise digest the oldest poll.  So a group's queue holds work while
+    // ahead -> enqueue Knobs::run_ahead more iterations behind it; otherwise digest the oldest poll.  So a group's queue holds work while
     // the host waits for a poll, and the host never blocks on one group while another has nothing queued
     for (;;) {
       bool any = false;
       for (int k = base; k < top; ++k) {
         SolveRun &r = run[k];
-        const int ra = (h->g[k]->P.opt.max_cpu_time > 0.0 || r.use_graph || r.it < SolveRun::poll_every()) ? 0 : SolveRun::run_ahead();
+        const int ra = (h->g[k]->P.opt.max_cpu_time > 0.0 || r.use_graph || r.it < h->g[k]->knob->poll_every) ? 0 : h->g[k]->knob->run_ahead;
         if (!r.done && r.outstanding() == 0) { int rc = r.advance(); if (rc < 0) return rc; r.ran_ahead = false; any = true; }
         else if (!r.done && r.outstanding() == 1 && ra > 0 && !r.ran_ahead) { int rc = r.advance(ra); if (rc < 0) return rc; r.ran_ahead = true; any = true; }
         else if (r.outstanding() > 0) { int rc = r.complete_poll(); if (rc) return rc; r.ran_ahead = r.outstanding() > 0; any = true; }

@@ -85,6 +85,51 @@ def test_graph_replay_of_iteration_windows_is_bitwise_the_stream_loop(api, kind,
 
 
 @pytest.mark.gpu
+def test_kernel_route_is_fixed_when_the_handle_is_created(api, monkeypatch):
+    """The resident solver reads its CDDP_HIP_* switches once, in cddp_hip_create (cddp-cpp_amd/csrc/knobs.hpp): a handle keeps the
+    kernel route it was created with, whatever the environment says when it runs.  The matrix-core sweep (CDDP_HIP_SWEEP=mfma) is not
+    bitwise the reference-order one (tests/test_mfma_sweep.py), so the bits tell the two routes apart."""
+    from test_gpu_parity import make
+    from test_gpu_parity_r2 import _inputs
+    p = make(api, "quad12_ipddp_box")
+    B = 70
+    x0, U0, X0 = _inputs(api, p, B, 20261016)
+
+    def env(name, value):
+        if value is None:
+            monkeypatch.delenv(name, raising=False)
+        else:
+            monkeypatch.setenv(name, value)
+
+    def step(create_with, run_with):   # step level, as tests/test_mfma_sweep.py::_sweep
+        env("CDDP_HIP_SWEEP", create_with)
+        hs = api.HipBatchSolver(p, B)
+        env("CDDP_HIP_SWEEP", run_with)
+        hs.set_initial(x0, U0, X0); hs.initialize()
+        ok = hs.backward(); K, k = hs.gains(); Vx, Vxx = hs.value(); tr = hs.forward(0.5 ** np.arange(4))
+        hs.close()
+        return [ok, K, k, Vx, Vxx] + [tr[f].copy() for f in tr.dtype.names]
+
+    def same(xs, ys):
+        return all(a.shape == b.shape and a.tobytes() == b.tobytes() for a, b in zip(xs, ys))
+
+    ref, ref_mfma = step(None, None), step("mfma", "mfma")
+    assert not same(ref, ref_mfma), "the two sweeps must be told apart"
+    assert same(step(None, "mfma"), ref), "a handle created without CDDP_HIP_SWEEP ran another sweep"
+    assert same(step("mfma", None), ref_mfma), "a handle created under CDDP_HIP_SWEEP=mfma ran another sweep"
+
+    # the stacks' layout is the handle's too: linearization() decodes what the solve wrote, whatever CDDP_HIP_T4 says later
+    env("CDDP_HIP_SWEEP", None); env("CDDP_HIP_T4", None)
+    hs = api.HipBatchSolver(p, B)
+    hs.set_initial(x0, U0, X0); hs.solve()
+    lin = hs.linearization()
+    env("CDDP_HIP_T4", "0")
+    lin2 = hs.linearization()
+    hs.close()
+    assert same(lin, lin2)
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("kind", ["cartpole_ipddp", "cartpole_logddp"])
 def test_successive_chunks_of_a_large_batch_do_not_change_results(api, kind, monkeypatch):
     """A batch above 8192 trajectories is solved as successive chunks on the handle (capi.hip::pick_groups, one chunk in flight at a
