@@ -615,14 +615,18 @@ LaunchFn pick_coop(int nx, int nu, int m) {
   return nullptr;
 }
 
-// batch-major [b][r] <-> stack [r][Bp] (r = t * E + e), one thread per element, b fastest: the stack side is coalesced
+// batch-major [b][r] <-> stack [r][Bp] (r = t * E + e), one thread per element, b fastest: the stack side is coalesced.  Rows past
+// gridDim.y (at most kTransposeRows: the grid's y extent is 65535) are taken by a stride loop -- F_xx at nx = 12 has N * 1728 rows.
+constexpr int kTransposeRows = 65535;
 __global__ void k_stack_transpose(double *aos, double *soa, int B, int Bp, int R, int to_stack, int E, int t4) {
-  const int b = blockIdx.x * blockDim.x + threadIdx.x, r = blockIdx.y;
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= B) return;
-  size_t si = (size_t)r * Bp + b;
-  if (t4) { const int t = r / E, e = r - t * E; si = (((size_t)t * (size_t)(Bp >> 2) + (size_t)(b >> 2)) * E + e) * 4 + (size_t)(b & 3); }
-  if (to_stack) soa[si] = aos[(size_t)b * R + r];
-  else aos[(size_t)b * R + r] = soa[si];
+  for (int r = blockIdx.y; r < R; r += gridDim.y) {
+    size_t si = (size_t)r * Bp + b;
+    if (t4) { const int t = r / E, e = r - t * E; si = (((size_t)t * (size_t)(Bp >> 2) + (size_t)(b >> 2)) * E + e) * 4 + (size_t)(b & 3); }
+    if (to_stack) soa[si] = aos[(size_t)b * R + r];
+    else aos[(size_t)b * R + r] = soa[si];
+  }
 }
 }  // namespace
 
@@ -670,25 +674,31 @@ int stage_reserve(cddp_hip_stack_handle *h, size_t n) {
   h->d_stage = (double *)q; h->stage_cap = n;
   return 0;
 }
-int upload(cddp_hip_stack_handle *h, const double *src, double *dst, int T, int E) {
+// Layout of one device array: kPerStep, a per-step stack or output ([t][e][Bp], or tile-minor on a t4 handle, whatever the horizon);
+// kPlain, the [1][E][Bp] inputs and per-trajectory arrays (V_xN, V_xxN, H_T, b_T, lambda_prev, floor, dlambda, dV), plain on every handle.
+enum StackLayout { kPlain = 0, kPerStep = 1 };
+inline int tile_minor(const cddp_hip_stack_handle *h, StackLayout l) { return (l == kPerStep && h->a.t4) ? 1 : 0; }
+inline dim3 transpose_grid(const cddp_hip_stack_handle *h, int R) {
+  return dim3((unsigned)((h->B + 255) / 256), (unsigned)std::min(R, kTransposeRows));
+}
+int upload(cddp_hip_stack_handle *h, const double *src, double *dst, int T, int E, StackLayout l) {
   if (!src) return 0;
   const size_t n = (size_t)T * E * h->B;
   if (n == 0) return 0;
   { int rc = stage_reserve(h, n); if (rc) return rc; }
   SCHK(hipMemcpyAsync(h->d_stage, src, n * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  hipLaunchKernelGGL(k_stack_transpose, dim3((unsigned)((h->B + 255) / 256), (unsigned)(T * E)), dim3(256), 0, h->stream, h->d_stage, dst, h->B, h->Bp, T * E, 1, E,
-                     (h->a.t4 && T > 1) ? 1 : 0);
+  hipLaunchKernelGGL(k_stack_transpose, transpose_grid(h, T * E), dim3(256), 0, h->stream, h->d_stage, dst, h->B, h->Bp, T * E, 1, E, tile_minor(h, l));
   SCHK(hipGetLastError());
   SCHK(hipStreamSynchronize(h->stream));   // the caller may reuse src; the staging buffer is reused by the next upload
   return 0;
 }
-int download(cddp_hip_stack_handle *h, const double *src, double *dst, int T, int E) {
+int download(cddp_hip_stack_handle *h, const double *src, double *dst, int T, int E, StackLayout l) {
   if (!dst) return 0;
   const size_t n = (size_t)T * E * h->B;
   if (n == 0) return 0;
   { int rc = stage_reserve(h, n); if (rc) return rc; }
-  hipLaunchKernelGGL(k_stack_transpose, dim3((unsigned)((h->B + 255) / 256), (unsigned)(T * E)), dim3(256), 0, h->stream, h->d_stage, const_cast<double *>(src), h->B, h->Bp, T * E, 0, E,
-                     (h->a.t4 && T > 1) ? 1 : 0);
+  hipLaunchKernelGGL(k_stack_transpose, transpose_grid(h, T * E), dim3(256), 0, h->stream, h->d_stage, const_cast<double *>(src), h->B, h->Bp, T * E, 0, E,
+                     tile_minor(h, l));
   SCHK(hipGetLastError());
   SCHK(hipMemcpyAsync(dst, h->d_stage, n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   SCHK(hipStreamSynchronize(h->stream));
@@ -762,10 +772,11 @@ int cddp_hip_set_stacks(cddp_hip_stack_handle *h, const double *fx, const double
   if (!h->have_dyn && !(fx && fu && lx && lu && lxx && luu && lux && VxN && VxxN))
     return sfail(-1, "the first cddp_hip_set_stacks call must supply every stack (later calls may pass NULL to keep one)");
   const int N = h->N, nx = h->nx, nu = h->nu;
-  struct { const double *src; const double *dst; int T, E; } items[] = {
-      {fx, h->a.fx, N, nx * nx}, {fu, h->a.fu, N, nx * nu}, {lx, h->a.lx, N, nx}, {lu, h->a.lu, N, nu}, {lxx, h->a.lxx, N, nx * nx},
-      {luu, h->a.luu, N, nu * nu}, {lux, h->a.lux, N, nu * nx}, {VxN, h->a.VxN, 1, nx}, {VxxN, h->a.VxxN, 1, nx * nx}};
-  for (auto &it : items) { int rc = upload(h, it.src, (double *)it.dst, it.T, it.E); if (rc) return rc; }
+  struct { const double *src; const double *dst; int T, E; StackLayout l; } items[] = {
+      {fx, h->a.fx, N, nx * nx, kPerStep}, {fu, h->a.fu, N, nx * nu, kPerStep}, {lx, h->a.lx, N, nx, kPerStep}, {lu, h->a.lu, N, nu, kPerStep},
+      {lxx, h->a.lxx, N, nx * nx, kPerStep}, {luu, h->a.luu, N, nu * nu, kPerStep}, {lux, h->a.lux, N, nu * nx, kPerStep},
+      {VxN, h->a.VxN, 1, nx, kPlain}, {VxxN, h->a.VxxN, 1, nx * nx, kPlain}};
+  for (auto &it : items) { int rc = upload(h, it.src, (double *)it.dst, it.T, it.E, it.l); if (rc) return rc; }
   h->have_dyn = true; h->swept = false;
   return 0;
 }
@@ -775,7 +786,7 @@ int cddp_hip_set_defect_stack(cddp_hip_stack_handle *h, const double *defects) {
   SCHK(hipSetDevice(h->device));
   if (!defects) { h->a.dfc = nullptr; h->swept = false; return 0; }
   if (!h->d_dfc) { int rc = salloc(h, &h->d_dfc, (size_t)h->N * h->nx * h->Bp); if (rc) return rc; }
-  int rc = upload(h, defects, h->d_dfc, h->N, h->nx); if (rc) return rc;
+  int rc = upload(h, defects, h->d_dfc, h->N, h->nx, kPerStep); if (rc) return rc;
   h->a.dfc = h->d_dfc; h->swept = false;
   return 0;
 }
@@ -813,7 +824,7 @@ int cddp_hip_set_control_box(cddp_hip_stack_handle *h, const double *lower, cons
     SCHK(hipMemcpyAsync(h->d_up, upper, sizeof(double) * nu, hipMemcpyHostToDevice, h->stream));
     SCHK(hipStreamSynchronize(h->stream));
   }
-  if (U) { int rc = upload(h, U, h->d_U, N, nu); if (rc) return rc; }
+  if (U) { int rc = upload(h, U, h->d_U, N, nu, kPerStep); if (rc) return rc; }
   h->a.lo = h->d_lo; h->a.up = h->d_up; h->a.U = h->d_U;
   h->swept = false;
   return 0;
@@ -832,7 +843,7 @@ int cddp_hip_set_hessian_stacks(cddp_hip_stack_handle *h, const double *Fxx, con
   }
   struct { const double *src; double *dst; int T, E; } items[] = {
       {Fxx, h->d_Fxx, N, nx * nx * nx}, {Fuu, h->d_Fuu, N, nx * nu * nu}, {Fux, h->d_Fux, N, nx * nu * nx}};
-  for (auto &it : items) { int rc = upload(h, it.src, it.dst, it.T, it.E); if (rc) return rc; }
+  for (auto &it : items) { int rc = upload(h, it.src, it.dst, it.T, it.E, kPerStep); if (rc) return rc; }
   h->a.Fxx = h->d_Fxx; h->a.Fuu = h->d_Fuu; h->a.Fux = h->d_Fux;
   h->swept = false;
   return 0;
@@ -846,7 +857,7 @@ int cddp_hip_set_constraint_stacks(cddp_hip_stack_handle *h, const double *y, co
   const int N = h->N, nx = h->nx, nu = h->nu, m = h->m;
   struct { const double *src; const double *dst; int T, E; } items[] = {
       {y, h->a.y, N, m}, {s, h->a.s, N, m}, {g, h->a.g, N, m}, {Gx, h->a.Gx, N, m * nx}, {Gu, h->a.Gu, N, m * nu}};
-  for (auto &it : items) { int rc = upload(h, it.src, (double *)it.dst, it.T, it.E); if (rc) return rc; }
+  for (auto &it : items) { int rc = upload(h, it.src, (double *)it.dst, it.T, it.E, kPerStep); if (rc) return rc; }
   h->have_con = true; h->swept = false;
   return 0;
 }
@@ -877,10 +888,10 @@ int cddp_hip_set_terminal_equality(cddp_hip_stack_handle *h, int pT, const doubl
   }
   h->te.pT = pT;
   int rc;
-  if ((rc = upload(h, HT, const_cast<double *>(h->te.HT), pT, nx))) return rc;
-  if ((rc = upload(h, bT, const_cast<double *>(h->te.bT), 1, pT))) return rc;
-  if ((rc = upload(h, lambda_prev, const_cast<double *>(h->te.lam_prev), 1, pT))) return rc;
-  if ((rc = upload(h, reg_floor, const_cast<double *>(h->te.floor_), 1, 1))) return rc;
+  if ((rc = upload(h, HT, const_cast<double *>(h->te.HT), pT, nx, kPlain))) return rc;   // (k_stacks_te reads H_T [r][i][Bp] on every handle)
+  if ((rc = upload(h, bT, const_cast<double *>(h->te.bT), 1, pT, kPlain))) return rc;
+  if ((rc = upload(h, lambda_prev, const_cast<double *>(h->te.lam_prev), 1, pT, kPlain))) return rc;
+  if ((rc = upload(h, reg_floor, const_cast<double *>(h->te.floor_), 1, 1, kPlain))) return rc;
   h->have_te = true;
   return 0;
 }
@@ -890,8 +901,8 @@ int cddp_hip_stacks_get_terminal(cddp_hip_stack_handle *h, double *dlambda, doub
   if (!h->swept_te) return sfail(-1, "no terminal-equality sweep result");
   SCHK(hipSetDevice(h->device));
   int rc;
-  if ((rc = download(h, h->te.dlam, dlambda, 1, h->te.pT))) return rc;
-  if ((rc = download(h, h->te.dX, dX, h->N + 1, h->nx))) return rc;
+  if ((rc = download(h, h->te.dlam, dlambda, 1, h->te.pT, kPlain))) return rc;
+  if ((rc = download(h, h->te.dX, dX, h->N + 1, h->nx, kPerStep))) return rc;
   return 0;
 }
 
@@ -999,11 +1010,11 @@ int cddp_hip_stacks_get_gains(cddp_hip_stack_handle *h, double *K, double *k, do
   SCHK(hipSetDevice(h->device));
   const int N = h->N, nx = h->nx, nu = h->nu;
   int rc;
-  if ((rc = download(h, h->a.K, K, N, nu * nx))) return rc;
-  if ((rc = download(h, h->a.k, k, N, nu))) return rc;
-  if ((rc = download(h, h->a.Vx, Vx, N + 1, nx))) return rc;
-  if ((rc = download(h, h->a.Vxx, Vxx, N + 1, nx * nx))) return rc;
-  if ((rc = download(h, h->a.dV, dV, 1, 2))) return rc;
+  if ((rc = download(h, h->a.K, K, N, nu * nx, kPerStep))) return rc;
+  if ((rc = download(h, h->a.k, k, N, nu, kPerStep))) return rc;
+  if ((rc = download(h, h->a.Vx, Vx, N + 1, nx, kPerStep))) return rc;
+  if ((rc = download(h, h->a.Vxx, Vxx, N + 1, nx * nx, kPerStep))) return rc;
+  if ((rc = download(h, h->a.dV, dV, 1, 2, kPlain))) return rc;
   return 0;
 }
 
@@ -1013,11 +1024,11 @@ int cddp_hip_stacks_get_constraint_gains(cddp_hip_stack_handle *h, double *k_y, 
   SCHK(hipSetDevice(h->device));
   const int N = h->N, nx = h->nx, m = h->m;
   int rc;
-  if ((rc = download(h, h->a.ky, k_y, N, m))) return rc;
-  if ((rc = download(h, h->a.Ky, K_y, N, m * nx))) return rc;
-  if ((rc = download(h, h->a.ks, k_s, N, m))) return rc;
-  if ((rc = download(h, h->a.Ks, K_s, N, m * nx))) return rc;
-  if ((rc = download(h, h->a.dX, dX, N + 1, nx))) return rc;
+  if ((rc = download(h, h->a.ky, k_y, N, m, kPerStep))) return rc;
+  if ((rc = download(h, h->a.Ky, K_y, N, m * nx, kPerStep))) return rc;
+  if ((rc = download(h, h->a.ks, k_s, N, m, kPerStep))) return rc;
+  if ((rc = download(h, h->a.Ks, K_s, N, m * nx, kPerStep))) return rc;
+  if ((rc = download(h, h->a.dX, dX, N + 1, nx, kPerStep))) return rc;
   return 0;
 }
 

@@ -410,7 +410,11 @@ TERMINAL_PLUGIN_CASES = {
     "di_box_term_eq": ("di", 12, 0.1, [1.0, 0.0], 1.0, 0.1, 1.0, (-8.0, 8.0), {"T": ("eq", [0.0, 0.0])}, True),
     "di_term_eq_and_ineq": ("di", 12, 0.1, [1.0, 0.0], 1.0, 0.1, 1.0, None, {"A_ineq": ("ineq", [[0.0, 1.0]], [0.4]), "B_eq": ("eq", [0.2, 0.0])}, True),
     "di_box_term_ineq": ("di", 12, 0.1, [1.0, 0.0], 1.0, 0.1, 10.0, (-6.0, 6.0), {"T": ("ineq", [[1.0, 0.0], [0.0, 1.0]], [0.3, 0.3])}, True),
+    # Hill-Clohessy-Wiltshire (nx = 6, nu = 3): the full-state terminal equality (pT = 6) runs on a handle whose default stacks are tile-minor
+    "hcw_term_eq": ("hcw", 20, 10.0, [10.0, 5.0, -2.0, 0.0, 0.0, 0.0], 0.0, 1.0, 0.0, None, {"T": ("eq", [0.0] * 6)}, True),
+    "hcw_box_term_eq": ("hcw", 20, 10.0, [10.0, 5.0, -2.0, 0.0, 0.0, 0.0], 0.0, 1.0, 0.0, (-0.5, 0.5), {"T": ("eq", [0.0] * 6)}, True),
 }
+HCW_MEAN_MOTION = math.sqrt(3.986004418e14 / (6371e3 + 500e3) ** 3)   # 500 km circular orbit (pyapi.hcw_problem)
 
 
 @pytest.mark.gpu
@@ -433,18 +437,27 @@ def test_plugin_solve_with_terminal_constraints_against_the_twin(api, pycddp, ca
         def get_state_hessian(self, s, c, t=0.0): return [np.zeros((2, 2)), np.zeros((2, 2))]
         def get_control_hessian(self, s, c, t=0.0): return [np.zeros((1, 1)), np.zeros((1, 1))]
         def get_cross_hessian(self, s, c, t=0.0): return [np.zeros((1, 2)), np.zeros((1, 2))]
-    nx = 1 if plant == "qss" else 2
+
+    class HCW(pycddp.DynamicalSystem):   # the twin's plant (spacecraft_linear.cpp:24-120) as a user DynamicalSystem
+        def __init__(self): super().__init__(6, 3, dt, "euler"); self.p = T.HCW(HCW_MEAN_MOTION, 1.0)
+        def get_continuous_dynamics(self, s, c, t=0.0): return self.p.f(np.asarray(s, float), np.asarray(c, float), t)
+        def get_state_jacobian(self, s, c, t=0.0): return self.p.A.copy()
+        def get_control_jacobian(self, s, c, t=0.0): return self.p.B.copy()
+        def get_state_hessian(self, s, c, t=0.0): return [np.zeros((6, 6)) for _ in range(6)]
+        def get_control_hessian(self, s, c, t=0.0): return [np.zeros((3, 3)) for _ in range(6)]
+        def get_cross_hessian(self, s, c, t=0.0): return [np.zeros((3, 6)) for _ in range(6)]
+    nx, nu = {"qss": (1, 1), "di": (2, 1), "hcw": (6, 3)}[plant]
     okw = dict(max_iterations=40, tolerance=1e-6, acceptable_tolerance=1e-6, use_ilqr=use_ilqr)
     o = _options(pycddp, **okw)
     o.regularization.initial_value = 1e-6; o.ipddp.barrier.mu_initial = 1e-1
     x0 = np.array(x0, float); goal = np.zeros(nx)
     sv = pycddp.CDDP(x0, goal, N, dt, o)
-    sv.set_dynamical_system(QSS() if plant == "qss" else DI())
-    sv.set_objective(pycddp.QuadraticObjective(Qs * np.eye(nx), Rs * np.eye(1), Qfs * np.eye(nx), goal, [], dt))
+    sv.set_dynamical_system({"qss": QSS, "di": DI, "hcw": HCW}[plant]())
+    sv.set_objective(pycddp.QuadraticObjective(Qs * np.eye(nx), Rs * np.eye(nu), Qfs * np.eye(nx), goal, [], dt))
     cons = {}
     if box is not None:
-        sv.add_constraint("ControlConstraint", pycddp.ControlConstraint(np.array([box[0]]), np.array([box[1]])))
-        cons["ControlConstraint"] = T.ControlBox([box[0]], [box[1]])
+        sv.add_constraint("ControlConstraint", pycddp.ControlConstraint(np.full(nu, box[0]), np.full(nu, box[1])))
+        cons["ControlConstraint"] = T.ControlBox([box[0]] * nu, [box[1]] * nu)
     for name, spec in term.items():
         sv.add_terminal_constraint(name, pycddp.TerminalEqualityConstraint(np.array(spec[1], float)) if spec[0] == "eq"
                                    else pycddp.TerminalInequalityConstraint(np.array(spec[1], float), np.array(spec[2], float)))
@@ -455,7 +468,8 @@ def test_plugin_solve_with_terminal_constraints_against_the_twin(api, pycddp, ca
     sw, th = C.c_int(), C.c_int()   # cddp_hip_plugin_last_stats describes the terminal-constraint solve, too
     assert api.load_hip().cddp_hip_plugin_last_stats(None, None, None, C.byref(sw), C.byref(th)) == 0
     assert sw.value >= sol.iterations_completed and th.value >= 1
-    tw = T.Twin(dict(solver="IPDDP", model=TwinQSS() if plant == "qss" else TwinDI(), integrator="euler", dt=dt, N=N, Q=Qs * np.eye(nx), R=Rs * np.eye(1),
+    twin_model = {"qss": TwinQSS, "di": TwinDI, "hcw": lambda: T.HCW(HCW_MEAN_MOTION, 1.0)}[plant]()
+    tw = T.Twin(dict(solver="IPDDP", model=twin_model, integrator="euler", dt=dt, N=N, Q=Qs * np.eye(nx), R=Rs * np.eye(nu),
                      Qf=Qfs * np.eye(nx), xref=list(goal), constraints=cons, terminal=term,
                      options=dict(max_iterations=40, tolerance=1e-6, acceptable_tolerance=1e-6, reg_initial_value=1e-6, mu_initial=1e-1, use_ilqr=use_ilqr)))
     tw.set_initial(x0, None)

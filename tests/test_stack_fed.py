@@ -139,21 +139,7 @@ def _plugin_problem(kind):
     raise KeyError(kind)
 
 
-def _twin_stacks(tw):
-    """What a host-plugin adapter hands to cddp_hip_set_stacks / cddp_hip_set_constraint_stacks for the twin's iterate."""
-    N, nx, nu, m = tw.N, tw.nx, tw.nu, tw.m
-    fx = np.zeros((N, nx, nx)); fu = np.zeros((N, nx, nu)); lx = np.zeros((N, nx)); lu = np.zeros((N, nu))
-    Gx = np.zeros((N, m, nx)); Gu = np.zeros((N, m, nu))
-    for t in range(N):
-        fx[t], fu[t] = tw.lin(t)
-        lx[t], lu[t], lxx, luu, lux = tw.cost_derivs(t)
-        off = 0
-        for _, c in tw.cons:
-            gx, gu = c.jac(tw.X[t], tw.U[t]); Gx[t, off:off + c.dim] = gx; Gu[t, off:off + c.dim] = gu; off += c.dim
-    H = 2.0 * tw.Qf
-    return dict(fx=fx, fu=fu, lx=lx, lu=lu, lxx=np.tile(lxx, (N, 1, 1)), luu=np.tile(luu, (N, 1, 1)), lux=np.tile(lux, (N, 1, 1)),
-                VxN=2.0 * tw.Qf @ (tw.X[N] - tw.xref), VxxN=H, y=getattr(tw, "Y", np.zeros((N, m))).copy(), s=getattr(tw, "S", np.zeros((N, m))).copy(),
-                g=getattr(tw, "G", np.zeros((N, m))).copy(), Gx=Gx, Gu=Gu)
+from stack_data import twin_stacks as _twin_stacks  # noqa: E402  (shared with tests/test_stack_twin.py)
 
 
 @pytest.mark.parametrize("kind", ["quadratic_scalar_box", "quadratic_scalar_linear", "tilted_unicycle_box_ball"])
@@ -364,14 +350,28 @@ def test_stack_handle_argument_checks(api):
 
 
 # ---- round 6: the terminal-equality branch of the stack-fed sweeps (stacks_te.hpp, CDDP_HIP_STACKS_IPDDP_TERM_EQ) -------------------------------
+# (nx, nu, pT, N): the (nx, nu) of pick_te() (stacks_te.hpp), pT up to kPTS = 8, one-step horizons; the nx = 6 shape on its default
+# tile-minor layout and on the plain one.  (pick_te() also lists (2, 2), but no m = 0 handle exists for it -- pick() has no (2, 2, 0) and
+# cddp_hip_stacks_create refuses the shape -- so that kernel cannot be reached.)
+TE_CASES = [(1, 1, 1, 2), (1, 1, 1, 8), (2, 1, 2, 12), (3, 2, 2, 20), (4, 1, 3, 15), (3, 1, 2, 9), (4, 2, 3, 11),
+            (1, 1, 1, 1), (3, 2, 2, 1), (4, 2, 2, 1)]
+TE_CASES = [(s, None) for s in TE_CASES] + [((6, 3, pT, N), layout) for pT in (1, 2, 6, 8) for N in (8, 1) for layout in (None, "plain")]
+TE_IDS = ["shape%d" % i if i < 5 else "nx%d_nu%d_p%d_N%d-%s" % (s + (l or "default",)) for i, (s, l) in enumerate(TE_CASES)]   # (the first
+# five keep the ids they had before the list grew)
+
+
 @pytest.mark.gpu
-@pytest.mark.parametrize("shape", [(1, 1, 1, 2), (1, 1, 1, 8), (2, 1, 2, 12), (3, 2, 2, 20), (4, 1, 3, 15)])
-def test_terminal_equality_stack_sweep_against_the_twin(api, shape):
+@pytest.mark.parametrize("shape,layout", TE_CASES, ids=TE_IDS)
+def test_terminal_equality_stack_sweep_against_the_twin(api, shape, layout, monkeypatch):
     """solveTerminalEqualityLQR (ipddp_solver.cpp:478-639) on host-fed LQ stacks: dense H_T, previous multipliers, cross terms M, indefinite-free
     random models -- gains, value recursion (P, p), multiplier step, linear-policy rollout, max |r + B^T p| and max |k| against the numpy twin's
     restatement (oracle/twin/cddp_twin_te.py), per trajectory."""
     import cddp_twin_te as TE
     nx, nu, pT, N = shape
+    if layout:
+        monkeypatch.setenv("CDDP_HIP_STACKS_LAYOUT", layout)
+    else:
+        monkeypatch.delenv("CDDP_HIP_STACKS_LAYOUT", raising=False)
     B = 5
     rng = np.random.default_rng(nx * 100 + nu * 10 + pT)
     A = np.tile(np.eye(nx), (B, N, 1, 1)) + 0.1 * rng.standard_normal((B, N, nx, nx)); Bm = 0.3 * rng.standard_normal((B, N, nx, nu))
@@ -406,3 +406,18 @@ def test_terminal_equality_stack_sweep_against_the_twin(api, shape):
         assert np.max(np.abs(dX[b] - np.stack(dXt))) < tol(np.stack(dXt))
         inf_du = max(float(np.max(np.abs(r[b, t] + Bm[b, t].T @ pt[t + 1]))) for t in range(N))
         assert abs(sc["inf_du"][b] - inf_du) < 1e-9 * max(1.0, inf_du) and abs(sc["step_norm"][b] - max(float(np.max(np.abs(v))) for v in kt)) < 1e-9 * max(1.0, float(np.max(np.abs(np.stack(kt)))))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("nx,nu", [(3, 2), (4, 1)])
+def test_terminal_equality_refuses_tile_minor_small_shapes(api, nx, nu, monkeypatch):
+    """The terminal-equality kernels of nx < 6 read [t][e][batch] stacks only: a handle forced tile-minor (possible for the shapes with a
+    cooperative sweep; the others ignore the request and stay plain) is refused, not swept wrong."""
+    monkeypatch.setenv("CDDP_HIP_STACKS_LAYOUT", "t4")
+    B, N = 3, 4
+    hs = api.HipStackSolver(B, nx, nu, 0, N)
+    try:
+        with pytest.raises(api.HipError, match="tile-minor"):
+            hs.set_terminal_equality(np.ones((B, 1, nx)), np.zeros((B, 1)), np.zeros((B, 1)), 1e-8)
+    finally:
+        hs.close()

@@ -2,8 +2,9 @@
 (stacks.hip::sweep) on the same uploaded stacks: every output BITWISE equal, for every branch the boundary offers
 (clddp_solver.cpp:79-204 with and without the control box, ipddp_solver.cpp:1048-1118 and 1355-1568, logddp_solver.cpp:470-575,
 msipddp_solver.cpp:1112-1208), with and without the dynamics Hessian stacks, and through the "increase the regularisation and
-retry" loop (cddp_solver_base.cpp:93-111).  The one-lane form itself is held to the oracle / twins by tests/test_stack_fed*.py and
-tests/test_logddp_stack_fed.py; (12, 4, 8) additionally replays one quadrotor-shaped sweep of the solver core."""
+retry" loop (cddp_solver_base.cpp:93-111).  Bitwise equality cannot see what the two forms share (an index or a transposition of the
+upload); every shape and form is held to the stack-level numpy reference by tests/test_stack_fed_shapes.py, the small shapes also to the
+oracle / twins by tests/test_stack_fed.py, tests/test_logddp_stack_fed.py and tests/test_msipddp.py."""
 import os
 
 import numpy as np
