@@ -21,10 +21,6 @@
 #include <type_traits>
 #include <utility>
 
-#ifndef CDDP_DX_PREFETCH_DEEP
-#define CDDP_DX_PREFETCH_DEEP 1
-#endif
-
 namespace cddp_dev {
 
 #define GI(t, E, e) (((((size_t)(t)) * (size_t)d.NB + (size_t)(b >> 6)) * (E) + (e)) * 64 + (size_t)(b & 63))
@@ -752,11 +748,7 @@ __global__ __launch_bounds__(64 * (1 + NH)) void k_backward_ipddp_coop(DevBuf d,
       // (D - 1 steps of rows in flight: at most ~56 loads, the vmcnt counter holds 63; the main loop has NO branch around a load --
       //  the waitcnt pass merges the states at every join and would otherwise wait for all but the newest step's rows)
       constexpr int kRows = (int)(sizeof(RIn) / sizeof(double));
-#ifdef CDDP_ROLES_D
-      constexpr int D = CDDP_ROLES_D;
-#else
       constexpr int D = kRows > 28 ? 2 : (1 + 56 / kRows > 8 ? 8 : 1 + 56 / kRows);
-#endif
       auto dstep = [&](const int t, const RIn &rc, RIn &rl, const bool fetch) {
         if (fetch) { load_r(clampt(t + D - 1), rl); PIPELINE_FENCE(); }
         lds_sync();                                                    // dx_t went into the ring one step ago
@@ -879,7 +871,7 @@ __global__ __launch_bounds__(64 * (1 + NH)) void k_backward_ipddp_coop(DevBuf d,
       lds_sync();
       // (round 5) the rows of step t + 3 are requested while step t runs: a step is ~150 cycles of dependent arithmetic, a fetch one
       // memory round trip -- with the rows of step t + 1 requested at the top of step t, every step waited for its own round trip
-      constexpr bool kDeep = CDDP_DX_PREFETCH_DEEP && sizeof(RIn) <= 24 * sizeof(double);
+      constexpr bool kDeep = sizeof(RIn) <= 24 * sizeof(double);
       if constexpr (kDeep) {
         auto dstep = [&](const int t, const RIn &rc, RIn &rl) {
           if (t >= N) return;
@@ -1103,10 +1095,7 @@ __global__ __launch_bounds__(64) void k_backward_coop_plain(DevBuf d, const Prob
       // (a data-dependent loop of dependent divisions / square roots, replicated by the lanes of the group) run BEFORE the sixteen
       // T1 entries are fetched from LDS and Q_xx / Q_ux are formed: nothing of those is live across the loop, which is what had the
       // round-3 kernel at 256 VGPR + 124 AGPR with ~250 accvgpr moves per step.  Pure reordering of independent statements.
-#ifndef CDDP_EARLYQP
-#define CDDP_EARLYQP 1
-#endif
-      constexpr bool kEarlyQP = CLDDP && !LOGDDP && NU == 1 && !kQuad && CDDP_EARLYQP;
+      constexpr bool kEarlyQP = CLDDP && !LOGDDP && NU == 1 && !kQuad;
       double T1[NX * NX], T2[NU * NX];
       double Qxxc[NX], Quxc[NU], Quu[NU * NU];
       double kk[NU], KKc[NU];
@@ -1915,9 +1904,6 @@ __global__ __launch_bounds__(64) void k_backward_ipddp_coop_big(DevBuf d, const 
 template <int K> DEV double row_bcast(double v) { return __builtin_amdgcn_update_dpp(0.0, v, 0x150 + K, 0xf, 0xf, true); }
 template <class F, int... Is> DEV void static_for_impl(F &&f, std::integer_sequence<int, Is...>) { (f(std::integral_constant<int, Is>{}), ...); }
 template <int N, class F> DEV void static_for(F &&f) { static_for_impl(f, std::make_integer_sequence<int, N>{}); }
-#ifndef BIG2_EXP
-#define BIG2_EXP 0   // timing experiments only (profiles/r05_big2_roles.md): the product is 0
-#endif
 template <class Model, class Cons>
 struct CoopBig2Cfg {
   static constexpr int NX = Model::NX, NU = Model::NU, G = CoopCfg<Model>::G, TPW = 64 / G, G2 = 2 * G;
@@ -1929,13 +1915,10 @@ struct CoopBig2Cfg {
                        oQux = oKK + NU * NX, oKtQ = oQux + NU * NX, oVx = oKtQ + NX * NU, oDx = oVx + NX,
                        oC = oDx + NX, oQuu = oC + 2 * RC, oFlag = oQuu + NE, oKv = oFlag + 1, RAW = oKv + NU;
   static constexpr int STRIDE = (RAW + 31) / 32 * 32 + 4;
-#ifndef CDDP_BIG2_R0
-#define CDDP_BIG2_R0 ((NX * 3 + 3) / 4)
-#endif
-  static constexpr int R0 = CDDP_BIG2_R0;                                              // value-update rows of the A side (it has the slack)
+  static constexpr int R0 = (NX * 3 + 3) / 4;                                         // value-update rows of the A side (it has the slack)
 };
 
-DEV void wg_sync() { if (BIG2_EXP == 6) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); else asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+DEV void wg_sync() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 template <class Model, class Cons>
 __global__ __launch_bounds__(128) void k_backward_ipddp_coop_big2(DevBuf d, const ProblemDev *__restrict__ Pk, const double *__restrict__ xrt,
@@ -1957,10 +1940,6 @@ __global__ __launch_bounds__(128) void k_backward_ipddp_coop_big2(DevBuf d, cons
   }
   const int q = lane % G, tl = lane / G;
   const int qc = q < NX ? q : NX - 1;          // owned column (lanes past nx shadow the last one)
-  unsigned long long tk_acc[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, tk_last = 0;
-  auto tick = [&](const int k) {
-    if (BIG2_EXP == 9) { __builtin_amdgcn_sched_barrier(0); const unsigned long long now = __builtin_readcyclecounter(); tk_acc[k] += now - tk_last; tk_last = now; __builtin_amdgcn_sched_barrier(0); }
-  };
   const int q2 = q + G * w;                    // slice index of the cooperative fetches
   const int b_raw = coop_group<C::TPW>((int)blockIdx.x, d.xcd_map) * C::TPW + tl;
   const int b = b_raw < d.B ? b_raw : d.B - 1; // (addresses only; a trajectory past the end never sweeps)
@@ -2031,7 +2010,7 @@ __global__ __launch_bounds__(128) void k_backward_ipddp_coop_big2(DevBuf d, cons
 #pragma unroll
         for (int i = 0; i < NX; ++i) pv[(size_t)i * NX * 64] = Vc[i];
       }
-      if (pg_ok && !(BIG2_EXP == 9 && pt_g < 10)) {
+      if (pg_ok) {
         const size_t tb = (size_t)pt_g * tstr;
         if (q < NU) d.k[tb * NU + offk] = pkq;
         double *pKp = d.K + tb * (NU * NX) + offK;
@@ -2045,7 +2024,6 @@ __global__ __launch_bounds__(128) void k_backward_ipddp_coop_big2(DevBuf d, cons
       }
       pv_ok = false; pg_ok = false;
     };
-    if (BIG2_EXP == 9) tk_last = __builtin_readcyclecounter();
     while (__builtin_amdgcn_ballot_w64(act) != 0) {
       const bool isN = t >= N;
       const int ts = isN ? N - 1 : t, tp = isN ? N - 1 : (t > 0 ? t - 1 : 0);
@@ -2057,7 +2035,6 @@ __global__ __launch_bounds__(128) void k_backward_ipddp_coop_big2(DevBuf d, cons
       double Aq[NX], lq[NX];
 #pragma unroll
       for (int j = 0; j < NX; ++j) { Aq[j] = La[j * NX + qc]; lq[j] = ldsQ[j * NX + qc]; }
-      tick(0);
       // round 1: T1[i, qc] = sum_k A[k, i] V[k, qc]
       double T1[NX];
       static_for<NX>([&](auto I) {
@@ -2067,7 +2044,6 @@ __global__ __launch_bounds__(128) void k_backward_ipddp_coop_big2(DevBuf d, cons
         for (int k = 0; k < NX; ++k) s += row_bcast<i>(Aq[k]) * Vc[k];
         T1[i] = s;
       });
-      tick(1);
       // round 2: Q_xx[i, qc] = 2 Q dt [i, qc] + sum_j T1[i, j] A[j, qc]
       double Qxx[NX];
 #pragma unroll
@@ -2079,9 +2055,7 @@ __global__ __launch_bounds__(128) void k_backward_ipddp_coop_big2(DevBuf d, cons
 #pragma unroll
       for (int i = R0; i < NX; ++i) Mb[i * NX + qc] = Qxx[i];          // the gain side's rows of the value update
       flush();                                                          // the previous step's stores
-      tick(2);
       wg_sync();                                                        // ---- barrier 1: K, Q_ux, K^T Q_uu, the verdict
-      tick(3);
       // rows [0, R0) of Vn[i, qc] = ((Q_xx[i, qc] + K[:, i] . Q_ux[:, qc]) + Q_ux[:, i] . K[:, qc]) + (K^T Q_uu)[i, :] . K[:, qc]
       double Quxq[NU], KKc[NU], KtQq[NU];
       const int verdict = (int)Ls[C::oFlag];                            // 0 step done, 1 restart the pass, 2 give up
@@ -2103,12 +2077,8 @@ __global__ __launch_bounds__(128) void k_backward_ipddp_coop_big2(DevBuf d, cons
       }
 #pragma unroll
       for (int i = 0; i < R0; ++i) Mb[i * NX + qc] = Vn[i];
-      tick(4);
       storeAB(tp & 1, nab);
-      if (BIG2_EXP == 9) lds_sync();
-      tick(5);
       wg_sync();                                                        // ---- barrier 2: Vn, V_x
-      tick(6);
       {
         double mr[NX], mc[NX];
 #pragma unroll
@@ -2135,16 +2105,11 @@ __global__ __launch_bounds__(128) void k_backward_ipddp_coop_big2(DevBuf d, cons
         else if (t == 0) act = false;
         else t = t - 1;
       }
-      tick(7);
     }
     flush();
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
     wg_sync();                                                          // the rollout epilogue of the gain side re-reads K, k
-    if (BIG2_EXP == 9 && q == 0 && was_act) {
-#pragma unroll
-      for (int j = 0; j < 10; ++j) d.k[GI(j, NU, 1)] = (double)tk_acc[j];
-    }
     return;
   }
   // -------------------------------------------------------------------------------------------------- the gain side
@@ -2159,7 +2124,6 @@ __global__ __launch_bounds__(128) void k_backward_ipddp_coop_big2(DevBuf d, cons
     double Vc[NX], Vx[NX];
 #pragma unroll
     for (int i = 0; i < NX; ++i) { Vc[i] = 0.0; Vx[i] = 0.0; }
-    if (BIG2_EXP == 9) tk_last = __builtin_readcyclecounter();
     while (__builtin_amdgcn_ballot_w64(act) != 0) {
       const bool isN = t >= N;
       const int ts = isN ? N - 1 : t, tp = isN ? N - 1 : (t > 0 ? t - 1 : 0);
@@ -2178,7 +2142,6 @@ __global__ __launch_bounds__(128) void k_backward_ipddp_coop_big2(DevBuf d, cons
 #pragma unroll
       for (int e = 0; e < RC; ++e) Lcr[e] = Lc[e];
       __builtin_amdgcn_sched_barrier(0);
-      tick(0);
       // ---- round 1: T2[u, qc] = sum_k B[k, u] V[k, qc], Q_x[qc]
       double T2[NU];
 #pragma unroll
@@ -2193,7 +2156,6 @@ __global__ __launch_bounds__(128) void k_backward_ipddp_coop_big2(DevBuf d, cons
 #pragma unroll
         for (int k = 0; k < NX; ++k) s2 += Aq[k] * Vx[k];
         Qxq = cxq + s2; }
-      tick(1);
       // ---- round 2: Q_ux[:, qc] = T2 A[:, qc]; Q_uu = 2 R dt + T2 B and Q_u = c_u + B^T V_x, one entry (or a few) per lane, one LDS round
       double Quxq[NU];
 #pragma unroll
@@ -2227,7 +2189,6 @@ __global__ __launch_bounds__(128) void k_backward_ipddp_coop_big2(DevBuf d, cons
         if (e < C::NE) Ls[C::oQuu + e] = addend[jq] + s;
       }
       lds_sync();
-      tick(2);
       double Quu[NU * NU], Qu[NU];
 #pragma unroll
       for (int i = 0; i < NU * NU; ++i) Quu[i] = Ls[C::oQuu + i];
@@ -2286,10 +2247,7 @@ __global__ __launch_bounds__(128) void k_backward_ipddp_coop_big2(DevBuf d, cons
 #pragma unroll
         for (int u = 0; u < NU; ++u) Ls[C::oKv + u] = kk[u];
       }
-      if (BIG2_EXP == 9) lds_sync();
-      tick(3);
       wg_sync();                                                        // ---- barrier 1
-      tick(4);
       constexpr int R1 = NX - R0;
       double qx[R1 > 0 ? R1 : 1];
 #pragma unroll
@@ -2342,13 +2300,8 @@ __global__ __launch_bounds__(128) void k_backward_ipddp_coop_big2(DevBuf d, cons
 #pragma unroll
       for (int il = 0; il < R1; ++il) Mb[(R0 + il) * NX + qc] = Vn[il];
       Ls[C::oVx + qc] = Vxq;
-      if (BIG2_EXP == 9) lds_sync();
-      tick(5);
       storeAB(tp & 1, nab);
-      if (BIG2_EXP == 9) lds_sync();
-      tick(6);
       wg_sync();                                                        // ---- barrier 2
-      tick(7);
       {
         double mr[NX], mc[NX], vxr[NX];
 #pragma unroll
@@ -2360,7 +2313,6 @@ __global__ __launch_bounds__(128) void k_backward_ipddp_coop_big2(DevBuf d, cons
 #pragma unroll
           for (int i = 0; i < NX; ++i) { Vc[i] = 0.5 * (mr[i] + mc[i]); Vx[i] = vxr[i]; }
         }
-        tick(8);
       }
       if (act) {
         if (isN) t = N - 1;
@@ -2369,15 +2321,10 @@ __global__ __launch_bounds__(128) void k_backward_ipddp_coop_big2(DevBuf d, cons
         else if (t == 0) { act = false; ok = true; }
         else t = t - 1;
       }
-      tick(9);
     }
   }
   wg_sync();                                                            // the A side's last stores (K, k of step 0) are out
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-  if (BIG2_EXP == 9 && q == 0 && was_act) {
-#pragma unroll
-    for (int j = 0; j < 10; ++j) d.k[GI(j, NU, 0)] = (double)tk_acc[j];
-  }
   if (!was_act) return;
   bool conv = false;
   if (ok) {
@@ -2385,7 +2332,7 @@ __global__ __launch_bounds__(128) void k_backward_ipddp_coop_big2(DevBuf d, cons
     const double asn = fabs(d.alpha_pr[b]) * step_norm;
     const double sdu_early = scaled_inf_du_v<Model, Cons>(d, b, cur, inf_du);   // computeScaledDualInfeasibility (:931)
     conv = (inf_pr < tol && sdu_early < tol && inf_comp < tol && asn < o.tolerance * 10.0);
-    if ((!conv || force) && BIG2_EXP != 1) {
+    if (!conv || force) {
       // rolloutLinearPolicy, dx0 = 0 (ipddp_solver.cpp:1511-1520): lane qc computes row qc of dx_{t+1}, lane u < nu the control
       // row du[u] = k[u] + K[u, :] dx; dx and du travel by row broadcast, so a step is one short dependent chain with no LDS round
       // trip, and the rows of K, A, B of the next steps (independent of dx) are fetched three steps ahead -- the one-wave kernel

@@ -810,16 +810,11 @@ __global__ __launch_bounds__(64 * (1 + NC)) void k_forward_ipddp_pc(DevBuf d, co
     //  at the top of their own step.)
     constexpr bool kPing = sizeof(StepIn) <= 40 * sizeof(double);
     constexpr bool kEarly = !kPing && sizeof(StepIn) <= 96 * sizeof(double);
-    // Prefetch distance of the ping-pong form, in steps (kDepth + 1 rotating register sets).  Measured at C2 on one box
-    // (profiles/r03_ladder_sweep.md): producer / consumer distance 1 / 1: 22.7 ms of rollout class per solve, 3 / 1: 23.5, 1 / 2: 23.1,
-    // 5 / 3: 25.0 -- one step of look-ahead already covers the loaded memory latency; more sets only cost registers.
-#ifndef CDDP_K4_DEPTH_P
-#define CDDP_K4_DEPTH_P 1
-#endif
-#ifndef CDDP_K4_DEPTH_C
-#define CDDP_K4_DEPTH_C 1
-#endif
-    constexpr int kDepthP = (kPing && sizeof(StepIn) <= 12 * sizeof(double)) ? CDDP_K4_DEPTH_P : 1;
+    // The prefetch distance of the ping-pong form is ONE step (two rotating register sets), here and in the consumer.  Round 3 measured
+    // longer ones at C2 on one box (profiles/r03_ladder_sweep.md): producer / consumer distance 1 / 1: 22.7 ms of rollout class per solve,
+    // 3 / 1: 23.5, 1 / 2: 23.1, 5 / 3: 25.0 -- one step of look-ahead already covered the loaded memory latency; more sets only cost
+    // registers.  (The two-set loops below keep the shape they had with a distance parameter: written out by hand they are the same
+    //  program and another register allocation -- profiles/r08_isa_identity.md.)
     // The largest records (7-joint arm: 126 doubles) are streamed: the old state row and, per control i, the gain row with
     // u_old[i], k[i] -- two chunk buffers; x_old of step t + 1 and its first chunk are fetched behind the integrator (42
     // doubles live there instead of 126).  Same sums.  With the consumer's chunks (below) the kernel fits two wavefronts per SIMD.
@@ -833,7 +828,7 @@ __global__ __launch_bounds__(64 * (1 + NC)) void k_forward_ipddp_pc(DevBuf d, co
     double xo_c[NX];
     auto step = [&](const int t, StepIn &cs, StepIn &nxt) {
       if constexpr (kPing) {
-        const int tn = t + kDepthP < N ? t + kDepthP : N - 1;   // unconditional (clamped) prefetch
+        const int tn = t + 1 < N ? t + 1 : N - 1;   // unconditional (clamped) prefetch
         load_step(tn, nxt);
       }
       PIPELINE_FENCE();
@@ -909,17 +904,17 @@ __global__ __launch_bounds__(64 * (1 + NC)) void k_forward_ipddp_pc(DevBuf d, co
     StepIn ra;
     int t = 0;
     if constexpr (kPing) {
-      StepIn R[kDepthP + 1];   // step t lives in R[t % (kDepthP + 1)]; every index below is a compile-time constant
+      StepIn R[2];   // step t lives in R[t % 2]; every index below is a compile-time constant
 #pragma unroll
-      for (int j = 0; j < kDepthP; ++j) load_step(j < N ? j : N - 1, R[j]);
+      for (int j = 0; j < 1; ++j) load_step(j < N ? j : N - 1, R[j]);
       prime();
-      for (; t + kDepthP < N; t += kDepthP + 1) {
+      for (; t + 1 < N; t += 2) {
 #pragma unroll
-        for (int j = 0; j <= kDepthP; ++j) step(t + j, R[j], R[(j + kDepthP) % (kDepthP + 1)]);
+        for (int j = 0; j <= 1; ++j) step(t + j, R[j], R[(j + 1) % 2]);
         if (__builtin_amdgcn_ballot_w64(alive) == 0ull) { t = N; break; }   // nothing downstream reads the rows any more
       }
 #pragma unroll
-      for (int j = 0; j <= kDepthP; ++j) if (t + j < N) step(t + j, R[j], R[(j + kDepthP) % (kDepthP + 1)]);
+      for (int j = 0; j <= 1; ++j) if (t + j < N) step(t + j, R[j], R[(j + 1) % 2]);
     } else {
       if constexpr (kChunkP) { ld<NX>(Xc + GI(0, NX, 0), kLS, xo_c); load_pchunk(0, 0, pk0); } else load_step(0, ra);
       prime();
@@ -992,7 +987,6 @@ __global__ __launch_bounds__(64 * (1 + NC)) void k_forward_ipddp_pc(DevBuf d, co
   };
   constexpr bool kPing = sizeof(StepIn) <= 40 * sizeof(double);   // see the producer
   constexpr bool kEarly = !kPing && sizeof(StepIn) <= 96 * sizeof(double);
-  constexpr int kDepthC = (kPing && sizeof(StepIn) <= 16 * sizeof(double)) ? CDDP_K4_DEPTH_C : 1;
   // The largest records of control-box layouts (7-joint arm: 169 doubles per lane and step) are streamed in NU chunks
   // instead: chunk i = gain row i and the slack / dual entries of the two constraint rows that read it (upper and lower
   // bound of control i), two chunk buffers, chunk i + 1 in flight while chunk i is reduced, chunk 0 of the next step behind
@@ -1011,12 +1005,12 @@ __global__ __launch_bounds__(64 * (1 + NC)) void k_forward_ipddp_pc(DevBuf d, co
   Chunk ck0, ck1;
   auto step = [&](const int t, StepIn &cs, StepIn &nxt) {
     if constexpr (kPing) {
-      const int tn = t + NC * kDepthC < N ? t + NC * kDepthC : N - 1;   // unconditional (clamped) prefetch: this consumer's next step
+      const int tn = t + NC < N ? t + NC : N - 1;   // unconditional (clamped) prefetch: this consumer's next step
       load_step(tn, nxt);
     } else if constexpr (!kEarly && !kChunk) load_step(t, cs);
     PIPELINE_FENCE();
     // take step t from the ring, then hand the slot back
-    if (!CDDP_RING_LAZY_POLL || seen_prod < t + 1) seen_prod = __builtin_amdgcn_readfirstlane(wait_ge(&s_prod, t + 1));
+    if (seen_prod < t + 1) seen_prod = __builtin_amdgcn_readfirstlane(wait_ge(&s_prod, t + 1));
     double rx[NX], dx[NX], u[NU];
     {
       const double *rs = s_ring + (size_t)(t % kRing) * RW * 64 + lane;
@@ -1142,7 +1136,7 @@ __global__ __launch_bounds__(64 * (1 + NC)) void k_forward_ipddp_pc(DevBuf d, co
   };
   StepIn ra;
   if constexpr (NC > 1) {
-    static_assert(NC == 1 || (kPing && kDepthC == 1), "two consumers: ping-pong records with one step of look-ahead only");
+    static_assert(NC == 1 || kPing, "two consumers: ping-pong records with one step of look-ahead only");
     // consumer ci walks t = ci, ci + NC, ...; two register sets, the record of its NEXT step in flight while the current one is reduced
     StepIn R0, R1;
     load_step(ci < N ? ci : N - 1, R0);
@@ -1182,14 +1176,14 @@ __global__ __launch_bounds__(64 * (1 + NC)) void k_forward_ipddp_pc(DevBuf d, co
       return;
     }
   } else if constexpr (kPing) {
-    StepIn R[kDepthC + 1];   // see the producer
+    StepIn R[2];   // see the producer
 #pragma unroll
-    for (int j = 0; j < kDepthC; ++j) load_step(j < N ? j : N - 1, R[j]);
+    for (int j = 0; j < 1; ++j) load_step(j < N ? j : N - 1, R[j]);
     prime();
     int t = 0;
-    for (; t + kDepthC < N; t += kDepthC + 1) {
+    for (; t + 1 < N; t += 2) {
 #pragma unroll
-      for (int j = 0; j <= kDepthC; ++j) step(t + j, R[j], R[(j + kDepthC) % (kDepthC + 1)]);
+      for (int j = 0; j <= 1; ++j) step(t + j, R[j], R[(j + 1) % 2]);
       if (__builtin_amdgcn_ballot_w64(alive) == 0ull) {   // every trial of the tile has failed: release the producer
         __hip_atomic_store(s_cons, kAbort, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         if (active) d.t_steps[ti] = fail_t;
@@ -1198,7 +1192,7 @@ __global__ __launch_bounds__(64 * (1 + NC)) void k_forward_ipddp_pc(DevBuf d, co
       }
     }
 #pragma unroll
-    for (int j = 0; j <= kDepthC; ++j) if (t + j < N) step(t + j, R[j], R[(j + kDepthC) % (kDepthC + 1)]);
+    for (int j = 0; j <= 1; ++j) if (t + j < N) step(t + j, R[j], R[(j + 1) % 2]);
   } else {
     if constexpr (kChunk) load_chunk(0, 0, ck0); else load_step(0, ra);
     prime();

@@ -635,7 +635,7 @@ __global__ __launch_bounds__(128) void k_forward_logddp_pc(DevBuf d, const Probl
     for (int s = 0; s < NSEG; ++s) evn[GI(0, NS, s)] = 0.0;
   }
   for (int t = 0; t < N; ++t) {
-    if (!CDDP_RING_LAZY_POLL || seen_prod < t + 1) seen_prod = __builtin_amdgcn_readfirstlane(wait_ge(&s_prod, t + 1));
+    if (seen_prod < t + 1) seen_prod = __builtin_amdgcn_readfirstlane(wait_ge(&s_prod, t + 1));
     double x[NX], u[NU];
     {
       const double *rs = s_ring + (size_t)(t % kRing) * RW * 64 + lane;

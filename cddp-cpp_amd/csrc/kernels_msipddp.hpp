@@ -428,10 +428,7 @@ __global__ __launch_bounds__(64) void k_backward_msipddp(DevBuf d, const Problem
         ld<M>(d.G + (size_t)cur * d.planeM + GI(tt, M, 0), kLS, r.g);
       }
     };
-#ifndef CDDP_MS_SWEEP_PF
-#define CDDP_MS_SWEEP_PF 1
-#endif
-    constexpr bool kPF = CDDP_MS_SWEEP_PF && sizeof(Rec) <= 56 * sizeof(double);
+    constexpr bool kPF = sizeof(Rec) <= 56 * sizeof(double);
     auto step = [&](const int t, const Rec &c, Rec &n) -> bool {
       if constexpr (kPF) { fetch(t > 0 ? t - 1 : 0, n); PIPELINE_FENCE(); }
       const double (&A)[NX * NX] = c.A; const double (&Bm)[NX * NU] = c.Bm; const double (&x)[NX] = c.x; const double (&u)[NU] = c.u;
@@ -1634,7 +1631,7 @@ __global__ __launch_bounds__(128) void k_forward_msipddp_pc(DevBuf d, const Prob
   constexpr bool kPingC = sizeof(CRec) <= 40 * sizeof(double);
   auto step = [&](const int t, CRec &c, CRec &n) {
     if constexpr (kPingC) { fetch(t + 1 < N ? t + 1 : N - 1, n); PIPELINE_FENCE(); }
-    if (!CDDP_RING_LAZY_POLL || seen_prod < t + 1) seen_prod = __builtin_amdgcn_readfirstlane(wait_ge(&s_prod, t + 1));
+    if (seen_prod < t + 1) seen_prod = __builtin_amdgcn_readfirstlane(wait_ge(&s_prod, t + 1));
     double x[NX], dx[NX], u[NU], n1_prev;
     {
       const double *rs = s_ring + (size_t)(t % kRing) * RW * 64 + lane;

@@ -28,19 +28,11 @@ namespace cddp_dev {
 
 #define GI(t, E, e) (((((size_t)(t)) * (size_t)d.NB + (size_t)(b >> 6)) * (E) + (e)) * 64 + (size_t)(b & 63))
 
+// recombination rows (P4 of k_backward_te_coop) fetched this many trips ahead; round 5 held it and the lane-shared reduced terminal
+// system (P3) bitwise to one row per trip and the one-lane system (profiles/r05_big2_roles.md)
+constexpr int kTeP4Unr = 4;
 // NGRP groups of LDS operands, group g + 1 fetched (ldg) before group g is reduced (cmp), a scheduling barrier in between: left to
 // itself the compiler issues one ds_read, waits for it and multiplies -- one LDS round trip per operand (profiles/r05_big2_roles.md)
-#ifndef CDDP_TE_STAGED
-#define CDDP_TE_STAGED 1
-#endif
-// reduced terminal system on the lanes of the group (TeCfg::kP3Par) / recombination rows fetched four trips ahead; 0: the one-lane
-// system and one row per trip (the forms these are held bitwise to)
-#ifndef CDDP_TE_P3PAR
-#define CDDP_TE_P3PAR 1
-#endif
-#ifndef CDDP_TE_P4UNR
-#define CDDP_TE_P4UNR 4
-#endif
 template <int NGRP, int BN, class LD, class CMP> DEV void lds_pipe(LD &&ldg, CMP &&cmp) {
   double b0[BN], b1[BN];
   ldg(0, b0);
@@ -180,50 +172,7 @@ __global__ __launch_bounds__(64) void k_te_condense(DevBuf d, const ProblemDev *
 
 // ---------------------------------------------------------------------------------------------
 // Reduced-system helpers on memory operands (LDS): the steps of LDLTd<NMAX>::compute / solve and of
-// singular_minmax (kernels.hpp) with an explicit leading dimension; run-time size n.
-DEV bool ldlt_mem_compute(double *m, double *trd, double *temp, int n, int ld) {
-  if (n <= 1) { if (n == 1) trd[0] = 0.0; return true; }
-  bool found_zero_pivot = false, ret = true;
-  for (int k = 0; k < n; ++k) {
-    int big = k;
-    double bigv = fabs(m[k * ld + k]);
-    for (int i = k + 1; i < n; ++i) { const double v = fabs(m[i * ld + i]); if (v > bigv) { bigv = v; big = i; } }
-    trd[k] = (double)big;
-    if (k != big) {
-      const int s = n - big - 1;
-      for (int j = 0; j < k; ++j) { const double t = m[k * ld + j]; m[k * ld + j] = m[big * ld + j]; m[big * ld + j] = t; }
-      for (int i = 0; i < s; ++i) { const double t = m[(big + 1 + i) * ld + k]; m[(big + 1 + i) * ld + k] = m[(big + 1 + i) * ld + big]; m[(big + 1 + i) * ld + big] = t; }
-      { const double t = m[k * ld + k]; m[k * ld + k] = m[big * ld + big]; m[big * ld + big] = t; }
-      for (int i = k + 1; i < big; ++i) { const double t = m[i * ld + k]; m[i * ld + k] = m[big * ld + i]; m[big * ld + i] = t; }
-    }
-    const int rs = n - k - 1;
-    if (k > 0) {
-      for (int j = 0; j < k; ++j) temp[j] = m[j * ld + j] * m[k * ld + j];
-      double s = 0.0;
-      for (int j = 0; j < k; ++j) s += m[k * ld + j] * temp[j];
-      m[k * ld + k] -= s;
-      for (int i = 0; i < rs; ++i) {
-        double t = 0.0;
-        for (int j = 0; j < k; ++j) t += m[(k + 1 + i) * ld + j] * temp[j];
-        m[(k + 1 + i) * ld + k] -= t;
-      }
-    }
-    const double akk = m[k * ld + k];
-    const bool valid = fabs(akk) > 0.0;
-    if (k == 0 && !valid) {
-      for (int j = 0; j < n; ++j) {
-        trd[j] = (double)j;
-        for (int i = j + 1; i < n; ++i) ret = ret && (m[i * ld + j] == 0.0);
-      }
-      return ret;
-    }
-    if (rs > 0 && valid) { for (int i = 0; i < rs; ++i) m[(k + 1 + i) * ld + k] /= akk; }
-    else if (rs > 0) { for (int i = 0; i < rs; ++i) ret = ret && (m[(k + 1 + i) * ld + k] == 0.0); }
-    if (found_zero_pivot && valid) ret = false;
-    else if (!valid) found_zero_pivot = true;
-  }
-  return ret;
-}
+// singular_minmax (kernels.hpp) with an explicit leading dimension; run-time size n.  (compute: ldlt_mem_compute_coop below)
 DEV void ldlt_mem_solve(const double *m, const double *trd, int n, int ld, double *x) {
   for (int k = 0; k < n; ++k) { const int t = (int)trd[k]; if (t != k) { const double v = x[k]; x[k] = x[t]; x[t] = v; } }
   for (int i = 0; i < n; ++i) { double s = x[i]; for (int kk = 0; kk < i; ++kk) s -= m[i * ld + kk] * x[kk]; x[i] = s; }
@@ -231,7 +180,7 @@ DEV void ldlt_mem_solve(const double *m, const double *trd, int n, int ld, doubl
   for (int i = n - 1; i >= 0; --i) { double s = x[i]; for (int kk = i + 1; kk < n; ++kk) s -= m[kk * ld + i] * x[kk]; x[i] = s; }
   for (int k = n - 1; k >= 0; --k) { const int t = (int)trd[k]; if (t != k) { const double v = x[k]; x[k] = x[t]; x[t] = v; } }
 }
-// ldlt_mem_compute on the G lanes of a trajectory (lane q; gmask = the group's lanes): the pivot search reads the diagonal in one
+// LDLTd<NMAX>::compute on the G lanes of a trajectory (lane q; gmask = the group's lanes): the pivot search reads the diagonal in one
 // batch and compares in the one-lane order; the elements of a transposition, the entries of temp and the rows below the pivot
 // (their update sum and their division) are spread over the lanes; m_kk - s is formed by every lane (each needs the pivot).  Every
 // entry goes through the operations of the one-lane loop in the same order: same bits.  The return value is the same on every lane.
@@ -413,8 +362,11 @@ __global__ __launch_bounds__(64) void k_backward_te_coop(DevBuf d, const Problem
 #pragma unroll
     for (int j = 0; j < C::NC; ++j) { const int e = q + G * j; if (e < REC) Lc[e] = r.c[j]; }
   };
+  // The one compile-time experiment left in the kernel headers.  9: phase timers (profiles/r05_big2_roles.md section 6, read by
+  // profiles/scripts/te_phase_timers.py); the product is 0.  With 0 every tick() is an empty call, and yet taking the sixteen calls out
+  // gave this kernel another register allocation (profiles/r08_isa_identity.md), so they stay until a change that may move its code.
 #ifndef TE_EXP
-#define TE_EXP 0   // 9: phase timers (profiles/r05_big2_roles.md); the product is 0
+#define TE_EXP 0
 #endif
   unsigned long long tk_acc[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, tk_last = 0;
   auto tick = [&](const int k) {
@@ -506,21 +458,13 @@ __global__ __launch_bounds__(64) void k_backward_te_coop(DevBuf d, const Problem
           __builtin_amdgcn_sched_barrier(0);
         }
       }
-      if constexpr (CDDP_TE_STAGED) {
-        lds_pipe<NU, NX>([&](const int u, auto &buf) {
+      lds_pipe<NU, NX>([&](const int u, auto &buf) {
 #pragma unroll
-          for (int k = 0; k < NX; ++k) buf[k] = Lb[k * NU + u];
-        }, [&](const int u, const auto &buf) { double s = 0.0;
+        for (int k = 0; k < NX; ++k) buf[k] = Lb[k * NU + u];
+      }, [&](const int u, const auto &buf) { double s = 0.0;
 #pragma unroll
-          for (int k = 0; k < NX; ++k) s += buf[k] * Vc[k];
-          Ls[C::oT2 + u * NX + qc] = s; });
-      } else {
-#pragma unroll
-      for (int u = 0; u < NU; ++u) { double s = 0.0;
-#pragma unroll
-        for (int k = 0; k < NX; ++k) s += Lb[k * NU + u] * Vc[k];
-        Ls[C::oT2 + u * NX + qc] = s; }
-      }
+        for (int k = 0; k < NX; ++k) s += buf[k] * Vc[k];
+        Ls[C::oT2 + u * NX + qc] = s; });
       lds_sync();
       tick(8);
       // round 2a: Q + A^T P A (in place over T1, row by row), Q_ux column; the entries of Q_uu spread over the lanes
@@ -553,53 +497,32 @@ __global__ __launch_bounds__(64) void k_backward_te_coop(DevBuf d, const Problem
         }
       }
       double Quxq[NU];
-      if constexpr (CDDP_TE_STAGED) {
-        lds_pipe<NU, NX>([&](const int u, auto &buf) {
+      lds_pipe<NU, NX>([&](const int u, auto &buf) {
 #pragma unroll
-          for (int j = 0; j < NX; ++j) buf[j] = Ls[C::oT2 + u * NX + j];
-        }, [&](const int u, const auto &buf) { double s = 0.0;
+        for (int j = 0; j < NX; ++j) buf[j] = Ls[C::oT2 + u * NX + j];
+      }, [&](const int u, const auto &buf) { double s = 0.0;
 #pragma unroll
-          for (int j = 0; j < NX; ++j) s += buf[j] * Aq[j];
-          Quxq[u] = s + 0.0;            // + M^T, M = 0 without G_x
-          Ls[C::oQux + u * NX + qc] = Quxq[u]; });
-        lds_pipe<C::NQ, 2 * NX + 2>([&](const int j, auto &buf) {
-          const int e = q + G * j;
-          const int ee = e < NU * NU ? e : NU * NU - 1;
-          const int u = ee / NU, w = ee - u * NU;
-#pragma unroll
-          for (int k = 0; k < NX; ++k) { buf[k] = Ls[C::oT2 + u * NX + k]; buf[NX + k] = Lb[k * NU + w]; }
-          buf[2 * NX] = Lc[C::cRR + u * NU + w]; buf[2 * NX + 1] = Lc[C::cRR + w * NU + u];
-        }, [&](const int j, const auto &buf) {
-          const int e = q + G * j;
-          const int ee = e < NU * NU ? e : NU * NU - 1;
-          const int u = ee / NU, w = ee - u * NU;
-          double s = 0.0;               // (B^T P) B; (B^T P^T) B is the same number: P is exactly symmetric
-#pragma unroll
-          for (int k = 0; k < NX; ++k) s += buf[k] * buf[NX + k];
-          double ruw = buf[2 * NX], rwu = buf[2 * NX + 1];
-          if (u == w) { ruw += reg; rwu += reg; }
-          if (e < NU * NU) Ls[C::oQuu + e] = 0.5 * (((ruw + s) + rwu) + s);
-        });
-      } else {
-#pragma unroll
-      for (int u = 0; u < NU; ++u) { double s = 0.0;
-#pragma unroll
-        for (int j = 0; j < NX; ++j) s += Ls[C::oT2 + u * NX + j] * Aq[j];
+        for (int j = 0; j < NX; ++j) s += buf[j] * Aq[j];
         Quxq[u] = s + 0.0;            // + M^T, M = 0 without G_x
-        Ls[C::oQux + u * NX + qc] = Quxq[u]; }
+        Ls[C::oQux + u * NX + qc] = Quxq[u]; });
+      lds_pipe<C::NQ, 2 * NX + 2>([&](const int j, auto &buf) {
+        const int e = q + G * j;
+        const int ee = e < NU * NU ? e : NU * NU - 1;
+        const int u = ee / NU, w = ee - u * NU;
 #pragma unroll
-      for (int j = 0; j < C::NQ; ++j) {
+        for (int k = 0; k < NX; ++k) { buf[k] = Ls[C::oT2 + u * NX + k]; buf[NX + k] = Lb[k * NU + w]; }
+        buf[2 * NX] = Lc[C::cRR + u * NU + w]; buf[2 * NX + 1] = Lc[C::cRR + w * NU + u];
+      }, [&](const int j, const auto &buf) {
         const int e = q + G * j;
         const int ee = e < NU * NU ? e : NU * NU - 1;
         const int u = ee / NU, w = ee - u * NU;
         double s = 0.0;               // (B^T P) B; (B^T P^T) B is the same number: P is exactly symmetric
 #pragma unroll
-        for (int k = 0; k < NX; ++k) s += Ls[C::oT2 + u * NX + k] * Lb[k * NU + w];
-        double ruw = Lc[C::cRR + u * NU + w], rwu = Lc[C::cRR + w * NU + u];
+        for (int k = 0; k < NX; ++k) s += buf[k] * buf[NX + k];
+        double ruw = buf[2 * NX], rwu = buf[2 * NX + 1];
         if (u == w) { ruw += reg; rwu += reg; }
         if (e < NU * NU) Ls[C::oQuu + e] = 0.5 * (((ruw + s) + rwu) + s);
-      }
-      }
+      });
       lds_sync();
       tick(9);
       // round 2b: factor (replicated; lane 0 parks it in LDS for the variant solves), K column, row of K^T Q_uu
@@ -630,21 +553,13 @@ __global__ __launch_bounds__(64) void k_backward_te_coop(DevBuf d, const Problem
       }
 #pragma unroll
       for (int i = 0; i < NU; ++i) bad = bad || !dfinite(KKc[i]);
-      if constexpr (CDDP_TE_STAGED) {
-        lds_pipe<NU, NU>([&](const int j, auto &buf) {
+      lds_pipe<NU, NU>([&](const int j, auto &buf) {
 #pragma unroll
-          for (int u = 0; u < NU; ++u) buf[u] = Ls[C::oQuu + u * NU + j];
-        }, [&](const int j, const auto &buf) { double s = 0.0;     // row qc of K^T Q_uu
+        for (int u = 0; u < NU; ++u) buf[u] = Ls[C::oQuu + u * NU + j];
+      }, [&](const int j, const auto &buf) { double s = 0.0;     // row qc of K^T Q_uu
 #pragma unroll
-          for (int u = 0; u < NU; ++u) s += KKc[u] * buf[u];
-          Ls[C::oKtQ + qc * NU + j] = s; });
-      } else {
-#pragma unroll
-      for (int j = 0; j < NU; ++j) { double s = 0.0;     // row qc of K^T Q_uu
-#pragma unroll
-        for (int u = 0; u < NU; ++u) s += KKc[u] * Ls[C::oQuu + u * NU + j];
-        Ls[C::oKtQ + qc * NU + j] = s; }
-      }
+        for (int u = 0; u < NU; ++u) s += KKc[u] * buf[u];
+        Ls[C::oKtQ + qc * NU + j] = s; });
 #pragma unroll
       for (int u = 0; u < NU; ++u) Ls[C::oKK + u * NX + qc] = KKc[u];
       lds_sync();
@@ -659,22 +574,14 @@ __global__ __launch_bounds__(64) void k_backward_te_coop(DevBuf d, const Problem
         double drift[NX], Qu[NU], kk[NU];
 #pragma unroll
         for (int i = 0; i < NX; ++i) drift[i] = pv[i] + 0.0;     // + P * 0 (no affine dynamics term)
-        if constexpr (CDDP_TE_STAGED) {
-          lds_pipe<NU, NX + 1>([&](const int i, auto &buf) {
+        lds_pipe<NU, NX + 1>([&](const int i, auto &buf) {
 #pragma unroll
-            for (int k = 0; k < NX; ++k) buf[k] = Lb[k * NU + i];
-            buf[NX] = Lc[C::cR + i];
-          }, [&](const int i, const auto &buf) { double a = 0.0;
+          for (int k = 0; k < NX; ++k) buf[k] = Lb[k * NU + i];
+          buf[NX] = Lc[C::cR + i];
+        }, [&](const int i, const auto &buf) { double a = 0.0;
 #pragma unroll
-            for (int k = 0; k < NX; ++k) a += buf[k] * drift[k];
-            Qu[i] = buf[NX] + a; });
-        } else {
-#pragma unroll
-        for (int i = 0; i < NU; ++i) { double a = 0.0;
-#pragma unroll
-          for (int k = 0; k < NX; ++k) a += Lb[k * NU + i] * drift[k];
-          Qu[i] = Lc[C::cR + i] + a; }
-        }
+          for (int k = 0; k < NX; ++k) a += buf[k] * drift[k];
+          Qu[i] = buf[NX] + a; });
         if constexpr (NU == 1) kk[0] = -ldlt1_solve(Ls[C::oQuu], Qu[0]);
         else {
           double col[NU];
@@ -684,36 +591,22 @@ __global__ __launch_bounds__(64) void k_backward_te_coop(DevBuf d, const Problem
 #pragma unroll
           for (int i = 0; i < NU; ++i) kk[i] = -col[i];
         }
-        if constexpr (CDDP_TE_STAGED) {
-          lds_pipe<NX, NX + 3 * NU + 1>([&](const int i, auto &buf) {
+        lds_pipe<NX, NX + 3 * NU + 1>([&](const int i, auto &buf) {
 #pragma unroll
-            for (int k = 0; k < NX; ++k) buf[k] = La[k * NX + i];
+          for (int k = 0; k < NX; ++k) buf[k] = La[k * NX + i];
 #pragma unroll
-            for (int j = 0; j < NU; ++j) { buf[NX + j] = Ls[C::oQux + j * NX + i]; buf[NX + NU + j] = Ls[C::oKK + j * NX + i]; buf[NX + 2 * NU + j] = Ls[C::oKtQ + i * NU + j]; }
-            buf[NX + 3 * NU] = Lc[C::cQ + i];
-          }, [&](const int i, const auto &buf) {
-            double a = 0.0;
-#pragma unroll
-            for (int k = 0; k < NX; ++k) a += buf[k] * drift[k];
-            const double Qx = buf[NX + 3 * NU] + a;
-            double a1 = 0.0, a2 = 0.0, a3 = 0.0;
-#pragma unroll
-            for (int j = 0; j < NU; ++j) { a1 += buf[NX + j] * kk[j]; a2 += buf[NX + NU + j] * Qu[j]; a3 += buf[NX + 2 * NU + j] * kk[j]; }
-            Ls[C::oPv + i * G + q] = ((Qx + a1) + a2) + a3;
-          });
-        } else {
-#pragma unroll 4
-        for (int i = 0; i < NX; ++i) {
+          for (int j = 0; j < NU; ++j) { buf[NX + j] = Ls[C::oQux + j * NX + i]; buf[NX + NU + j] = Ls[C::oKK + j * NX + i]; buf[NX + 2 * NU + j] = Ls[C::oKtQ + i * NU + j]; }
+          buf[NX + 3 * NU] = Lc[C::cQ + i];
+        }, [&](const int i, const auto &buf) {
           double a = 0.0;
 #pragma unroll
-          for (int k = 0; k < NX; ++k) a += La[k * NX + i] * drift[k];
-          const double Qx = Lc[C::cQ + i] + a;
+          for (int k = 0; k < NX; ++k) a += buf[k] * drift[k];
+          const double Qx = buf[NX + 3 * NU] + a;
           double a1 = 0.0, a2 = 0.0, a3 = 0.0;
 #pragma unroll
-          for (int j = 0; j < NU; ++j) { a1 += Ls[C::oQux + j * NX + i] * kk[j]; a2 += Ls[C::oKK + j * NX + i] * Qu[j]; a3 += Ls[C::oKtQ + i * NU + j] * kk[j]; }
+          for (int j = 0; j < NU; ++j) { a1 += buf[NX + j] * kk[j]; a2 += buf[NX + NU + j] * Qu[j]; a3 += buf[NX + 2 * NU + j] * kk[j]; }
           Ls[C::oPv + i * G + q] = ((Qx + a1) + a2) + a3;
-        }
-        }
+        });
         lds_sync();
 #pragma unroll
         for (int i = 0; i < NX; ++i) { pv[i] = Ls[C::oPv + i * G + q]; bad = bad || !dfinite(pv[i]); }
@@ -818,43 +711,26 @@ __global__ __launch_bounds__(64) void k_backward_te_coop(DevBuf d, const Problem
         PIPELINE_FENCE();
         const double *La = Ls + C::rA + (t & 1) * NX * NX, *Lb = Ls + C::rB + (t & 1) * NX * NU, *Lk = Ls + C::rK + (t & 1) * NU * NX;
         double du[NU];
-        if constexpr (CDDP_TE_STAGED) {
-          lds_pipe<NU, NX>([&](const int i, auto &buf) {
+        lds_pipe<NU, NX>([&](const int i, auto &buf) {
 #pragma unroll
-            for (int j = 0; j < NX; ++j) buf[j] = Lk[i * NX + j];
-          }, [&](const int i, const auto &buf) { double a = 0.0;
+          for (int j = 0; j < NX; ++j) buf[j] = Lk[i * NX + j];
+        }, [&](const int i, const auto &buf) { double a = 0.0;
 #pragma unroll
-            for (int j = 0; j < NX; ++j) a += buf[j] * dx[j];
-            du[i] = rc.kf[i] + a; });
-          lds_pipe<NX, NX + NU>([&](const int i, auto &buf) {
+          for (int j = 0; j < NX; ++j) a += buf[j] * dx[j];
+          du[i] = rc.kf[i] + a; });
+        lds_pipe<NX, NX + NU>([&](const int i, auto &buf) {
 #pragma unroll
-            for (int j = 0; j < NX; ++j) buf[j] = La[i * NX + j];
+          for (int j = 0; j < NX; ++j) buf[j] = La[i * NX + j];
 #pragma unroll
-            for (int j = 0; j < NU; ++j) buf[NX + j] = Lb[i * NU + j];
-          }, [&](const int i, const auto &buf) {
-            double a = 0.0, c = 0.0;
-#pragma unroll
-            for (int j = 0; j < NX; ++j) a += buf[j] * dx[j];
-#pragma unroll
-            for (int j = 0; j < NU; ++j) c += buf[NX + j] * du[j];
-            Ls[C::rPv + i * G + q] = (a + c) + 0.0;
-          });
-        } else {
-#pragma unroll
-        for (int i = 0; i < NU; ++i) { double a = 0.0;
-#pragma unroll
-          for (int j = 0; j < NX; ++j) a += Lk[i * NX + j] * dx[j];
-          du[i] = rc.kf[i] + a; }
-#pragma unroll 4
-        for (int i = 0; i < NX; ++i) {
+          for (int j = 0; j < NU; ++j) buf[NX + j] = Lb[i * NU + j];
+        }, [&](const int i, const auto &buf) {
           double a = 0.0, c = 0.0;
 #pragma unroll
-          for (int j = 0; j < NX; ++j) a += La[i * NX + j] * dx[j];
+          for (int j = 0; j < NX; ++j) a += buf[j] * dx[j];
 #pragma unroll
-          for (int j = 0; j < NU; ++j) c += Lb[i * NU + j] * du[j];
+          for (int j = 0; j < NU; ++j) c += buf[NX + j] * du[j];
           Ls[C::rPv + i * G + q] = (a + c) + 0.0;
-        }
-        }
+        });
         store_r((t & 1) ^ 1, rn);
         lds_sync();
 #pragma unroll
@@ -869,11 +745,11 @@ __global__ __launch_bounds__(64) void k_backward_te_coop(DevBuf d, const Problem
       lds_sync();
       tick(2);
       // ---- P3: reduced terminal system (:550-617); operands in LDS (overlaying the sweep area)
-      if constexpr (CDDP_TE_P3PAR != 0) {
+      {
         // (round 5) the lanes of the group share the system: every entry of A_s, A_s^T A_s, A_s^T b, of the shifted matrix and of
         // the residual is its own sequential sum (entries / rows spread over the lanes), the factorisation runs with one lane per
         // row (ldlt_mem_compute_coop); the scales stay in sequence, every accept / skip decision is taken by all lanes on the
-        // same LDS values.  Same work area as the one-lane form below, which it is held bitwise to.
+        // same LDS values.  Held bitwise to the one-lane system of te_backward (profiles/r05_big2_roles.md).
         const int p = pT, ld_ = pT;
         double *As = Ls, *AtA = As + p * p, *Sh = AtA + p * p, *Uw = Sh + p * p, *rhs = Uw + p * p, *Atb = rhs + p,
                *lam = Atb + p, *best = lam + p, *temp = best + p, *trd = temp + p;
@@ -908,7 +784,12 @@ __global__ __launch_bounds__(64) void k_backward_te_coop(DevBuf d, const Problem
         const double trace_term = (tr > 1.0 ? tr / (p > 1 ? p : 1) : 1.0);
         const double base_floor = dmax(1e-10, o.ipddp_jacobian_regularization_value * solver_pow(dmax(mu, 0.0), o.ipddp_jacobian_regularization_exponent));
         const double regv = dmax(base_floor, 1e-6 * trace_term);
-        double svd_reg = 0.0;   // (only a non-finite system runs the Jacobi sweeps: see the one-lane form below)
+        // te_backward adds svd_reg = max(1e-8 smax - smin, 0) of the singular values of A_s (80 Jacobi sweeps) and takes
+        // reg_base = max(regv, svd_reg).  Whenever tr = ||A_s||_F^2 is finite that maximum is regv, whatever the
+        // sweeps return: smax <= ||A_s||_F = sqrt(tr), so svd_reg <= 1e-8 sqrt(tr), while regv >= 1e-6 max(1, tr / p) --
+        // for tr <= 1 that is 1e-8 against 1e-6, for tr > 1 the ratio is <= 1e-2 p / sqrt(tr) <= 0.16 (p <= 16).  The
+        // sweeps therefore only run for a non-finite system, where they reproduce te_backward's NaN / inf handling.
+        double svd_reg = 0.0;
         if (!dfinite(tr)) {
           if (q == 0) {
             double smax, smin;
@@ -953,67 +834,6 @@ __global__ __launch_bounds__(64) void k_backward_te_coop(DevBuf d, const Problem
         lds_sync();
         tick(15);
         for (int i = q; i < p; i += G) { const double bv = found ? best[i] : 0.0; d.dLamT[(size_t)i * Bp + b] = bv; Ls[C::oBest + i] = bv; }
-      } else if (q == 0) {
-        const int p = pT, ld_ = pT;
-        double *As = Ls, *AtA = As + p * p, *Sh = AtA + p * p, *Uw = Sh + p * p, *rhs = Uw + p * p, *Atb = rhs + p,
-               *lam = Atb + p, *best = lam + p, *temp = best + p, *trd = temp + p;
-        const double *xT = Ls + C::oXT;
-        for (int r = 0; r < p; ++r) {
-          const int cr = ldsCol[r];
-          for (int i = 0; i < p; ++i) {
-            double a = 0.0;
-            for (int k = 0; k < NX; ++k) a += ((k == cr) ? 1.0 : 0.0) * (xT[(i + 1) * NX + k] - xT[k]);
-            As[r * ld_ + i] = a;
-          }
-          double hx = 0.0;
-          for (int k = 0; k < NX; ++k) hx += ((k == cr) ? 1.0 : 0.0) * xT[k];
-          rhs[r] = (-Ls[C::oH + r]) - hx;
-        }
-        double tr = 0.0;
-        for (int i = 0; i < p; ++i) {
-          for (int c = 0; c < p; ++c) { double a = 0.0; for (int k = 0; k < p; ++k) a += As[k * ld_ + i] * As[k * ld_ + c]; AtA[i * ld_ + c] = a; }
-          double a = 0.0; for (int k = 0; k < p; ++k) a += As[k * ld_ + i] * rhs[k]; Atb[i] = a;
-        }
-        for (int i = 0; i < p; ++i) tr += AtA[i * ld_ + i];
-        const double trace_term = (tr > 1.0 ? tr / (p > 1 ? p : 1) : 1.0);
-        const double base_floor = dmax(1e-10, o.ipddp_jacobian_regularization_value * solver_pow(dmax(mu, 0.0), o.ipddp_jacobian_regularization_exponent));
-        const double regv = dmax(base_floor, 1e-6 * trace_term);
-        // te_backward adds svd_reg = max(1e-8 smax - smin, 0) of the singular values of A_s (80 Jacobi sweeps) and takes
-        // reg_base = max(regv, svd_reg).  Whenever tr = ||A_s||_F^2 is finite that maximum is regv, whatever the
-        // sweeps return: smax <= ||A_s||_F = sqrt(tr), so svd_reg <= 1e-8 sqrt(tr), while regv >= 1e-6 max(1, tr / p) --
-        // for tr <= 1 that is 1e-8 against 1e-6, for tr > 1 the ratio is <= 1e-2 p / sqrt(tr) <= 0.16 (p <= 16).  The
-        // sweeps therefore only run for a non-finite system, where they reproduce te_backward's NaN / inf handling.
-        double svd_reg = 0.0;
-        if (!dfinite(tr)) {
-          double smax, smin;
-          singular_minmax_mem(Uw, As, p, ld_, smax, smin);
-          svd_reg = dmax(1e-8 * smax - smin, 0.0);
-        }
-        const double reg_base = dmax(regv, svd_reg);
-        double rn2 = 0.0; for (int r = 0; r < p; ++r) rn2 += rhs[r] * rhs[r];
-        const double cap = 100.0 * (1.0 + sqrt(rn2));
-        for (int i = 0; i < p; ++i) best[i] = 0.0;
-        double best_res = INFINITY; bool found = false;
-        for (int sc = 0; sc < 5; ++sc) {
-          const double scale = (sc == 0) ? 1.0 : (sc == 1) ? 10.0 : (sc == 2) ? 100.0 : (sc == 3) ? 1e3 : 1e4;
-          const double reg_i = dmax(reg_base * scale, 1e-12);
-          for (int i = 0; i < p; ++i) for (int c = 0; c < p; ++c) Sh[i * ld_ + c] = AtA[i * ld_ + c] + reg_i * ((i == c) ? 1.0 : 0.0);
-          if (!ldlt_mem_compute(Sh, trd, temp, p, ld_)) continue;
-          for (int i = 0; i < p; ++i) lam[i] = Atb[i];
-          ldlt_mem_solve(Sh, trd, p, ld_, lam);
-          bool fin = true; double ln = 0.0;
-          for (int i = 0; i < p; ++i) { fin = fin && dfinite(lam[i]); ln += lam[i] * lam[i]; }
-          if (!fin) continue;
-          ln = sqrt(ln);
-          if (ln > cap) { const double f2 = cap / dmax(ln, 1e-12); for (int i = 0; i < p; ++i) lam[i] = lam[i] * f2; }
-          double res = 0.0;
-          for (int r = 0; r < p; ++r) { double a = 0.0; for (int i = 0; i < p; ++i) a += As[r * ld_ + i] * lam[i]; const double e = a - rhs[r]; res += e * e; }
-          res = sqrt(res);
-          if (!dfinite(res)) continue;
-          if (!found || res < best_res) { for (int i = 0; i < p; ++i) best[i] = lam[i]; best_res = res; found = true; }
-        }
-        if (!found) for (int i = 0; i < p; ++i) best[i] = 0.0;
-        for (int i = 0; i < p; ++i) { d.dLamT[(size_t)i * Bp + b] = best[i]; Ls[C::oBest + i] = best[i]; }
       }
       lds_sync();
       tick(3);
@@ -1024,77 +844,53 @@ __global__ __launch_bounds__(64) void k_backward_te_coop(DevBuf d, const Problem
 #pragma unroll
         for (int w = 0; w < C::PMAX; ++w) bw[w] = (w < pT) ? Ls[C::oBest + w] : 0.0;
         // one element (t, i) per lane and trip: its VP = 16 variant values are one 128-byte row, fetched whole
-        auto combine = [&](const double *row) {
-          double rv[VP];
-#pragma unroll
-          for (int w = 0; w < VP; ++w) rv[w] = row[w];
+        // the rows of UNR trips leave memory before the first is combined (one row per trip: a memory round trip per trip)
+        constexpr int UNR = kTeP4Unr;
+        auto combine_r = [&](const double (&rv)[VP]) {
           const double k0 = rv[0];
           double ko = k0;
 #pragma unroll
           for (int w = 0; w < C::PMAX; ++w) if (w < pT) ko += bw[w] * (rv[w + 1] - k0);
           return ko;
         };
-        if constexpr (CDDP_TE_P4UNR > 1) {
-          // the rows of UNR trips leave memory before the first is combined (one row per trip: a memory round trip per trip)
-          constexpr int UNR = CDDP_TE_P4UNR;
-          auto combine_r = [&](const double (&rv)[VP]) {
-            const double k0 = rv[0];
-            double ko = k0;
+        const int nk = N * NU, np = (N + 1) * NX;
+        for (int idx0 = q; idx0 < nk; idx0 += G * UNR) {
+          double rv[UNR][VP];
 #pragma unroll
-            for (int w = 0; w < C::PMAX; ++w) if (w < pT) ko += bw[w] * (rv[w + 1] - k0);
-            return ko;
-          };
-          const int nk = N * NU, np = (N + 1) * NX;
-          for (int idx0 = q; idx0 < nk; idx0 += G * UNR) {
-            double rv[UNR][VP];
+          for (int j = 0; j < UNR; ++j) {
+            const int idx = idx0 + G * j < nk ? idx0 + G * j : idx0;
+            const double *row = tek + ((size_t)(idx / NU) * Bp * NU + (size_t)b * NU + (idx % NU)) * VP;
 #pragma unroll
-            for (int j = 0; j < UNR; ++j) {
-              const int idx = idx0 + G * j < nk ? idx0 + G * j : idx0;
-              const double *row = tek + ((size_t)(idx / NU) * Bp * NU + (size_t)b * NU + (idx % NU)) * VP;
+            for (int w = 0; w < VP; ++w) rv[j][w] = row[w];
+          }
+          PIPELINE_FENCE();
 #pragma unroll
-              for (int w = 0; w < VP; ++w) rv[j][w] = row[w];
-            }
-            PIPELINE_FENCE();
-#pragma unroll
-            for (int j = 0; j < UNR; ++j) {
-              const int idx = idx0 + G * j;
-              if (idx < nk) {
-                const int t = idx / NU, i = idx - t * NU;
-                const double ko = combine_r(rv[j]);
-                d.k[GI(t, NU, i)] = ko;
-                if (d.t4) d.Kt[G4(t, NU * NX + NU, NU * NX + i)] = ko;
-                sn = dmax(sn, fabs(ko));
-              }
+          for (int j = 0; j < UNR; ++j) {
+            const int idx = idx0 + G * j;
+            if (idx < nk) {
+              const int t = idx / NU, i = idx - t * NU;
+              const double ko = combine_r(rv[j]);
+              d.k[GI(t, NU, i)] = ko;
+              if (d.t4) d.Kt[G4(t, NU * NX + NU, NU * NX + i)] = ko;
+              sn = dmax(sn, fabs(ko));
             }
           }
-          for (int idx0 = q; idx0 < np; idx0 += G * UNR) {
-            double rv[UNR][VP];
+        }
+        for (int idx0 = q; idx0 < np; idx0 += G * UNR) {
+          double rv[UNR][VP];
 #pragma unroll
-            for (int j = 0; j < UNR; ++j) {
-              const int idx = idx0 + G * j < np ? idx0 + G * j : idx0;
-              const double *row = tep + ((size_t)(idx / NX) * Bp * NX + (size_t)b * NX + (idx % NX)) * VP;
+          for (int j = 0; j < UNR; ++j) {
+            const int idx = idx0 + G * j < np ? idx0 + G * j : idx0;
+            const double *row = tep + ((size_t)(idx / NX) * Bp * NX + (size_t)b * NX + (idx % NX)) * VP;
 #pragma unroll
-              for (int w = 0; w < VP; ++w) rv[j][w] = row[w];
-            }
-            PIPELINE_FENCE();
-#pragma unroll
-            for (int j = 0; j < UNR; ++j) {
-              const int idx = idx0 + G * j;
-              if (idx < np) { const int t = idx / NX, i = idx - t * NX; d.Vx[GI(t, NX, i)] = combine_r(rv[j]); }
-            }
+            for (int w = 0; w < VP; ++w) rv[j][w] = row[w];
           }
-        } else {
-        for (int idx = q; idx < N * NU; idx += G) {
-          const int t = idx / NU, i = idx - t * NU;
-          const double ko = combine(tek + (((size_t)t * Bp + b) * NU + i) * VP);
-          d.k[GI(t, NU, i)] = ko;
-          if (d.t4) d.Kt[G4(t, NU * NX + NU, NU * NX + i)] = ko;
-          sn = dmax(sn, fabs(ko));
-        }
-        for (int idx = q; idx < (N + 1) * NX; idx += G) {
-          const int t = idx / NX, i = idx - t * NX;
-          d.Vx[GI(t, NX, i)] = combine(tep + (((size_t)t * Bp + b) * NX + i) * VP);
-        }
+          PIPELINE_FENCE();
+#pragma unroll
+          for (int j = 0; j < UNR; ++j) {
+            const int idx = idx0 + G * j;
+            if (idx < np) { const int t = idx / NX, i = idx - t * NX; d.Vx[GI(t, NX, i)] = combine_r(rv[j]); }
+          }
         }
       }
       Ls[C::oRed + q] = sn;
@@ -1103,7 +899,7 @@ __global__ __launch_bounds__(64) void k_backward_te_coop(DevBuf d, const Problem
       for (int j = 0; j < G; ++j) step_norm = dmax(step_norm, Ls[C::oRed + j]);
       tick(4);
       // ---- P5: linear-policy rollout dX with the final gains (ipddp_solver.cpp:1511-1520); lane qc = row qc
-      if constexpr (G == 16 && CDDP_TE_STAGED) {
+      if constexpr (G == 16) {
         // (as the epilogue of k_backward_ipddp_coop_big2: dx and du by row broadcast, the rows of K, A, B two steps ahead)
         struct RIn5 { double Kr[NX], kq, Ar[NX], Br[NU]; };
         const size_t tstr = (size_t)d.NB * 64;

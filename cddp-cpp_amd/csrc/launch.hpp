@@ -92,18 +92,14 @@ struct Launcher {
   // LogDDP on the device (kernels_logddp.hpp): one-lane kernels for every plant without a terminal set.  Register-resident up to
   // nx = 8; the nx >= 12 plants work through scratch in the sweep (12 KB per lane at the quadrotor: correct, slow -- the cooperative
   // LDS-operand form the IPDDP sweeps have is not built for LogDDP).  Full DDP (use_ilqr = 0) needs the explicit Hessian tensors.
-#ifndef CDDP_LOGDDP_MAX_NX
-#define CDDP_LOGDDP_MAX_NX 16
-#endif
-  static constexpr bool kLog = !TERM && Model::NX <= CDDP_LOGDDP_MAX_NX;
+  static constexpr int kLogMaxNx = 16;
+  static constexpr bool kLog = !TERM && Model::NX <= kLogMaxNx;
   // MSIPDDP on the device (kernels_msipddp.hpp); with path constraints only the shapes for which the reference's recursion is defined
   // (nu = 1 or nx = nu, msipddp_solver.cpp:1398).  Round 5: up to nx = 13, i.e. the unconstrained quadrotor runs resident (one-lane sweep
   // through scratch: correct, slow -- 9 KB per lane); the reference's own MSIPDDPTest.SolveQuadrotor (test_msipddp_solver.cpp:565) adds a
   // control box with nu = 4, nx = 13 -- a shape :1398 does not define -- and stays refused on both routes.
-#ifndef CDDP_MSIPDDP_MAX_NX
-#define CDDP_MSIPDDP_MAX_NX 13
-#endif
-  static constexpr bool kMs = !TERM && Model::NX <= CDDP_MSIPDDP_MAX_NX && (Cons::M == 0 || Model::NU == 1 || Model::NX == Model::NU);
+  static constexpr int kMsMaxNx = 13;
+  static constexpr bool kMs = !TERM && Model::NX <= kMsMaxNx && (Cons::M == 0 || Model::NU == 1 || Model::NX == Model::NU);
   static constexpr int ms_cst_size() { if constexpr (kMs && Cons::M > 0) return MsCst<Model, Cons>::SIZE; else return 0; }
   static dim3 gridB(const DevBuf &d) { return dim3((d.B + 63) / 64); }
   // Step sizes per rollout workgroup of the small path-constrained layouts: the two-wave form (default), CDDP_HIP_K4_NA = 2 | 3 =

@@ -233,15 +233,8 @@ DEV void sc_rows(const double *__restrict__ L, const double (&v)[K], Addr addr, 
 // arithmetic, all writes", and the matrix products are tiled: the R x CC outputs are cut into BR x BC blocks, one per lane of the group,
 // so that a lane reads (BR + BC) operands per k for BR BC multiply-adds (one column per lane needs 1 + 1 / rows reads per multiply-add
 // and leaves 16 - CC lanes idle).  Each output element is still ONE sequential sum over k ascending from 0.0 of the same products.
-#ifndef SC_V1_NX
-#define SC_V1_NX 13   // state sizes from here on keep the column-per-lane step (sweep_coop_v1)
-#endif
-#ifndef SC_FETCH_LATE
-#define SC_FETCH_LATE 0
-#endif
-#ifndef SC_MM_BUDGET
-#define SC_MM_BUDGET 24   // doubles of operands per chunk of a tiled product (two chunks in flight)
-#endif
+constexpr int kScV1Nx = 13;      // state sizes from here on keep the column-per-lane step (sweep_coop_v1)
+constexpr int kScMmBudget = 24;  // doubles of operands per chunk of a tiled product (two chunks in flight)
 constexpr int sc_tile_pick(int R, int CC, bool tall) {   // BR * 256 + BC: fewest outputs per lane with at most sixteen blocks, then the fewest operand reads
   int best = 256 * R + CC, bestArea = 1 << 30, bestSum = 1 << 30;
   for (int br = 1; br <= R; ++br)
@@ -276,7 +269,7 @@ template <int R, int CC, int K, bool MID, bool TALL = false, class LA, class RA,
 DEV void sc_mm(const double *__restrict__ L, const int gl, LA lhs, RA rhs, MA mid, Pre pre, Out out) {
   typedef SCTile<R, CC, TALL> T;
   constexpr int BR = T::BR, BC = T::BC;
-  constexpr int KC0 = SC_MM_BUDGET / (BR + BC + (MID ? 1 : 0)), KC = KC0 < 1 ? 1 : (KC0 > K ? K : KC0), NCH = (K + KC - 1) / KC;
+  constexpr int KC0 = kScMmBudget / (BR + BC + (MID ? 1 : 0)), KC = KC0 < 1 ? 1 : (KC0 > K ? K : KC0), NCH = (K + KC - 1) / KC;
   T tl; tl.init(gl);
   decltype(pre(0, 0)) pv[BR][BC];
   double acc[BR][BC];
@@ -835,9 +828,7 @@ DEV bool sweep_coop(const StackArgs &a0, const int b, const int gl0, const typen
     }
     lds_sync();
     SC_TICK(0);
-#if !SC_FETCH_LATE
     if (t > 0) rec.fetch(a, t - 1, gl, vo);   // in flight behind this step's arithmetic, parked at its end
-#endif
     // ---------------------------------------------------------------- Q_x, Q_u, T1 = A^T V_xx, T2 = B^T V_xx
     {
       double qx[(NX + 15) / 16], qu[(NU + 15) / 16];
@@ -1139,9 +1130,6 @@ DEV bool sweep_coop(const StackArgs &a0, const int b, const int gl0, const typen
                              [](int, int) { return 0.0; }, [&](int i, int j, double s1, double) { L[C::oKtQ + i * NU + j] = s1; });
     lds_sync();
     SC_TICK(8);
-#if SC_FETCH_LATE
-    if (t > 0) rec.fetch(a, t - 1, gl, vo);   // behind V_n and the symmetrisation (~5 k clocks), parked at the end of the step
-#endif
     // ---------------------------------------------------------------- value update
     double vxn[(NX + 15) / 16];
     SC_EACH(NX, i) {
@@ -1323,7 +1311,7 @@ __global__ __launch_bounds__(64) void k_stacks_backward_coop(StackArgs a) {
   double dV0 = 0, dV1 = 0, inf_du = 0, inf_pr = 0, inf_comp = 0, step_norm = 0;
   bool ok = false;
   for (;;) {
-    if constexpr (NX >= SC_V1_NX) ok = sweep_coop_v1<NX, NU, M>(a, b, gl, vo, L, reg, mu, dV0, dV1, inf_du, inf_pr, inf_comp, step_norm);
+    if constexpr (NX >= kScV1Nx) ok = sweep_coop_v1<NX, NU, M>(a, b, gl, vo, L, reg, mu, dV0, dV1, inf_du, inf_pr, inf_comp, step_norm);
     else ok = sweep_coop<NX, NU, M>(a, b, gl, vo, L, reg, mu, dV0, dV1, inf_du, inf_pr, inf_comp, step_norm);
     if (ok || !(a.reg_factor > 1.0)) break;
     reg = reg * a.reg_factor;
