@@ -79,7 +79,7 @@ const std::vector<KernelSet> &registry() {
     std::vector<KernelSet> r;
     register_pendulum(r); register_cartpole(r); register_unicycle(r); register_lti(r);
     register_quadrotor(r); register_quad12(r); register_manipulator(r); register_manip7(r); register_terminal(r); register_statebox(r);
-    register_vehicles(r); register_spacecraft(r);
+    register_vehicles(r); register_spacecraft(r); register_plants_small(r); register_plants_nx10(r);
     return r;
   }();
   return v;
@@ -160,11 +160,14 @@ bool model_has_hessians(int model) {
          model == CDDP_HIP_MODEL_BICYCLE || model == CDDP_HIP_MODEL_CAR || model == CDDP_HIP_MODEL_MANIPULATOR || model == CDDP_HIP_MODEL_HCW ||
          model == CDDP_HIP_MODEL_QUADROTOR || model == CDDP_HIP_MODEL_QUADROTOR_EULER12 || model == CDDP_HIP_MODEL_MANIPULATOR7 ||   // round 4: blocked second-order duals
          model == CDDP_HIP_MODEL_EULER_ATTITUDE || model == CDDP_HIP_MODEL_QUATERNION_ATTITUDE || model == CDDP_HIP_MODEL_MRP_ATTITUDE ||
-         model == CDDP_HIP_MODEL_SPACECRAFT_LANDING2D;   // (SpacecraftTwobody: none -- the reference's cross Hessian throws)
+         model == CDDP_HIP_MODEL_SPACECRAFT_LANDING2D ||   // (SpacecraftTwobody: none -- the reference's cross Hessian throws)
+         model == CDDP_HIP_MODEL_DUBINS_CAR || model == CDDP_HIP_MODEL_DREYFUS_ROCKET || model == CDDP_HIP_MODEL_ACROBOT || model == CDDP_HIP_MODEL_USV_3DOF ||
+         model == CDDP_HIP_MODEL_FORKLIFT || model == CDDP_HIP_MODEL_SPACECRAFT_LINEAR_FUEL || model == CDDP_HIP_MODEL_QUADROTOR_RATE;   // (SpacecraftNonlinear: none, as SpacecraftTwobody)
 }
 
 // the refusal of options.use_ilqr = 0 for a plant without Hessian tensors
 int fail_no_hessians(int model) {
+  if (model == CDDP_HIP_MODEL_SPACECRAFT_NONLINEAR) return fail(-3, "use_ilqr=false: %s", SpacecraftNonlinearModel::kNoHessMsg);
   if (model == CDDP_HIP_MODEL_SPACECRAFT_TWOBODY) return fail(-3, "use_ilqr=false: %s", SpacecraftTwobodyModel::kNoHessMsg);
   return fail(-3, "use_ilqr=false needs the plant's Hessian tensors, which model id %d does not have", model);
 }
@@ -195,6 +198,7 @@ int flatten(const cddp_hip_problem *p, ProblemDev &P) {
     if (cddp_host_model_params(p->model, p->nx, p->nu, p->model_params, P.mp, err)) return fail(-2, "%s", err.c_str());
   }
   if (p->model == CDDP_HIP_MODEL_CAR) P.mp[1] = p->dt;   // the car is a discrete plant: its step uses the timestep (car.cpp:24-60)
+  if (p->model == CDDP_HIP_MODEL_FORKLIFT) P.mp[3] = p->dt;   // likewise (forklift.cpp:17-48)
   if (p->model == CDDP_HIP_MODEL_LTI) {
     if (!p->lti_A || !p->lti_B) return fail(-2, "LTI model needs lti_A and lti_B");
     if (p->nx * p->nx + p->nx * p->nu + 1 > 32) return fail(-3, "LTI dims too large for the device parameter block");

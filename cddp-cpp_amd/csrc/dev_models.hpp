@@ -1035,6 +1035,319 @@ struct SpacecraftLanding2DModel {
   }
 };
 
+// ================================================================================ the remaining small plants (nx <= 8)
+// ---------------------------------------------------------------------------- DubinsCar (dubins_car.cpp)
+// State [x, y, theta], control [omega]; params: speed.  Analytic Jacobians (:72-102) and state Hessian (:104-126), zero control Hessian
+// (:128-141); the cross Hessian is the base class's autodiff default on speed cos / sin(theta), omega: no (u, x) term, i.e. zero.
+struct DubinsCarModel {
+  static constexpr int ID = CDDP_HIP_MODEL_DUBINS_CAR, NX = 3, NU = 1;
+  static constexpr bool kDiscrete = false;
+  static constexpr bool kHasHess = true;
+  DEV static void f(const double *p, const double *x, const double *u, double *xd) {
+    double s, c; plant_sincos(x[2], &s, &c);
+    xd[0] = p[0] * c; xd[1] = p[0] * s; xd[2] = u[0];
+  }
+  DEV static void jac(const double *p, const double *x, const double *, double *Fx, double *Fu) {
+    double s, c; plant_sincos(x[2], &s, &c);
+#pragma unroll
+    for (int i = 0; i < 9; ++i) Fx[i] = 0.0;
+    Fx[0 * 3 + 2] = -p[0] * s;
+    Fx[1 * 3 + 2] = p[0] * c;
+    Fu[0] = 0.0; Fu[1] = 0.0; Fu[2] = 1.0;
+  }
+  DEV static void hess(const double *p, const double *x, const double *, double *Fxx, double *Fuu, double *Fux) {
+    double s, c; plant_sincos(x[2], &s, &c);
+    for (int i = 0; i < NX * NX * NX; ++i) Fxx[i] = 0.0;
+    for (int i = 0; i < NX * NU * NU; ++i) Fuu[i] = 0.0;
+    for (int i = 0; i < NX * NU * NX; ++i) Fux[i] = 0.0;
+    Fxx[0 * 9 + 2 * 3 + 2] = -p[0] * c;
+    Fxx[1 * 9 + 2 * 3 + 2] = -p[0] * s;
+  }
+};
+
+// ---------------------------------------------------------------------------- DreyfusRocket (dreyfus_rocket.cpp)
+// State [x, x_dot], control [theta]; params: thrust_acceleration, gravity_acceleration.  Analytic Jacobians (:46-64), zero state Hessian,
+// analytic control Hessian (:72-82); cross Hessian: the autodiff default on an expression without a (u, x) term, i.e. zero.
+struct DreyfusRocketModel {
+  static constexpr int ID = CDDP_HIP_MODEL_DREYFUS_ROCKET, NX = 2, NU = 1;
+  static constexpr bool kDiscrete = false;
+  static constexpr bool kHasHess = true;
+  DEV static void f(const double *p, const double *x, const double *u, double *xd) {
+    xd[0] = x[1];
+    xd[1] = p[0] * dcos(u[0]) - p[1];
+  }
+  DEV static void jac(const double *p, const double *, const double *u, double *Fx, double *Fu) {
+    Fx[0] = 0.0; Fx[1] = 1.0; Fx[2] = 0.0; Fx[3] = 0.0;
+    Fu[0] = 0.0; Fu[1] = -p[0] * dsin(u[0]);
+  }
+  DEV static void hess(const double *p, const double *, const double *u, double *Fxx, double *Fuu, double *Fux) {
+    for (int i = 0; i < NX * NX * NX; ++i) Fxx[i] = 0.0;
+    for (int i = 0; i < NX * NU * NX; ++i) Fux[i] = 0.0;
+    Fuu[0] = 0.0;
+    Fuu[1] = -p[0] * dcos(u[0]);
+  }
+};
+
+// ---------------------------------------------------------------------------- Acrobot (acrobot.cpp)
+// State [theta1, theta2, theta1_dot, theta2_dot], control [torque on the second joint]; params: l1, l2, m1, m2, J1, J2; gravity 9.81 and
+// friction 1.0 are fixed (acrobot.hpp:138-139).  No derivative override: every Jacobian and Hessian is the base class's autodiff of the
+// autodiff expression (:98-163), which is the value expression on duals.  The 2 x 2 mass-matrix inverse is Eigen's fixed-size one on the
+// scalar type at hand: cofactors times 1 / det, then the matrix-vector product.
+struct AcrobotDyn {
+  template <class S>
+  DEV static void eval(const double *p, const S *x, const S *u, S *xd) {
+    const double l1 = p[0], l2 = p[1], m1 = p[2], m2 = p[3], J1 = p[4], J2 = p[5], gravity = 9.81, friction = 1.0;
+    const S theta1 = x[0], theta2 = x[1], w1 = x[2], w2 = x[3];
+    const S c1 = dcos(theta1), s2 = dsin(theta2), c2 = dcos(theta2), c12 = dcos(theta1 + theta2);
+    const S m11 = (S(m1 * l1 * l1 + J1) + S(m2) * (S(l1 * l1 + l2 * l2) + S(2 * l1 * l2) * c2)) + S(J2);
+    const S m12 = S(m2) * (S(l2 * l2) + S(l1 * l2) * c2) + S(J2);
+    const S m22 = S(l2 * l2 * m2 + J2);
+    const S tmp = S(l1 * l2 * m2) * s2;
+    const S b1 = -((S(2.0) * w1) * w2 + w2 * w2) * tmp;
+    const S b2 = (tmp * w1) * w1;
+    const S g1 = (S((m1 + m2) * l1) * c1 + S(m2 * l2) * c12) * S(gravity);
+    const S g2 = (S(m2 * l2) * c12) * S(gravity);
+    const S r1 = ((S(0.0) - b1) - g1) - S(friction) * w1;
+    const S r2 = ((u[0] - b2) - g2) - S(friction) * w2;
+    const S invdet = S(1.0) / (m11 * m22 - m12 * m12);
+    xd[0] = w1;
+    xd[1] = w2;
+    xd[2] = (m22 * invdet) * r1 + ((-m12) * invdet) * r2;
+    xd[3] = ((-m12) * invdet) * r1 + (m11 * invdet) * r2;
+  }
+};
+struct AcrobotModel {
+  static constexpr int ID = CDDP_HIP_MODEL_ACROBOT, NX = 4, NU = 1;
+  static constexpr bool kDiscrete = false;
+  static constexpr bool kHasHess = true;   // Dual2N<5>, the cart-pole's frame
+  DEV static void f(const double *p, const double *x, const double *u, double *xd) { AcrobotDyn::eval<double>(p, x, u, xd); }
+  DEV static void jac(const double *p, const double *x, const double *u, double *Fx, double *Fu) { ad_jacobian<AcrobotDyn, NX, NU>(p, x, u, Fx, Fu); }
+  DEV static void hess(const double *p, const double *x, const double *u, double *Fxx, double *Fuu, double *Fux) {
+    ad_hessian<AcrobotDyn, NX, NU>(p, x, u, 1.0, Fxx, Fuu, Fux);
+  }
+};
+
+// ---------------------------------------------------------------------------- Usv3Dof (usv_3dof.cpp)
+// Surface vessel, state [x, y, psi, u, v, r], control [tau_u, tau_v, tau_r].  The caller passes no parameters: the library fills
+// p[0..8] = M^-1 (Eigen's fixed 3 x 3 inverse of M_rb + M_a), p[9..17] = D_L, p[18..20] = m_x, m_y, m_yr from the reference's fixed vessel
+// (:17-48; host_models.cpp).  Jacobians: the analytic ones as written at :152-227 (not autodiff: equal to rounding, another operation
+// order).  State and cross Hessians: the base class's autodiff of :104-150; control Hessian: a zero override (:237-246) -- and the
+// autodiff expression is linear in tau, so the blocked contraction of the device build adds exact zeros there.
+struct Usv3DofDyn {
+  template <class S>
+  DEV static void eval(const double *p, const S *x, const S *tau, S *xd) {
+    const S psi = x[2], u = x[3], v = x[4], r = x[5];
+    const S c_psi = dcos(psi), s_psi = dsin(psi);
+    const double m_x = p[18], m_y = p[19], m_yr = p[20];
+    xd[0] = c_psi * u - s_psi * v;
+    xd[1] = s_psi * u + c_psi * v;
+    xd[2] = r;
+    const S nu[3] = {u, v, r};
+    // C(nu) nu with C's structural zeros left out (x + 0 * y == x for finite operands)
+    const S C02 = S(-m_y) * v - S(m_yr) * r, C12 = S(m_x) * u, C20 = S(m_y) * v + S(m_yr) * r, C21 = S(-m_x) * u;
+    const S Cnu[3] = {C02 * r, C12 * r, C20 * u + C21 * v};
+    S w[3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+      const S Dnu = (S(p[9 + 3 * i]) * nu[0] + S(p[9 + 3 * i + 1]) * nu[1]) + S(p[9 + 3 * i + 2]) * nu[2];
+      w[i] = (tau[i] - Cnu[i]) - Dnu;
+    }
+#pragma unroll
+    for (int i = 0; i < 3; ++i) xd[3 + i] = (S(p[3 * i]) * w[0] + S(p[3 * i + 1]) * w[1]) + S(p[3 * i + 2]) * w[2];
+  }
+};
+struct Usv3DofModel {
+  static constexpr int ID = CDDP_HIP_MODEL_USV_3DOF, NX = 6, NU = 3;
+  static constexpr bool kDiscrete = false;
+#ifdef CDDP_HOST_MODELS
+  static constexpr bool kHasHess = true;
+  static constexpr bool kHessBlocked = false;
+  static void hess(const double *p, const double *x, const double *u, double *Fxx, double *Fuu, double *Fux) {
+    ad_hessian<Usv3DofDyn, NX, NU>(p, x, u, 1.0, Fxx, Fuu, Fux);
+    for (int i = 0; i < NX * NU * NU; ++i) Fuu[i] = 0.0;
+  }
+#else
+  static constexpr bool kHasHess = false;   // device: the blocked contraction, as the attitude plants of the same size
+  static constexpr bool kHessBlocked = true;
+  typedef Usv3DofDyn HessDyn;
+  static constexpr double kHessDiv = 1.0;
+#endif
+  DEV static void f(const double *p, const double *x, const double *u, double *xd) { Usv3DofDyn::eval<double>(p, x, u, xd); }
+  DEV static void jac(const double *p, const double *x, const double *, double *Fx, double *Fu) {
+    const double u = x[3], v = x[4], r = x[5];
+    double s_psi, c_psi; plant_sincos(x[2], &s_psi, &c_psi);
+    const double m_x = p[18], m_y = p[19], m_yr = p[20];
+#pragma unroll
+    for (int i = 0; i < NX * NX; ++i) Fx[i] = 0.0;
+#pragma unroll
+    for (int i = 0; i < NX * NU; ++i) Fu[i] = 0.0;
+    Fx[0 * NX + 2] = -s_psi * u - c_psi * v;
+    Fx[1 * NX + 2] = c_psi * u - s_psi * v;
+    Fx[0 * NX + 3] = c_psi; Fx[0 * NX + 4] = -s_psi;
+    Fx[1 * NX + 3] = s_psi; Fx[1 * NX + 4] = c_psi;
+    Fx[2 * NX + 5] = 1.0;
+    double G[9];   // -dCnu_dnu - D_L
+    G[0] = 0.0; G[1] = -m_y * r; G[2] = -m_y * v - 2 * m_yr * r;
+    G[3] = m_x * r; G[4] = 0.0; G[5] = m_x * u;
+    G[6] = (m_y - m_x) * v + m_yr * r; G[7] = (m_y - m_x) * u; G[8] = m_yr * u;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) G[i] = -G[i] - p[9 + i];
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+      for (int j = 0; j < 3; ++j) {
+        Fx[(3 + i) * NX + 3 + j] = (p[3 * i] * G[j] + p[3 * i + 1] * G[3 + j]) + p[3 * i + 2] * G[6 + j];
+        Fu[(3 + i) * NU + j] = p[3 * i + j];
+      }
+  }
+};
+
+// ---------------------------------------------------------------------------- Forklift (forklift.cpp)
+// A DISCRETE plant like the car: getDiscreteDynamics is overridden (:17-48, the integrator argument is ignored) and everything else
+// differentiates it -- Jacobians are the autodiff gradient of the discrete map with J.diagonal() -= 1 and J /= timestep (:50-87),
+// Hessians its autodiff Hessian / timestep (:89-125; the cross Hessian through the base default on (x+ - x) / timestep is the same
+// block).  State [x, y, theta, v, steering angle], control [acceleration, steering rate]; params: wheelbase, rear_steer (0 / 1),
+// max_steering_angle (carried, unused by the dynamics), p[3] = timestep (filled in by the library).
+struct ForkliftDyn {
+  template <class S>
+  DEV static void eval(const double *p, const S *x, const S *u, S *xn) {
+    const double L = p[0], h = p[3];
+    const double steer_sign = p[1] != 0.0 ? -1.0 : 1.0;
+    const S theta = x[2], v = x[3];
+    const S effective_delta = S(steer_sign) * x[4];
+    const S cos_theta = dcos(theta), sin_theta = dsin(theta), tan_delta = dtan(effective_delta);
+    const S hv = S(h) * v;
+    xn[0] = x[0] + hv * cos_theta;
+    xn[1] = x[1] + hv * sin_theta;
+    xn[2] = x[2] + (hv * tan_delta) / S(L);
+    xn[3] = x[3] + S(h) * u[0];
+    xn[4] = x[4] + S(h) * u[1];
+  }
+};
+struct ForkliftModel {
+  static constexpr int ID = CDDP_HIP_MODEL_FORKLIFT, NX = 5, NU = 2;
+  static constexpr bool kDiscrete = true;
+  static constexpr bool kHasHess = true;
+  DEV static void step(const double *p, const double *x, const double *u, double *xn) { ForkliftDyn::eval<double>(p, x, u, xn); }
+  DEV static void f(const double *, const double *, const double *, double *) {}
+  DEV static void jac(const double *p, const double *x, const double *u, double *Fx, double *Fu) {
+    ad_jacobian_blocked<ForkliftDyn, NX, NU, 4>(p, x, u, Fx, Fu);
+    const double h = p[3];
+#pragma unroll
+    for (int i = 0; i < NX; ++i) Fx[i * NX + i] -= 1.0;
+#pragma unroll
+    for (int i = 0; i < NX * NX; ++i) Fx[i] = Fx[i] / h;
+#pragma unroll
+    for (int i = 0; i < NX * NU; ++i) Fu[i] = Fu[i] / h;
+  }
+  DEV static void hess(const double *p, const double *x, const double *u, double *Fxx, double *Fuu, double *Fux) {
+    ad_hessian<ForkliftDyn, NX, NU>(p, x, u, p[3], Fxx, Fuu, Fux);
+  }
+};
+
+// ---------------------------------------------------------------------------- SpacecraftLinearFuel (spacecraft_linear_fuel.cpp)
+// HCW relative motion with a mass state: [x, y, z, vx, vy, vz, mass, accumulated control effort], control [Fx, Fy, Fz]; params:
+// mean_motion, isp, g0; epsilon = 1e-8 under the thrust norm is fixed (:27).  Jacobians: central FD (:124-139).  All three Hessians are
+// zero overrides (:141-158): full DDP is allowed and adds nothing.
+struct SpacecraftLinearFuelModel {
+  static constexpr int ID = CDDP_HIP_MODEL_SPACECRAFT_LINEAR_FUEL, NX = 8, NU = 3;
+  static constexpr bool kDiscrete = false;
+  static constexpr bool kHasHess = true;
+  static constexpr bool kHessBlocked = false;
+  DEV static void f(const double *p, const double *x, const double *u, double *xd) {
+    const double n = p[0], n2 = n * n, isp = p[1], g0 = p[2], mass = x[6];
+    xd[0] = x[3]; xd[1] = x[4]; xd[2] = x[5];
+    xd[3] = (2.0 * n * x[4] + 3.0 * n2 * x[0]) + u[0] / mass;
+    xd[4] = -2.0 * n * x[3] + u[1] / mass;
+    xd[5] = -n2 * x[2] + u[2] / mass;
+    const double thrust_squared = (u[0] * u[0] + u[1] * u[1]) + u[2] * u[2];
+    xd[6] = -sqrt(thrust_squared + 1e-8) / (isp * g0);
+    xd[7] = 0.5 * thrust_squared;
+  }
+  DEV static void jac(const double *p, const double *x, const double *u, double *Fx, double *Fu) { fd_jacobian<SpacecraftLinearFuelModel>(p, x, u, Fx, Fu); }
+  DEV static void hess(const double *, const double *, const double *, double *Fxx, double *Fuu, double *Fux) {
+    for (int i = 0; i < NX * NX * NX; ++i) Fxx[i] = 0.0;
+    for (int i = 0; i < NX * NU * NU; ++i) Fuu[i] = 0.0;
+    for (int i = 0; i < NX * NU * NX; ++i) Fux[i] = 0.0;
+  }
+};
+
+// ================================================================================ the two nx = 10 plants
+// ---------------------------------------------------------------------------- QuadrotorRate (quadrotor_rate.cpp)
+// Rate-controlled quadrotor: state [px, py, pz, vx, vy, vz, qw, qx, qy, qz], control [thrust, wx, wy, wz]; params: mass, max_thrust,
+// max_rate (the last two are carried, the dynamics do not read them; all three must be positive, host_models.cpp); gravity 9.81.
+// The value (:35-97) normalises q without a guard and goes through R (0, 0, thrust)^T and 0.5 Omega q; with the structural zeros left
+// out and the exact factor 0.5 taken out of the sums, those products are, operation for operation, the sums of the autodiff expression
+// (:142-202), so one templated body serves both.  Every derivative is the base class's autodiff THROUGH the normalisation.
+struct QuadrotorRateDyn {
+  template <class S>
+  DEV static void eval(const double *p, const S *x, const S *u, S *xd) {
+    const double mass = p[0], grav = 9.81;
+    const S qw = x[6], qx = x[7], qy = x[8], qz = x[9];
+    const S q_norm = dsqrt(((qw * qw + qx * qx) + qy * qy) + qz * qz);
+    const S qw_n = qw / q_norm, qx_n = qx / q_norm, qy_n = qy / q_norm, qz_n = qz / q_norm;
+    const S thrust = u[0], wx = u[1], wy = u[2], wz = u[3];
+    xd[0] = x[3]; xd[1] = x[4]; xd[2] = x[5];
+    const S R02 = S(2.0) * (qx_n * qz_n + qy_n * qw_n);
+    const S R12 = S(2.0) * (qy_n * qz_n - qx_n * qw_n);
+    const S R22 = S(1.0) - S(2.0) * (qx_n * qx_n + qy_n * qy_n);
+    xd[3] = (R02 * thrust) / S(mass);
+    xd[4] = (R12 * thrust) / S(mass);
+    xd[5] = (R22 * thrust) / S(mass) - S(grav);
+    xd[6] = S(0.5) * (((-qx_n) * wx - qy_n * wy) - qz_n * wz);
+    xd[7] = S(0.5) * ((qw_n * wx + qy_n * wz) - qz_n * wy);
+    xd[8] = S(0.5) * ((qw_n * wy - qx_n * wz) + qz_n * wx);
+    xd[9] = S(0.5) * ((qw_n * wz + qx_n * wy) - qy_n * wx);
+  }
+};
+struct QuadrotorRateModel {
+  static constexpr int ID = CDDP_HIP_MODEL_QUADROTOR_RATE, NX = 10, NU = 4;
+  static constexpr bool kDiscrete = false;
+#ifdef CDDP_HOST_MODELS
+  static constexpr bool kHasHess = true;
+  static constexpr bool kHessBlocked = false;
+  static void hess(const double *p, const double *x, const double *u, double *Fxx, double *Fuu, double *Fux) { ad_hessian<QuadrotorRateDyn, NX, NU>(p, x, u, 1.0, Fxx, Fuu, Fux); }
+#else
+  static constexpr bool kHasHess = false;   // device: the blocked contraction, as the 13-state quadrotor
+  static constexpr bool kHessBlocked = true;
+  typedef QuadrotorRateDyn HessDyn;
+  static constexpr double kHessDiv = 1.0;
+#endif
+  DEV static void f(const double *p, const double *x, const double *u, double *xd) { QuadrotorRateDyn::eval<double>(p, x, u, xd); }
+  DEV static void jac(const double *p, const double *x, const double *u, double *Fx, double *Fu) {
+    ad_jacobian_blocked<QuadrotorRateDyn, NX, NU, 4>(p, x, u, Fx, Fu);
+  }
+};
+
+// ---------------------------------------------------------------------------- SpacecraftNonlinear (spacecraft_nonlinear.cpp)
+// Nonlinear relative motion about an orbit that is itself integrated: state [px, py, pz, vx, vy, vz, r0, theta, dr0, dtheta], control
+// [ux, uy, uz]; params: mass, r_scale, v_scale (carried, unused by the dynamics), mu.  pow(s, 1.5) of the reference (:51) is taken as
+// s * sqrt(s): one correctly rounded square root and one product, within an ulp or two of the libm's pow and far inside the plant
+// tests' 1e-13.  Jacobians: central FD (:75-91).  State / control Hessians are zero overrides, but there is no autodiff expression, so
+// the base class's cross Hessian throws: full DDP is refused for this plant, as for SpacecraftTwobody.
+struct SpacecraftNonlinearModel {
+  static constexpr int ID = CDDP_HIP_MODEL_SPACECRAFT_NONLINEAR, NX = 10, NU = 3;
+  static constexpr bool kDiscrete = false;
+  static constexpr bool kHasHess = false;
+  static constexpr bool kHessBlocked = false;
+  static constexpr const char *kNoHessMsg = SpacecraftTwobodyModel::kNoHessMsg;
+  DEV static void f(const double *p, const double *x, const double *u, double *xd) {
+    const double mass = p[0], mu = p[3];
+    const double px = x[0], py = x[1], pz = x[2], vx = x[3], vy = x[4], r0 = x[6], dr0 = x[8], dtheta = x[9];
+    const double s = ((r0 + px) * (r0 + px) + py * py) + pz * pz;
+    const double den = s * sqrt(s);
+    const double r0_sq = r0 * r0;
+    const double ddr0 = -mu / r0_sq + r0 * dtheta * dtheta;
+    const double ddtheta = -2.0 * dr0 * dtheta / r0;
+    xd[0] = vx; xd[1] = vy; xd[2] = x[5];
+    xd[3] = ((((2.0 * dtheta * vy + ddtheta * py) + dtheta * dtheta * px) - mu * (px + r0) / den) + mu / r0_sq) + u[0] / mass;
+    xd[4] = ((((-2.0 * dtheta * vx - ddtheta * px) + dtheta * dtheta * py) - mu * py / den)) + u[1] / mass;
+    xd[5] = -mu * pz / den + u[2] / mass;
+    xd[6] = dr0; xd[7] = dtheta; xd[8] = ddr0; xd[9] = ddtheta;
+  }
+  DEV static void jac(const double *p, const double *x, const double *u, double *Fx, double *Fu) { fd_jacobian<SpacecraftNonlinearModel>(p, x, u, Fx, Fu); }
+};
+
 // ---- explicit integrators (dynamical_system.cpp:28-83) --------------------------------------
 // Loop-invariant integrator constants held in registers (SGPRs) by the serial kernels: the step size products
 // and the plant parameters would otherwise be re-fetched through dependent scalar loads -- and dt/6 re-divided --

@@ -416,5 +416,7 @@ void register_manip7(std::vector<KernelSet> &);
 void register_terminal(std::vector<KernelSet> &);
 void register_statebox(std::vector<KernelSet> &);
 void register_spacecraft(std::vector<KernelSet> &);
+void register_plants_small(std::vector<KernelSet> &);
+void register_plants_nx10(std::vector<KernelSet> &);
 
 }  // namespace cddp_dev

@@ -283,6 +283,41 @@ struct SpacecraftLanding2D : DynamicalSystem { // spacecraft_landing2d.hpp:38-45
                       double min_thrust = 880000.0, double max_thrust = 2210000.0, double max_gimble = 0.349066)
       : DynamicalSystem(CDDP_HIP_MODEL_SPACECRAFT_LANDING2D, 6, 2, dt, integ) { params = {mass, length, width, min_thrust, max_thrust, max_gimble}; }
 };
+struct DubinsCar : DynamicalSystem {         // dubins_car.hpp:39: (speed, timestep, integration_type); state [x, y, theta], control [omega]
+  DubinsCar(double speed, double dt, std::string integ = "euler") : DynamicalSystem(CDDP_HIP_MODEL_DUBINS_CAR, 3, 1, dt, integ) { params = {speed}; }
+};
+struct DreyfusRocket : DynamicalSystem {     // dreyfus_rocket.hpp:38: state [x, x_dot], control [theta]
+  DreyfusRocket(double dt, std::string integ = "rk4", double thrust_acceleration = 64.0, double gravity_acceleration = 32.0)
+      : DynamicalSystem(CDDP_HIP_MODEL_DREYFUS_ROCKET, 2, 1, dt, integ) { params = {thrust_acceleration, gravity_acceleration}; }
+};
+struct Acrobot : DynamicalSystem {           // acrobot.hpp:46: state [theta1, theta2, theta1_dot, theta2_dot], control [torque]
+  Acrobot(double dt, double l1 = 1.0, double l2 = 1.0, double m1 = 1.0, double m2 = 1.0, double J1 = 1.0, double J2 = 1.0, std::string integ = "euler")
+      : DynamicalSystem(CDDP_HIP_MODEL_ACROBOT, 4, 1, dt, integ) { params = {l1, l2, m1, m2, J1, J2}; }
+};
+struct Usv3Dof : DynamicalSystem {           // usv_3dof.hpp:31: state [x, y, psi, u, v, r], control [tau_u, tau_v, tau_r]; the library fills the vessel's block
+  Usv3Dof(double dt, std::string integ = "euler") : DynamicalSystem(CDDP_HIP_MODEL_USV_3DOF, 6, 3, dt, integ) {}
+};
+struct Forklift : DynamicalSystem {          // forklift.hpp:54: a DISCRETE plant; state [x, y, theta, v, delta], control [a, steering rate]
+  Forklift(double dt = 0.01, double wheelbase = 2.0, std::string integ = "euler", bool rear_steer = true, double max_steering_angle = 0.785398)
+      : DynamicalSystem(CDDP_HIP_MODEL_FORKLIFT, 5, 2, dt, integ) { params = {wheelbase, rear_steer ? 1.0 : 0.0, max_steering_angle}; }
+};
+struct SpacecraftLinearFuel : DynamicalSystem {   // spacecraft_linear_fuel.hpp:34: state [x, y, z, vx, vy, vz, mass, effort], control [Fx, Fy, Fz]
+  SpacecraftLinearFuel(double dt, double mean_motion, double isp, double g0 = 9.80665, std::string integ = "euler")
+      : DynamicalSystem(CDDP_HIP_MODEL_SPACECRAFT_LINEAR_FUEL, 8, 3, dt, integ) { params = {mean_motion, isp, g0}; }
+};
+struct QuadrotorRate : DynamicalSystem {     // quadrotor_rate.hpp: (timestep, mass, max_thrust, max_rate, integration_type); state [p, v, qw, qx, qy, qz], control [thrust, wx, wy, wz]
+  QuadrotorRate(double dt, double mass, double max_thrust, double max_rate, std::string integ = "euler")
+      : DynamicalSystem(CDDP_HIP_MODEL_QUADROTOR_RATE, 10, 4, dt, integ) {
+    if (!(mass > 0.0)) throw std::invalid_argument("Mass must be positive");
+    if (!(max_thrust > 0.0)) throw std::invalid_argument("Maximum thrust must be positive");
+    if (!(max_rate > 0.0)) throw std::invalid_argument("Maximum angular rate must be positive");
+    params = {mass, max_thrust, max_rate};
+  }
+};
+struct SpacecraftNonlinear : DynamicalSystem {   // spacecraft_nonlinear.hpp: state [p, v, r0, theta, dr0, dtheta], control [ux, uy, uz]; no full DDP
+  SpacecraftNonlinear(double dt, std::string integ = "rk4", double mass = 1.0, double r_scale = 1.0, double v_scale = 1.0, double mu = 1.0)
+      : DynamicalSystem(CDDP_HIP_MODEL_SPACECRAFT_NONLINEAR, 10, 3, dt, integ) { params = {mass, r_scale, v_scale, mu}; }
+};
 struct Manipulator : DynamicalSystem {
   Manipulator(double dt, std::string integ = "rk4") : DynamicalSystem(CDDP_HIP_MODEL_MANIPULATOR, 6, 3, dt, integ) {}
 };

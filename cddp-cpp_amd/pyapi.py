@@ -23,6 +23,8 @@ MODEL_QUADROTOR, MODEL_MANIPULATOR, MODEL_QUADROTOR_EULER12, MODEL_MANIPULATOR7 
 MODEL_BICYCLE, MODEL_CAR, MODEL_HCW = 8, 9, 10
 MODEL_EULER_ATTITUDE, MODEL_QUATERNION_ATTITUDE, MODEL_MRP_ATTITUDE = 11, 12, 13
 MODEL_SPACECRAFT_TWOBODY, MODEL_SPACECRAFT_LANDING2D = 14, 15
+MODEL_DUBINS_CAR, MODEL_DREYFUS_ROCKET, MODEL_ACROBOT, MODEL_USV_3DOF, MODEL_FORKLIFT = 16, 17, 18, 19, 20
+MODEL_QUADROTOR_RATE, MODEL_SPACECRAFT_LINEAR_FUEL, MODEL_SPACECRAFT_NONLINEAR = 21, 22, 23
 EULER, HEUN, RK3, RK4 = 0, 1, 2, 3
 SOLVER_CLDDP, SOLVER_IPDDP, SOLVER_LOGDDP, SOLVER_MSIPDDP = 0, 1, 2, 3
 CON_CONTROL_BOX, CON_STATE_BOX, CON_BALL, CON_LINEAR = 0, 1, 2, 3
@@ -590,6 +592,132 @@ def landing2d_problem(solver=SOLVER_IPDDP, horizon=80, constrained=True, integra
         p.add_control_box("ControlConstraint", [tmin / tmax, -gmax], [1.0, gmax])
     p.x0 = np.array([20.0, -2.0, 150.0, -15.0, 0.05, 0.0])
     p.U0_const = np.array([9.81 * mass / tmax, 0.0])
+    return p
+
+
+# ---- the remaining small plants (src/dynamics_model/{dubins_car,dreyfus_rocket,acrobot,usv_3dof,forklift,spacecraft_linear_fuel}.cpp)
+def dubins_problem(solver=SOLVER_IPDDP, horizon=60, constrained=True, integrator=None):
+    """Constant-speed Dubins car (state [x, y, theta], control [omega]; speed 1): a quarter turn to (3.8, 3.8, pi / 2), turn-rate box +-1;
+    starts from a constant turn rate."""
+    o = default_options(); o.max_iterations = 60; o.tolerance = 1e-5; o.acceptable_tolerance = 1e-6
+    dt = 0.1
+    p = Problem(solver, MODEL_DUBINS_CAR, EULER if integrator is None else integrator, 3, 1, horizon, dt, np.zeros((3, 3)), 0.1 * np.eye(1),
+                np.diag([100.0, 100.0, 50.0]), [3.8, 3.8, np.pi / 2], model_params=[1.0], options=o)
+    if constrained:
+        p.add_control_box("ControlConstraint", [-1.0], [1.0])
+    p.x0 = np.zeros(3)
+    p.U0_const = np.array([0.2])
+    return p
+
+
+def dreyfus_problem(solver=SOLVER_IPDDP, horizon=50, constrained=True, integrator=None):
+    """Dreyfus rocket (state [x, x_dot], control [thrust angle]; thrust 64, gravity 32 as the reference's defaults): climb one unit and
+    stop, thrust angle within [0.05, 3]; starts from the hover angle pi / 3."""
+    o = default_options(); o.max_iterations = 60; o.tolerance = 1e-5; o.acceptable_tolerance = 1e-6
+    dt = 0.01
+    p = Problem(solver, MODEL_DREYFUS_ROCKET, RK4 if integrator is None else integrator, 2, 1, horizon, dt, np.zeros((2, 2)), 0.1 * np.eye(1),
+                np.diag([100.0, 10.0]), [1.0, 0.0], model_params=[64.0, 32.0], options=o)
+    if constrained:
+        p.add_control_box("ControlConstraint", [0.05], [3.0])
+    p.x0 = np.zeros(2)
+    p.U0_const = np.array([np.pi / 3])
+    return p
+
+
+ACROBOT_PARAMS = (1.0, 1.0, 1.0, 1.0, 1.0, 1.0)   # acrobot.hpp:46-50 defaults: l1, l2, m1, m2, J1, J2
+
+
+def acrobot_problem(solver=SOLVER_IPDDP, horizon=80, constrained=True, integrator=None):
+    """Acrobot (state [theta1, theta2, theta1_dot, theta2_dot], torque on the second joint) from its hanging rest to a bent elbow,
+    torque box +-10."""
+    o = default_options(); o.max_iterations = 60; o.tolerance = 1e-4; o.acceptable_tolerance = 1e-6
+    dt = 0.02
+    p = Problem(solver, MODEL_ACROBOT, RK4 if integrator is None else integrator, 4, 1, horizon, dt, np.zeros((4, 4)), 0.01 * np.eye(1),
+                np.diag([100.0, 100.0, 10.0, 10.0]), [-np.pi / 2, 0.5, 0.0, 0.0], model_params=ACROBOT_PARAMS, options=o)
+    if constrained:
+        p.add_control_box("ControlConstraint", [-10.0], [10.0])
+    p.x0 = np.array([-np.pi / 2, 0.0, 0.0, 0.0])
+    return p
+
+
+def usv_problem(solver=SOLVER_IPDDP, horizon=80, constrained=True, integrator=None):
+    """3-DOF surface vessel (state [x, y, psi, u, v, r], control [tau_u, tau_v, tau_r]; the reference's fixed vessel, no parameters): from
+    rest to (3, 2) with heading 0.3, force / moment box +-200.  (Under use_ilqr = 0 the tensor terms make Q_xx indefinite at the
+    first iterate of this problem and the value recursion over 80 steps amplifies rounding: use a short horizon for full DDP.)"""
+    o = default_options(); o.max_iterations = 60; o.tolerance = 1e-4; o.acceptable_tolerance = 1e-6
+    dt = 0.1
+    p = Problem(solver, MODEL_USV_3DOF, RK4 if integrator is None else integrator, 6, 3, horizon, dt, np.zeros((6, 6)), 1e-4 * np.eye(3),
+                np.diag([100.0, 100.0, 100.0, 10.0, 10.0, 10.0]), [3.0, 2.0, 0.3, 0.0, 0.0, 0.0], options=o)
+    if constrained:
+        p.add_control_box("ControlConstraint", [-200.0] * 3, [200.0] * 3)
+    p.x0 = np.zeros(6)
+    return p
+
+
+FORKLIFT_PARAMS = (2.0, 1.0, 0.785398)   # forklift.hpp:54-58 defaults: wheelbase, rear_steer, max_steering_angle
+
+
+def forklift_problem(solver=SOLVER_IPDDP, horizon=100, constrained=True):
+    """The reference's rear-steered forklift (a DISCRETE plant; state [x, y, theta, v, steering angle], control [acceleration, steering
+    rate]): a lane change to (2, 1) with heading 0.5 at rest, box +-[1, 1].  (Under use_ilqr = 0 the first sweep over the 100 steps is
+    ill-conditioned in the same way as usv_problem's, more mildly.)"""
+    o = default_options(); o.max_iterations = 80; o.tolerance = 1e-4; o.acceptable_tolerance = 1e-6
+    dt = 0.03
+    p = Problem(solver, MODEL_FORKLIFT, EULER, 5, 2, horizon, dt, np.zeros((5, 5)), np.diag([0.1, 1.0]),
+                np.diag([100.0, 100.0, 50.0, 10.0, 10.0]), [2.0, 1.0, 0.5, 0.0, 0.0], model_params=FORKLIFT_PARAMS, options=o)
+    if constrained:
+        p.add_control_box("ControlConstraint", [-1.0, -1.0], [1.0, 1.0])
+    p.x0 = np.array([0.0, 0.0, 0.0, 0.5, 0.0])
+    p.U0_const = np.array([0.1, -0.05])
+    return p
+
+
+def linear_fuel_problem(solver=SOLVER_IPDDP, horizon=80, constrained=True, integrator=None):
+    """The HCW rendezvous of hcw_problem with a mass state (state [x, y, z, vx, vy, vz, mass, accumulated control effort]; 1 kg, Isp 300 s):
+    the mass and effort states carry no cost."""
+    o = default_options(); o.max_iterations = 40; o.tolerance = 1e-5; o.acceptable_tolerance = 1e-6; o.reg_initial_value = 1e-6
+    n = float(np.sqrt(3.986004418e14 / (6371e3 + 500e3) ** 3))
+    dt = 10.0
+    p = Problem(solver, MODEL_SPACECRAFT_LINEAR_FUEL, RK4 if integrator is None else integrator, 8, 3, horizon, dt,
+                np.diag([1e-4] * 3 + [1e-2] * 3 + [0.0, 0.0]), 1.0 * np.eye(3), np.diag([10.0] * 3 + [100.0] * 3 + [0.0, 0.0]), np.zeros(8),
+                model_params=[n, 300.0, 9.80665], options=o)
+    if constrained:
+        p.add_control_box("ControlConstraint", -0.5 * np.ones(3), 0.5 * np.ones(3))
+    p.x0 = np.array([-37.59664132226163, 27.312455860666148, 13.656227930333074, 0.015161970413423813, 0.08348413138390476, 0.04174206569195238,
+                     1.0, 0.0])
+    return p
+
+
+QUADROTOR_RATE_PARAMS = (1.0, 20.0, 0.5)   # mass, max_thrust, max_rate (the constants of the reference's own test of the plant)
+
+
+def quadrotor_rate_problem(solver=SOLVER_IPDDP, horizon=60, constrained=True, integrator=None):
+    """Rate-controlled quadrotor (state [p, v, q = (qw, qx, qy, qz)], control [thrust, wx, wy, wz]): from hover at the origin to hover at
+    (0.5, 0.3, 0.5), thrust within [0, max_thrust], body rates within +-max_rate; starts from the hover thrust."""
+    o = default_options(); o.max_iterations = 60; o.tolerance = 1e-4; o.acceptable_tolerance = 1e-6
+    dt = 0.05
+    mass, max_thrust, max_rate = QUADROTOR_RATE_PARAMS
+    goal = np.array([0.5, 0.3, 0.5, 0, 0, 0, 1.0, 0, 0, 0])
+    p = Problem(solver, MODEL_QUADROTOR_RATE, RK4 if integrator is None else integrator, 10, 4, horizon, dt, np.zeros((10, 10)),
+                np.diag([0.01, 0.1, 0.1, 0.1]), np.diag([100.0] * 3 + [10.0] * 3 + [10.0] * 4), goal, model_params=QUADROTOR_RATE_PARAMS, options=o)
+    if constrained:
+        p.add_control_box("ControlConstraint", [0.0, -max_rate, -max_rate, -max_rate], [max_thrust, max_rate, max_rate, max_rate])
+    p.x0 = np.array([0.0, 0, 0, 0, 0, 0, 1.0, 0, 0, 0])
+    p.U0_const = np.array([mass * 9.81, 0.0, 0.0, 0.0])
+    return p
+
+
+def spacecraft_nonlinear_problem(solver=SOLVER_IPDDP, horizon=40, constrained=True, integrator=None):
+    """Nonlinear relative motion in canonical units (mu = 1, circular reference orbit of radius 1, mass 1; state [p, v, r0, theta, dr0,
+    dtheta]): null a small offset from the reference orbit, acceleration box +-0.3.  The four orbit states carry no cost.  No full DDP:
+    use_ilqr = 0 is refused for this plant."""
+    o = default_options(); o.max_iterations = 40; o.tolerance = 1e-4; o.acceptable_tolerance = 1e-6
+    dt = 0.05
+    p = Problem(solver, MODEL_SPACECRAFT_NONLINEAR, RK4 if integrator is None else integrator, 10, 3, horizon, dt, np.zeros((10, 10)), 0.1 * np.eye(3),
+                np.diag([100.0] * 6 + [0.0] * 4), np.array([0.0] * 6 + [1.0, 0.0, 0.0, 1.0]), model_params=[1.0, 1.0, 1.0, 1.0], options=o)
+    if constrained:
+        p.add_control_box("ControlConstraint", -0.3 * np.ones(3), 0.3 * np.ones(3))
+    p.x0 = np.array([0.02, -0.01, 0.01, 0.0, 0.01, 0.0, 1.0, 0.0, 0.0, 1.0])
     return p
 
 

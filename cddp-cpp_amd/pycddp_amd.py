@@ -291,6 +291,28 @@ class SpacecraftLanding2D(_BuiltinPlant):   # bind_dynamics.cpp:218-225; state [
         self.params = [mass, length, width, min_thrust, max_thrust, max_gimble]
 
 
+class Forklift(_BuiltinPlant):      # bind_dynamics.cpp:164-170; a discrete plant (forklift.cpp:17-48): state [x, y, theta, v, delta], control [a, ddelta]
+    def __init__(self, timestep=0.01, wheelbase=2.0, integration_type="euler", rear_steer=True, max_steering_angle=0.785398):
+        self.model = _api().MODEL_FORKLIFT
+        super().__init__(5, 2, timestep, integration_type)
+        self.params = [float(wheelbase), 1.0 if rear_steer else 0.0, float(max_steering_angle)]   # (the library fills the timestep in)
+
+
+class QuadrotorRate(_BuiltinPlant):   # bind_dynamics.cpp:184-187: state [p, v, qw, qx, qy, qz], control [thrust, wx, wy, wz]
+    def __init__(self, timestep, mass, max_thrust, max_rate, integration_type="euler"):
+        for v, msg in ((mass, "Mass must be positive"), (max_thrust, "Maximum thrust must be positive"), (max_rate, "Maximum angular rate must be positive")):
+            if not v > 0.0:
+                raise ValueError(msg)        # quadrotor_rate.cpp:28-36 (std::invalid_argument -> ValueError in the binding)
+        self.model = _api().MODEL_QUADROTOR_RATE
+        super().__init__(10, 4, timestep, integration_type); self.params = [float(mass), float(max_thrust), float(max_rate)]
+
+
+class SpacecraftNonlinear(_BuiltinPlant):   # bind_dynamics.cpp:205-210: state [p, v, r0, theta, dr0, dtheta], control [ux, uy, uz]
+    def __init__(self, timestep, integration_type="rk4", mass=1.0, r_scale=1.0, v_scale=1.0, mu=1.0):
+        self.model = _api().MODEL_SPACECRAFT_NONLINEAR
+        super().__init__(10, 3, timestep, integration_type); self.params = [float(mass), float(r_scale), float(v_scale), float(mu)]
+
+
 class Manipulator(_BuiltinPlant):  # :189-191
     def __init__(self, timestep, integration_type="rk4"):
         self.model = _api().MODEL_MANIPULATOR
@@ -317,8 +339,9 @@ class LTISystem(DynamicalSystem):   # :233-237
     def get_cross_hessian(self, state, control, time=0.0): return [np.zeros((self.control_dim, self.state_dim))] * self.state_dim
 
 
-# ------------------------------------------------------------------------------------------------ objective / constraints
-# ---- plants without device kernels: evaluated on the host and solved through the plug-in route (GPU backward passes, host rollouts)
+# ---- plants that also keep a numpy restatement on the host (get_continuous_dynamics and the Jacobians below).  They are built-in plants
+# like the ones above (`model` id + `params`: the resident route); a Python subclass that sets `model = None` runs through the plug-in
+# route on the numpy methods (GPU backward passes, host rollouts).
 def _fd_jacobian(f, x, h=2e-5):     # helper.hpp:95-119 (finite_difference_jacobian, central differences)
     x = np.asarray(x, dtype=np.float64); xp = x.copy(); cols = []
     for i in range(x.size):
@@ -329,15 +352,25 @@ def _fd_jacobian(f, x, h=2e-5):     # helper.hpp:95-119 (finite_difference_jacob
 
 
 class _HostPlant(DynamicalSystem):
-    """A plant of the reference restated on the host only (model None: no kernels).  Zero Hessian blocks unless the subclass has some."""
+    """A plant of the reference with kernels (`_id`: the cddp_hip_model name) and a numpy restatement of its continuous dynamics and
+    Jacobians.  Zero Hessian blocks unless the subclass has some.  `model` is a class-level property and not an instance attribute on
+    purpose: a Python subclass that declares `model = None` shadows it and becomes a host plant (plug-in route on the numpy methods).
+    The numpy methods need nothing but numpy; the Hessians of Acrobot and Usv3Dof (_eval_hess) need the native library loaded."""
+    _id = None
+    model = property(lambda self: None if self._id is None else getattr(_api(), self._id))
+    def _eval_hess(self, state, control, which):   # the library's host build of the kernels' plant (cddp_hip_model_eval)
+        api = _api()
+        return list(api.model_eval(self.model, _INTEGRATORS[self.integration_type], self.timestep, self.params, self.state_dim, self.control_dim,
+                                   state, control, want=("hess",))["hess"][which])
     def get_state_hessian(self, state, control, time=0.0): return [np.zeros((self.state_dim, self.state_dim)) for _ in range(self.state_dim)]
     def get_control_hessian(self, state, control, time=0.0): return [np.zeros((self.control_dim, self.control_dim)) for _ in range(self.state_dim)]
     def get_cross_hessian(self, state, control, time=0.0): return [np.zeros((self.control_dim, self.state_dim)) for _ in range(self.state_dim)]
 
 
 class DubinsCar(_HostPlant):        # dubins_car.cpp:24-141 / bind_dynamics.cpp:160-162: state [x, y, theta], control [omega], constant speed
+    _id = "MODEL_DUBINS_CAR"
     def __init__(self, speed, timestep, integration_type="euler"):
-        super().__init__(3, 1, timestep, integration_type); self.speed = float(speed)
+        super().__init__(3, 1, timestep, integration_type); self.speed = float(speed); self.params = [self.speed]
     def get_continuous_dynamics(self, state, control, time=0.0):
         return np.array([self.speed * np.cos(state[2]), self.speed * np.sin(state[2]), control[0]])
     def get_state_jacobian(self, state, control, time=0.0):
@@ -349,9 +382,11 @@ class DubinsCar(_HostPlant):        # dubins_car.cpp:24-141 / bind_dynamics.cpp:
 
 
 class DreyfusRocket(_HostPlant):    # dreyfus_rocket.cpp:24-83 / bind_dynamics.cpp:212-216: state [x, x_dot], control [theta]
+    _id = "MODEL_DREYFUS_ROCKET"
     def __init__(self, timestep, integration_type="rk4", thrust_acceleration=64.0, gravity_acceleration=32.0):
         super().__init__(2, 1, timestep, integration_type)
         self.thrust_acceleration, self.gravity_acceleration = float(thrust_acceleration), float(gravity_acceleration)
+        self.params = [self.thrust_acceleration, self.gravity_acceleration]
     def get_thrust_acceleration(self): return self.thrust_acceleration
     def get_gravity_acceleration(self): return self.gravity_acceleration
     def get_continuous_dynamics(self, state, control, time=0.0):
@@ -375,8 +410,10 @@ class Acrobot(_HostPlant):          # acrobot.cpp:24-96 / bind_dynamics.cpp:172-
     """The reference differentiates its autodiff twin of the same expressions (dynamical_system.cpp: getStateJacobian by forward
     duals); here the Jacobians are complex-step derivatives of the one restatement below -- equal to the dual-number values to rounding."""
     gravity, friction = 9.81, 1.0     # acrobot.hpp:138-139
+    _id = "MODEL_ACROBOT"
     def __init__(self, timestep, l1=1.0, l2=1.0, m1=1.0, m2=1.0, J1=1.0, J2=1.0, integration_type="euler"):
         super().__init__(4, 1, timestep, integration_type); self.l1, self.l2, self.m1, self.m2, self.J1, self.J2 = l1, l2, m1, m2, J1, J2
+        self.params = [float(v) for v in (l1, l2, m1, m2, J1, J2)]
     def _f(self, s, c):
         l1, l2, m1, m2, J1, J2 = self.l1, self.l2, self.m1, self.m2, self.J1, self.J2
         th1, th2, w1, w2 = s[0], s[1], s[2], s[3]
@@ -396,9 +433,10 @@ class Acrobot(_HostPlant):          # acrobot.cpp:24-96 / bind_dynamics.cpp:172-
         return _cs_jacobian(lambda s: self._f(s, np.asarray(control, dtype=np.complex128)), state)
     def get_control_jacobian(self, state, control, time=0.0):
         return _cs_jacobian(lambda c: self._f(np.asarray(state, dtype=np.complex128), c), control)
-    def _no_hessian(self, *a, **k):
-        raise NotImplementedError("Acrobot: second derivatives are not restated (the reference takes them from autodiff); use_ilqr = True")
-    get_state_hessian = get_control_hessian = get_cross_hessian = _no_hessian
+    # second derivatives: autodiff in the reference; here the library's second-order duals on the kernels' expression
+    def get_state_hessian(self, state, control, time=0.0): return self._eval_hess(state, control, 0)
+    def get_control_hessian(self, state, control, time=0.0): return self._eval_hess(state, control, 1)
+    def get_cross_hessian(self, state, control, time=0.0): return self._eval_hess(state, control, 2)
 
 
 def _inv3_cofactor(M):              # Eigen's fixed 3 x 3 inverse: cofactors times 1 / det
@@ -410,9 +448,11 @@ def _inv3_cofactor(M):              # Eigen's fixed 3 x 3 inverse: cofactors tim
 
 class Usv3Dof(_HostPlant):          # usv_3dof.cpp:11-110 / bind_dynamics.cpp: state [x, y, psi, u, v, r], control [tau_u, tau_v, tau_r]
     """Generic surface-vessel parameters of the reference (:17-34).  Jacobians: complex-step derivatives of the restated dynamics (the
-    reference writes the same derivatives out by hand, :152-227); the control Hessian is zero (:237-248), the others are not restated."""
+    reference writes the same derivatives out by hand, :152-227); the control Hessian is zero (:237-248), the state and cross Hessians
+    (autodiff in the reference) come from the library's second-order duals on the kernels' expression."""
+    _id = "MODEL_USV_3DOF"
     def __init__(self, timestep, integration_type="euler"):
-        super().__init__(6, 3, timestep, integration_type)
+        super().__init__(6, 3, timestep, integration_type)     # (no parameters: the library fills the vessel's block itself)
         self.m, self.Iz = 100.0, 10.0
         self.X_udot, self.Y_vdot, self.Y_rdot, self.N_vdot, self.N_rdot = -10.0, -50.0, -5.0, -5.0, -5.0
         self.X_u, self.Y_v, self.Y_r, self.N_v, self.N_r = -20.0, -100.0, 0.0, 0.0, -20.0
@@ -433,17 +473,18 @@ class Usv3Dof(_HostPlant):          # usv_3dof.cpp:11-110 / bind_dynamics.cpp: s
         return _cs_jacobian(lambda s: self._f(s, np.asarray(control, dtype=np.complex128)), state)
     def get_control_jacobian(self, state, control, time=0.0):
         return _cs_jacobian(lambda c: self._f(np.asarray(state, dtype=np.complex128), c), control)
-    def _no_hessian(self, *a, **k):
-        raise NotImplementedError("Usv3Dof: state / cross second derivatives are not restated (autodiff in the reference); use_ilqr = True")
-    get_state_hessian = get_cross_hessian = _no_hessian
+    def get_state_hessian(self, state, control, time=0.0): return self._eval_hess(state, control, 0)
+    def get_cross_hessian(self, state, control, time=0.0): return self._eval_hess(state, control, 2)
 
 
 class SpacecraftLinearFuel(_HostPlant):   # spacecraft_linear_fuel.cpp:29-158 / bind_dynamics.cpp:199-203
     """HCW relative motion with mass: state [x, y, z, vx, vy, vz, mass, accumulated control effort], control [Fx, Fy, Fz]; the
     reference's Jacobians are central finite differences of the continuous dynamics (:124-141), its Hessians zero (:144-158)."""
+    _id = "MODEL_SPACECRAFT_LINEAR_FUEL"
     def __init__(self, timestep, mean_motion, isp, g0=9.80665, integration_type="euler"):
         super().__init__(8, 3, timestep, integration_type)
         self.mean_motion, self.isp, self.g0, self.epsilon = float(mean_motion), float(isp), float(g0), 1e-8
+        self.params = [self.mean_motion, self.isp, self.g0]
     def get_continuous_dynamics(self, state, control, time=0.0):
         x, y, z, vx, vy, vz, mass = (state[i] for i in range(7)); Fx, Fy, Fz = control[0], control[1], control[2]
         n = self.mean_motion; n2 = n * n
@@ -456,6 +497,7 @@ class SpacecraftLinearFuel(_HostPlant):   # spacecraft_linear_fuel.cpp:29-158 / 
         return _fd_jacobian(lambda c: self.get_continuous_dynamics(state, c, time), control)
 
 
+# ------------------------------------------------------------------------------------------------ objective / constraints
 class Objective:                    # objective.hpp:30-120 / bind_objective.cpp:34-45: bound WITHOUT a constructor
     def __init__(self, *args, **kwargs):
         # pybind11's message for a class bound without py::init; Python-defined objectives derive from NonlinearObjective (:62-63)

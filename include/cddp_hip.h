@@ -43,7 +43,8 @@ extern "C" {
 /* Built-in plants with device-side dynamics + derivatives
  * (reference src/dynamics_model/{pendulum,cartpole,unicycle,lti_system,quadrotor,
  *  manipulator,bicycle,car,spacecraft_linear,euler_attitude,quaternion_attitude,mrp_attitude,
- *  spacecraft_twobody,spacecraft_landing2d}.cpp).  model_params layout is documented per entry. */
+ *  spacecraft_twobody,spacecraft_landing2d,dubins_car,dreyfus_rocket,acrobot,usv_3dof,forklift,
+ *  quadrotor_rate,spacecraft_linear_fuel,spacecraft_nonlinear}.cpp).  model_params layout is documented per entry. */
 enum cddp_hip_model {
   CDDP_HIP_MODEL_PENDULUM = 0,   /* params: length, mass, damping, gravity                     */
   CDDP_HIP_MODEL_CARTPOLE = 1,   /* params: cart_mass, pole_mass, pole_length, gravity, damping */
@@ -66,9 +67,29 @@ enum cddp_hip_model {
   CDDP_HIP_MODEL_SPACECRAFT_TWOBODY = 14,  /* nx=6 [x,y,z,vx,vy,vz] / [ux,uy,uz] point mass about a central body
                                               (spacecraft_twobody.cpp); params: mu, mass.  Central-FD Jacobians; no full DDP
                                               (use_ilqr = 0 is refused: the reference's cross Hessian throws)               */
-  CDDP_HIP_MODEL_SPACECRAFT_LANDING2D = 15 /* nx=6 [x,x_dot,y,y_dot,theta,theta_dot] / [thrust fraction, gimbal angle]
+  CDDP_HIP_MODEL_SPACECRAFT_LANDING2D = 15,/* nx=6 [x,x_dot,y,y_dot,theta,theta_dot] / [thrust fraction, gimbal angle]
                                               (spacecraft_landing2d.cpp); params: mass, length, width, min_thrust,
                                               max_thrust, max_gimble (gravity 9.81, inertia mass * length^2 / 12)          */
+  CDDP_HIP_MODEL_DUBINS_CAR = 16,          /* nx=3 [x,y,theta] / [omega], constant speed (dubins_car.cpp); params: speed       */
+  CDDP_HIP_MODEL_DREYFUS_ROCKET = 17,      /* nx=2 [x,x_dot] / [theta] (dreyfus_rocket.cpp); params: thrust_acceleration,
+                                              gravity_acceleration                                                            */
+  CDDP_HIP_MODEL_ACROBOT = 18,             /* nx=4 [theta1,theta2,theta1_dot,theta2_dot] / [torque] (acrobot.cpp); params: l1, l2,
+                                              m1, m2, J1, J2 (gravity 9.81 and friction 1.0 are fixed); autodiff derivatives      */
+  CDDP_HIP_MODEL_USV_3DOF = 19,            /* nx=6 [x,y,psi,u,v,r] / [tau_u,tau_v,tau_r] surface vessel (usv_3dof.cpp); params:
+                                              none from the caller.  The library fills [0..8] = M^-1, [9..17] = D_L (row-major),
+                                              [18..20] = m_x, m_y, m_yr of the reference's fixed vessel                          */
+  CDDP_HIP_MODEL_FORKLIFT = 20,            /* DISCRETE nx=5 [x,y,theta,v,delta] / [a, steering rate] (forklift.cpp, h = dt; the
+                                              integrator is ignored); params: wheelbase, rear_steer (0 / 1), max_steering_angle
+                                              (carried, unused by the dynamics); the library fills [3] = dt                     */
+  CDDP_HIP_MODEL_QUADROTOR_RATE = 21,      /* nx=10 [px,py,pz,vx,vy,vz,qw,qx,qy,qz] / [thrust,wx,wy,wz] (quadrotor_rate.cpp); params: mass,
+                                              max_thrust, max_rate (each must be positive; the last two are carried, unused by the
+                                              dynamics); gravity 9.81; autodiff derivatives through the quaternion normalisation   */
+  CDDP_HIP_MODEL_SPACECRAFT_LINEAR_FUEL = 22,/* nx=8 [x,y,z,vx,vy,vz,mass,accumulated control effort] / [Fx,Fy,Fz]
+                                              (spacecraft_linear_fuel.cpp); params: mean_motion, isp, g0 (epsilon 1e-8 under the
+                                              thrust norm is fixed).  Central-FD Jacobians; all Hessians are zero                */
+  CDDP_HIP_MODEL_SPACECRAFT_NONLINEAR = 23 /* nx=10 [px,py,pz,vx,vy,vz,r0,theta,dr0,dtheta] / [ux,uy,uz] (spacecraft_nonlinear.cpp); params:
+                                              mass, r_scale, v_scale (carried, unused by the dynamics), mu.  Central-FD Jacobians; no full
+                                              DDP (use_ilqr = 0 is refused: the reference's cross Hessian throws)                  */
 };
 
 /* reference src/cddp_core/dynamical_system.cpp:28-83 */

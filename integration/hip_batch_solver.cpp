@@ -30,20 +30,28 @@
 #include "cddp_core/objective.hpp"
 #include "cddp_core/options.hpp"
 #include "cddp_core/terminal_constraint.hpp"
+#include "dynamics_model/acrobot.hpp"
 #include "dynamics_model/bicycle.hpp"
 #include "dynamics_model/car.hpp"
 #include "dynamics_model/cartpole.hpp"
+#include "dynamics_model/dreyfus_rocket.hpp"
+#include "dynamics_model/dubins_car.hpp"
 #include "dynamics_model/euler_attitude.hpp"
+#include "dynamics_model/forklift.hpp"
 #include "dynamics_model/lti_system.hpp"
 #include "dynamics_model/manipulator.hpp"
 #include "dynamics_model/mrp_attitude.hpp"
 #include "dynamics_model/pendulum.hpp"
 #include "dynamics_model/quadrotor.hpp"
+#include "dynamics_model/quadrotor_rate.hpp"
 #include "dynamics_model/quaternion_attitude.hpp"
 #include "dynamics_model/spacecraft_landing2d.hpp"
 #include "dynamics_model/spacecraft_linear.hpp"
+#include "dynamics_model/spacecraft_linear_fuel.hpp"
+#include "dynamics_model/spacecraft_nonlinear.hpp"
 #include "dynamics_model/spacecraft_twobody.hpp"
 #include "dynamics_model/unicycle.hpp"
+#include "dynamics_model/usv_3dof.hpp"
 
 #include "cddp_hip.h"   // this repository: include/cddp_hip.h
 
@@ -118,6 +126,8 @@ int integratorId(const std::string &s) {
 // its dynamics.  Quadrotor / Car / Bicycle / HCW keep their parameters private without accessors in the reference as it stands
 // (quadrotor.hpp:122-124, car.hpp:125, bicycle.hpp:102, spacecraft_linear.hpp:113-114): with integration/reference_getters.patch applied
 // (five one-line getters) define CDDP_HIP_REFERENCE_HAS_GETTERS and they go resident too; without it they take the plug-in route.
+// Likewise DubinsCar, Forklift, SpacecraftLinearFuel and SpacecraftNonlinear (the same patch); DreyfusRocket, Acrobot and QuadrotorRate
+// have public getters, Usv3Dof has no parameters.
 struct ModelDesc {
   int id = -1;
   std::vector<double> params;
@@ -148,6 +158,23 @@ bool describeModel(const DynamicalSystem &s, ModelDesc &m) {
     m.params = {p.getMass(), p.getLength(), p.getWidth(), p.getMinThrust(), p.getMaxThrust(), p.getMaxGimble()};
     return true;
   }
+  if (typeid(s) == typeid(DreyfusRocket)) {   // public getters (dreyfus_rocket.hpp:106-107)
+    const auto &p = static_cast<const DreyfusRocket &>(s);
+    m.id = CDDP_HIP_MODEL_DREYFUS_ROCKET; m.params = {p.getThrustAcceleration(), p.getGravityAcceleration()};
+    return true;
+  }
+  if (typeid(s) == typeid(Acrobot)) {   // public getters (acrobot.hpp:114-121); the device form holds the header's gravity and friction
+    const auto &p = static_cast<const Acrobot &>(s);
+    if (p.getGravity() != 9.81 || p.getFriction() != 1.0) return false;
+    m.id = CDDP_HIP_MODEL_ACROBOT; m.params = {p.getL1(), p.getL2(), p.getM1(), p.getM2(), p.getJ1(), p.getJ2()};
+    return true;
+  }
+  if (typeid(s) == typeid(QuadrotorRate)) {   // public getters (quadrotor_rate.hpp:130-132)
+    const auto &p = static_cast<const QuadrotorRate &>(s);
+    m.id = CDDP_HIP_MODEL_QUADROTOR_RATE; m.params = {p.getMass(), p.getMaxThrust(), p.getMaxRate()};
+    return true;
+  }
+  if (typeid(s) == typeid(Usv3Dof)) { m.id = CDDP_HIP_MODEL_USV_3DOF; return true; }   // no parameters: the vessel is fixed in the constructor (usv_3dof.cpp:17-48)
 #ifdef CDDP_HIP_REFERENCE_HAS_GETTERS
   if (typeid(s) == typeid(Quadrotor)) {
     const auto &p = static_cast<const Quadrotor &>(s);
@@ -173,6 +200,22 @@ bool describeModel(const DynamicalSystem &s, ModelDesc &m) {
   if (typeid(s) == typeid(SpacecraftTwobody)) {
     const auto &p = static_cast<const SpacecraftTwobody &>(s);
     m.id = CDDP_HIP_MODEL_SPACECRAFT_TWOBODY; m.params = {p.getMu(), p.getMass()};
+    return true;
+  }
+  if (typeid(s) == typeid(DubinsCar)) { m.id = CDDP_HIP_MODEL_DUBINS_CAR; m.params = {static_cast<const DubinsCar &>(s).getSpeed()}; return true; }
+  if (typeid(s) == typeid(Forklift)) {
+    const auto &p = static_cast<const Forklift &>(s);
+    m.id = CDDP_HIP_MODEL_FORKLIFT; m.params = {p.getWheelbase(), p.getRearSteer() ? 1.0 : 0.0, p.getMaxSteeringAngle()};
+    return true;
+  }
+  if (typeid(s) == typeid(SpacecraftNonlinear)) {
+    const auto &p = static_cast<const SpacecraftNonlinear &>(s);
+    m.id = CDDP_HIP_MODEL_SPACECRAFT_NONLINEAR; m.params = {p.getMass(), p.getRScale(), p.getVScale(), p.getMu()};
+    return true;
+  }
+  if (typeid(s) == typeid(SpacecraftLinearFuel)) {
+    const auto &p = static_cast<const SpacecraftLinearFuel &>(s);
+    m.id = CDDP_HIP_MODEL_SPACECRAFT_LINEAR_FUEL; m.params = {p.getMeanMotion(), p.getIsp(), p.getG0()};
     return true;
   }
 #endif
