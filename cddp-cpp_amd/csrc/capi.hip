@@ -130,6 +130,13 @@ struct Inner {
   double *d_head = nullptr, *h_head = nullptr; size_t head_cap = 0;   // cddp_hip_get_plan_head staging (device, pinned host)
   int *h_poll = nullptr;                         // pinned host words of the solve loop's polls, two slots of kPollWords: [0] running count, [1..] alpha histogram
   std::map<unsigned long long, hipGraphExec_t> graphs;   // CDDP_HIP_GRAPH=1: captured iteration windows by (ladder shape, length, last flag)
+  // shadow costate (K4b deferred into the next sweep launch; SolveRun::enqueue_iteration, kernels_lean.hpp "K4b, deferred")
+  bool shadow_bufs = false;      // the second value stack and the accept records are allocated (layout eligible at create)
+  int cs_epoch = 0;              // stamps handed out: two per enqueued outer iteration over the handle's life (SolveRun::enqueue_iteration)
+  int n_redo = 0;                // speculative solves discarded and run again with K4b on the chain (cddp_hip_costate_redos)
+  bool last_shadow = false;      // the last solve ran (and kept) the shadow schedule (cddp_hip_costate_mode)
+  bool ever_solved = false;
+  int *h_bad = nullptr;          // pinned host copy of DevBuf::cs_bad
 };
 
 namespace {
@@ -455,6 +462,32 @@ static int in_destroy(Inner *h);
 // the kernel route of a group (launch.hpp::Route): fixed by the switches read at create, the solver, the buffers and use_ilqr
 static void resolve_route(Inner *h) { h->route = h->ks->route(h->d, h->P.solver, *h->knob); h->d.t4 = h->route.t4; }
 
+// Shadow costate: the layouts whose K4b can leave the iteration's chain -- IPDDP with path rows on the role-split cooperative sweep, no
+// terminal set, Gauss-Newton, first-success rule (nothing reads Lambda during such a solve).  Not with the costate test hook (it needs
+// flag 2 on the chain) and not with captured windows (the value stack's parity would have to enter the graph key).
+static bool shadow_layout(const Inner *h) {
+  return h->P.solver == CDDP_HIP_SOLVER_IPDDP && h->P.m > 0 && h->P.n_term == 0 && !h->d.ddp && h->route.sweep == Route::kCoop && h->route.roles_nh > 0 &&
+         h->ks->shadow_extra(h->d, h->route) > 0;
+}
+// ... and the solves that may take it: the solve must be restartable from the device-resident initial trajectory (cold, or the "provided
+// trajectory" warm start; an "existing solver state" warm solve consumes state the solve itself overwrites, so it keeps K4b on the chain).
+// COSTATE unset: only where the sweep launch puts at most ONE workgroup on every CU of the group's share of the chip (conc groups in flight
+// share it).  The extra blocks are workgroups of the sweep kernel and carry its static LDS (53.6 - 57.2 KB), of which a CU holds two: beside
+// one sweep workgroup per CU they run under the sweep (C2: 128 sweep workgroups on 128 CUs, measured faster, profiles/r09_costate_shadow.md);
+// where the sweep already fills both places (C3 at its bench batch) they could only start as sweep workgroups finish, i.e. behind the sweep
+// -- that shape stays on the chain unless CDDP_HIP_COSTATE=shadow asks for it.
+static bool shadow_eligible(const Inner *h, int conc) {
+  if (!h->shadow_bufs || !shadow_layout(h)) return false;
+  if (h->knob->costate == Knobs::kCostateAuto) {
+    const int own = h->ks->shadow_extra(h->d, h->route) > 0 ? h->ks->sweep_blocks(h->d) : 0;
+    if (own <= 0 || own > device_cu_count(h->device) / std::max(1, conc)) return false;
+  }
+  if (h->knob->costate == Knobs::kCostateSync || h->knob->fail_costate != 0 || h->knob->graph) return false;
+  if (h->P.ls_rule != CDDP_HIP_LS_FIRST_SUCCESS) return false;
+  if (h->P.opt.warm_start && h->has_state) return false;
+  return true;
+}
+
 static int in_create(const cddp_hip_problem *problem, int batch, int device, const Knobs &knob, const CuSpec *cu, Inner **out) {
   if (!problem || !out) return fail(-1, "null argument");
   if (batch <= 0) return fail(-1, "batch must be positive");
@@ -588,6 +621,15 @@ static int in_create(const cddp_hip_problem *problem, int batch, int device, con
   d.P = h->dP;
   d.launched = h->d_launched;
   resolve_route(h);
+  if (shadow_layout(h) && knob.costate != Knobs::kCostateSync && !knob.fail_costate && !knob.graph) {
+#define DA(ptr, n) do { int rc_ = dalloc(h, &(ptr), (size_t)(n)); if (rc_) { in_destroy(h); return rc_; } } while (0)
+    DA(d.Vx2, (size_t)(N + 1) * nx * Bp); DA(d.Vxx2, (size_t)(N + 1) * nx * nx * Bp);
+    DA(d.cs_stampv, Bp); DA(d.cs_old, Bp); DA(d.cs_new, Bp); DA(d.cs_apr, Bp); DA(d.cs_vbuf, Bp); DA(d.cs_bad, 1);
+#undef DA
+    if (hipHostMalloc((void **)&h->h_bad, sizeof(int)) != hipSuccess) { const int rc_ = fail(-10, "hipHostMalloc failed"); in_destroy(h); return rc_; }
+    *h->h_bad = 0;
+    h->shadow_bufs = true;
+  }
   e = hipStreamSynchronize(h->stream);
   if (e != hipSuccess) { const int rc_ = fail(-10, "device initialisation failed: %s", hipGetErrorString(e)); in_destroy(h); return rc_; }
   *out = h;
@@ -607,6 +649,7 @@ static int in_destroy(Inner *h) {
   if (h->ev_poll) hipEventDestroy(h->ev_poll);
   if (h->ev_poll2) hipEventDestroy(h->ev_poll2);
   if (h->h_poll) hipHostFree(h->h_poll);
+  if (h->h_bad) hipHostFree(h->h_bad);
   if (h->d_head) hipFree(h->d_head);
   if (h->h_head) hipHostFree(h->h_head);
   if (h->own_stream && h->stream) hipStreamDestroy(h->stream);
@@ -882,6 +925,9 @@ struct SolveRun {
   int launches = 0, outer = 0, it = 0, max_it = 0, na = 0;
   bool two_stage_marks = false, first_rule = true, pinned = false, one_stage = true, done = false, cpu_time_hit = false, use_graph = false;
   int k1 = 1, k_cap = 1, k_cap2 = 1;
+  // shadow costate: K4b of an iteration rides in the next sweep launch (Inner::shadow_bufs); force_sync: the re-run of a discarded solve
+  bool shadow = false, force_sync = false, pre_has_state = false, redo_needed = false;
+  int stamp0 = 0;                   // the handle's stamp count when the solve began (outer iteration i carries stamp0 + 2 i and + 1)
   long waves_all = 0, per_alpha_waves = 1, two_stage_max_waves = 768;
   std::vector<int> hist_now, hist_prev;
   // Polls are double-buffered (round 5): behind a poll the host enqueues Knobs::run_ahead more iterations (default 1; none behind the two early polls that settle the ladder shape) BEFORE it waits for
@@ -1009,6 +1055,12 @@ struct SolveRun {
     if (!h->h_poll) HIPCHK(hipHostMalloc((void **)&h->h_poll, sizeof(int) * 2 * kPollWords));
     HIPCHK(hipMemsetAsync(h->d_launched, 0, sizeof(unsigned long long), s));
     HIPCHK(hipEventRecord(h->ev_begin, s));
+    pre_has_state = h->has_state;
+    shadow = !force_sync && shadow_eligible(h, conc) && max_it > 0;
+    redo_needed = false;
+    h->last_shadow = shadow; h->ever_solved = true;
+    if (shadow) HIPCHK(hipMemsetAsync(h->d.cs_bad, 0, sizeof(int), s));
+    stamp0 = h->cs_epoch;
     { int rc = run_initialize(h); if (rc) return rc; }
     launches = 1; outer = 0; it = 0; done = false;
     *h->h_poll = d.B;
@@ -1041,7 +1093,24 @@ struct SolveRun {
   // The kernels of ONE outer iteration (K1 .. K5 in the current ladder shape), enqueued on the group's stream.
   void enqueue_iteration(int last) {
     const ProblemDev &P = h->P;
-    const DevBuf &d = h->d;
+    if (shadow) {
+      // the sweep of this iteration writes the other value stack; its extra blocks read the one the previous sweep wrote
+      DevBuf &hd = h->d;
+      hd.Vx_prev = hd.Vx; hd.Vxx_prev = hd.Vxx;
+      std::swap(hd.Vx, hd.Vx2); std::swap(hd.Vxx, hd.Vxx2);
+      hd.cs_vsel ^= 1;
+    }
+    DevBuf dsh = h->d;   // the launches' copy: the shadow words of this iteration
+    if (shadow) {
+      // Two stamps per outer iteration: cs_epoch (even) for the accepts of stage 1 of a TWO-stage iteration, cs_epoch + 1 for every other
+      // accept.  The first kind cannot wait for the next sweep: the stage-2 rollout's lanes of a trajectory that is no longer in its phase
+      // run along on trial slots taken relative to the NEW current slot (kernels_lean.hpp, k_forward_ipddp_pc), one of which may be the
+      // slot the accepted step left -- whose x rows the costate needs.  Those rows are evaluated between update 1 and rollout 2.
+      h->cs_epoch += 2;
+      dsh.cs_mode = 1; dsh.cs_stamp = h->cs_epoch + 1; dsh.cs_want = dsh.cs_stamp - 2;
+      dsh.cs_fail_stamp = h->knob->fail_shadow > 0 ? stamp0 + 2 * h->knob->fail_shadow + 1 : 0;
+    }
+    const DevBuf &d = dsh;
     hipStream_t s = h->stream;
     const KernelSet *ks = h->ks;
     const Route &r = h->route;
@@ -1053,7 +1122,8 @@ struct SolveRun {
     mark(0);
     ks->derivs(d, r, 0, s);
     tl_sweep_hop = h->cu.sweep ? &h->cu.hop : nullptr;
-    ks->backward(d, r, P.solver, 0, 1, s);
+    if (shadow && outer > 1) { dsh.cs_extra = ks->shadow_extra(d, r); ks->backward(dsh, r, P.solver, 0, 1, s); dsh.cs_extra = 0; }   // (the first iteration has nothing pending)
+    else ks->backward(d, r, P.solver, 0, 1, s);
     tl_sweep_hop = nullptr;
     mark(1);
     to_fwd(0);
@@ -1063,15 +1133,22 @@ struct SolveRun {
       if (fwd_done) hipEventRecord(fwd_done, sf);
       from_fwd(1);
       mark(2);
-      ks->costate(d, r, P.solver, 0, na, PH_FWD1, 0, first_rule ? 1 : 2, s);   // best-merit rule: the candidate winner's costate only (k_costate)
+      if (!shadow) ks->costate(d, r, P.solver, 0, na, PH_FWD1, 0, first_rule ? 1 : 2, s);   // best-merit rule: the candidate winner's costate only (k_costate)
       ks->update(d, r, 1, na, last, 1, s);
       mark(3);
-      launches += 4;
+      launches += shadow ? 3 : 4;
     } else {
       ks->forward(d, r, P.solver, 0, k1, PH_FWD1, 0, 1, sf);
       from_fwd(1);
       mark(2);
-      ks->costate(d, r, P.solver, 0, k1, PH_FWD1, 0, 1, s);
+      if (!shadow) ks->costate(d, r, P.solver, 0, k1, PH_FWD1, 0, 1, s);
+      if (shadow) {   // stage-1 accepts of a two-stage iteration: their own stamp, evaluated at once from this sweep's value stack (see above)
+        DevBuf d1 = dsh;
+        d1.cs_stamp = h->cs_epoch;
+        ks->update(d1, r, 1, k1, last, 0, s);
+        d1.cs_want = d1.cs_stamp; d1.Vx_prev = d1.Vx; d1.Vxx_prev = d1.Vxx;
+        ks->shadow_flush(d1, nullptr, s);
+      } else
       ks->update(d, r, 1, k1, last, 0, s);
       mark(3);
       to_fwd(2);
@@ -1079,10 +1156,10 @@ struct SolveRun {
       if (fwd_done) hipEventRecord(fwd_done, sf);
       from_fwd(3);
       mark(4);
-      ks->costate(d, r, P.solver, k1, na - k1, PH_FWD2, 0, 1, s);
+      if (!shadow) ks->costate(d, r, P.solver, k1, na - k1, PH_FWD2, 0, 1, s);
       ks->update(d, r, 2, na, last, 1, s);
       mark(5);
-      launches += 6;
+      launches += shadow ? 5 : 6;
     }
   }
   bool polled_iteration(int i) const { return i % h->knob->poll_every == 0 || i == max_it || (i <= 2 && !pinned); }
@@ -1168,12 +1245,31 @@ struct SolveRun {
     return 0;
   }
 
+  // shadow costate, end of the solve (every exit: converged, max_iterations, max_cpu_time)
+  int flush() {
+    const DevBuf &d = h->d;
+    hipStream_t s = h->stream;
+    if (shadow) {
+      // the rows of the last enqueued iteration's accepts, then the value rows of trajectories whose last sweep wrote the other stack;
+      // the "not finite" word rides behind them and is read after the solve's one synchronisation
+      DevBuf df = h->d, dm = h->d;
+      df.cs_mode = 1; df.cs_want = h->cs_epoch > stamp0 ? h->cs_epoch + 1 : 0; df.Vx_prev = df.Vx; df.Vxx_prev = df.Vxx;
+      df.cs_fail_stamp = h->knob->fail_shadow > 0 ? stamp0 + 2 * h->knob->fail_shadow + 1 : 0;
+      h->ks->shadow_flush(df, &dm, s);
+      launches += df.cs_want > 0 ? 2 : 1;
+      HIPCHK(hipMemsetD32Async((hipDeviceptr_t)d.cs_vbuf, d.cs_vsel, (size_t)d.Bp, s));   // every trajectory's rows are in the current stack now
+      HIPCHK(hipMemcpyAsync(h->h_bad, d.cs_bad, sizeof(int), hipMemcpyDeviceToHost, s));
+    }
+    return 0;
+  }
+
   int finish(cddp_hip_stats *stats) {
     const DevBuf &d = h->d;
     hipStream_t s = h->stream;
     HIPCHK(hipEventRecord(h->ev_end, s));
     HIPCHK(hipStreamSynchronize(s));
     HIPCHK(hipGetLastError());
+    if (shadow && *h->h_bad != 0) { redo_needed = true; return 0; }   // discarded: cddp_hip_solve runs this group again with K4b on the chain
     if (tl_order_error != hipSuccess) {   // a cross-stream ordering call of this solve failed (launch.hpp::order_check): the results may come from racing kernels
       const hipError_t oe = tl_order_error; tl_order_error = hipSuccess;
       return fail(-10, "stream ordering (event record / wait) failed during the solve: %s", hipGetErrorString(oe));
@@ -1500,6 +1596,23 @@ int join_to_user(cddp_hip_handle *h) {
 
 }  // namespace
 
+// the host loop of the groups in flight together (cddp_hip_solve), until none of them has anything left to enqueue or digest
+static int drive_runs(SolveRun *run, int n) {
+  for (;;) {
+    bool any = false;
+    for (int k = 0; k < n; ++k) {
+      SolveRun &r = run[k];
+      const Inner *g = r.h;
+      const int ra = (g->P.opt.max_cpu_time > 0.0 || r.use_graph || r.it < g->knob->poll_every) ? 0 : g->knob->run_ahead;
+      if (!r.done && r.outstanding() == 0) { int rc = r.advance(); if (rc < 0) return rc; r.ran_ahead = false; any = true; }
+      else if (!r.done && r.outstanding() == 1 && ra > 0 && !r.ran_ahead) { int rc = r.advance(ra); if (rc < 0) return rc; r.ran_ahead = true; any = true; }
+      else if (r.outstanding() > 0) { int rc = r.complete_poll(); if (rc) return rc; r.ran_ahead = r.outstanding() > 0; any = true; }
+    }
+    if (!any) break;
+  }
+  return 0;
+}
+
 extern "C" {
 
 int cddp_hip_create(const cddp_hip_problem *problem, int batch, int device, cddp_hip_handle **out) {
@@ -1549,6 +1662,17 @@ int cddp_hip_destroy(cddp_hip_handle *h) {
 }
 
 int cddp_hip_num_groups(cddp_hip_handle *h) { return h ? (int)h->g.size() : -1; }
+int cddp_hip_costate_mode(cddp_hip_handle *h) {
+  if (!h) return -1;
+  for (Inner *q : h->g) if (!(q->ever_solved ? q->last_shadow : shadow_eligible(q, std::max(1, std::min(h->conc, (int)h->g.size()))))) return 0;
+  return 1;
+}
+int cddp_hip_costate_redos(cddp_hip_handle *h) {
+  if (!h) return -1;
+  int n = 0;
+  for (Inner *q : h->g) n += q->n_redo;
+  return n;
+}
 int cddp_hip_concurrency(cddp_hip_handle *h) { return h ? std::max(1, std::min(h->conc, (int)h->g.size())) : -1; }
 
 int cddp_hip_set_timing_detail(cddp_hip_handle *h, int detail) {
@@ -1688,18 +1812,10 @@ int cddp_hip_solve(cddp_hip_handle *h, cddp_hip_stats *stats) {
     // each pass, per group: no poll outstanding -> enqueue iterations up to the next polled one; one outstanding and not yet run
     // ahead -> enqueue Knobs::run_ahead more iterations behind it; otherwise digest the oldest poll.  So a group's queue holds work while
     // the host waits for a poll, and the host never blocks on one group while another has nothing queued
-    for (;;) {
-      bool any = false;
-      for (int k = base; k < top; ++k) {
-        SolveRun &r = run[k];
-        const int ra = (h->g[k]->P.opt.max_cpu_time > 0.0 || r.use_graph || r.it < h->g[k]->knob->poll_every) ? 0 : h->g[k]->knob->run_ahead;
-        if (!r.done && r.outstanding() == 0) { int rc = r.advance(); if (rc < 0) return rc; r.ran_ahead = false; any = true; }
-        else if (!r.done && r.outstanding() == 1 && ra > 0 && !r.ran_ahead) { int rc = r.advance(ra); if (rc < 0) return rc; r.ran_ahead = true; any = true; }
-        else if (r.outstanding() > 0) { int rc = r.complete_poll(); if (rc) return rc; r.ran_ahead = r.outstanding() > 0; any = true; }
-      }
-      if (!any) break;
-    }
+    { int rc = drive_runs(&run[base], top - base);
+      if (rc) { for (int k = 0; k < top; ++k) run[k].flush(); return rc; } }   // (the handle stays usable: pending costate rows and the value stacks are settled first)
   }
+  for (int k = 0; k < ng; ++k) { int rc = run[k].flush(); if (rc) return rc; }
   // whole-handle device time: group 0's stream waits for the other groups' end events, then stamps the end
   std::vector<cddp_hip_stats> gs(ng);
   for (int k = 1; k < ng; ++k) {
@@ -1707,6 +1823,21 @@ int cddp_hip_solve(cddp_hip_handle *h, cddp_hip_stats *stats) {
     HIPCHK(hipStreamWaitEvent(h->g[0]->stream, h->g[k]->ev_end, 0));
   }
   for (int k = 0; k < ng; ++k) { int rc = run[k].finish(stats ? &gs[k] : nullptr); if (rc) return rc; }
+  // Shadow costate: a group whose deferred evaluation met a non-finite row is solved AGAIN, from the initial trajectory the handle keeps on
+  // the device, with K4b on the chain (the serial move-past-the-bad-trial logic of k_update): the result of the unmodified launch sequence.
+  double redo_ms = 0.0;
+  for (int k = 0; k < ng; ++k) {
+    if (!run[k].redo_needed) continue;
+    Inner *q = h->g[k];
+    q->has_state = run[k].pre_has_state;   // the same initialisation mode as the discarded attempt
+    ++q->n_redo;
+    SolveRun rr;
+    rr.force_sync = true;
+    { int rc = rr.begin(q, stats != nullptr, conc); if (rc) return rc; }   // (the same ladder heuristics and host loop as the first attempt)
+    { int rc = drive_runs(&rr, 1); if (rc) return rc; }
+    { int rc = rr.finish(stats ? &gs[k] : nullptr); if (rc) return rc; }
+    if (stats) redo_ms += gs[k].solve_ms;
+  }
   { int rc = join_to_user(h); if (rc) return rc; }
   if (stats) {
     std::memset(stats, 0, sizeof(*stats));
@@ -1716,7 +1847,7 @@ int cddp_hip_solve(cddp_hip_handle *h, cddp_hip_stats *stats) {
     // 0's begin is the earliest up to the few microseconds of its own enqueue
     hipEventElapsedTime(&span_ms, h->g[0]->ev_begin, h->g[0]->ev_end);
     (void)first_begin_off;
-    stats->solve_ms = span_ms;
+    stats->solve_ms = span_ms + redo_ms;
     for (int k = 0; k < ng; ++k) {
       // class times: groups that run concurrently overlap in wall time, so their per-class event spans are averaged over the
       // `conc` groups in flight together; successive chunks add up

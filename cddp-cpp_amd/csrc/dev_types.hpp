@@ -108,6 +108,20 @@ struct DevBuf {
   int ladder_sorted;                       // the line-search ladder is strictly decreasing (what cddp_hip_build_alphas makes): the MSIPDDP rollout's dual step search probes only the two ends of the accepted interval
   double *ms_res;                          // [3][Bp] of the CURRENT iterate (mu-independent, kept for resetBarrierFilter): max |g + s|, max |F_t - x_{t+1}|, the violation sum
   int xcd_map;                             // cooperative sweeps: groups of one 64-trajectory tile on one XCD (kernels_coop.hpp::coop_group); CDDP_HIP_XCD_MAP=0 turns it off
+  // Shadow costate (K4b evaluated by extra workgroups of the NEXT role-split sweep, kernels_lean.hpp::costate_shadow_item).  The buffers exist on
+  // the handles whose layout is eligible (capi.hip::in_create), the per-launch words are set on the DevBuf copy a launch is given.
+  double *Vx2, *Vxx2;                      // second value-function stack: the sweeps of successive iterations alternate between (Vx, Vxx) and these
+  const double *Vx_prev, *Vxx_prev;        // per launch: the stack the PREVIOUS sweep wrote (what the deferred costate reads); flush: the current one
+  int *cs_stampv, *cs_old, *cs_new;        // [Bp] k_update's record of the accepted trial: stamp of the outer iteration, slot before, slot after
+  double *cs_apr;                          // [Bp] ... and its primal step size
+  int *cs_vbuf;                            // [Bp] which stack (0 | 1) the trajectory's last sweep wrote (k_value_merge brings stragglers over after a solve)
+  int *cs_bad;                             // one word: a deferred costate row was not finite -- the speculative solve is discarded (capi.hip::SolveRun::finish)
+  int cs_mode;                             // per launch: 1 = shadow scheduling (k_update records instead of reading flag 2; the sweep carries extra blocks)
+  int cs_stamp;                            // per launch: stamp of the outer iteration the launch belongs to (unique over the handle's life, > 0)
+  int cs_want;                             // per launch: the stamp whose accepted trials this launch evaluates (sweep: the previous iteration's, flush: its own)
+  int cs_fail_stamp;                       // TEST HOOK (0 in production; CDDP_HIP_TEST_FAIL_SHADOW=<outer iteration>): evaluating that iteration's stamps reports "not finite"
+  int cs_vsel;                             // which stack (0 | 1) Vx / Vxx are in this launch
+  int cs_extra;                            // per sweep launch: workgroups beyond the sweep's own (they take the deferred costate rows)
 };
 
 }  // namespace cddp_dev

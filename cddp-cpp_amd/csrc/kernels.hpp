@@ -1592,6 +1592,36 @@ DEV void filter_prune(const DevBuf &d, int b) {
   d.filt_n[b] = w;
 }
 
+// One row set of the costate trial, Lambda_new[t] = Lambda[t] + alpha_pr V_x[t] + V_xx[t] (x_new[t] - x[t]) (ipddp_solver.cpp:1613-1616,
+// 1660-1663): THE expressions and their order, shared by k_costate, the deferred evaluation (costate_shadow_item, kernels_lean.hpp)
+// and costate_trial_serial.  vt = the upper triangle of V_xx[t], row by row (V_xx is stored exactly symmetric).  Returns whether every
+// entry is finite.
+template <int NX>
+DEV bool costate_row_eval(const double *lo, const double *vx, const double *vt, const double *xo, const double *xn, const double a_pr, double *lam) {
+  bool finite = true;
+#pragma unroll
+  for (int i = 0; i < NX; ++i) {
+    double s = 0.0;
+#pragma unroll
+    for (int j = 0; j < NX; ++j) {
+      const int lo_ = i < j ? i : j, hi_ = i < j ? j : i;   // V_xx[i][j] from the stored upper triangle
+      s += vt[lo_ * NX - lo_ * (lo_ - 1) / 2 + (hi_ - lo_)] * (xn[j] - xo[j]);
+    }
+    lam[i] = (lo[i] + a_pr * vx[i]) + s;
+    finite = finite && dfinite(lam[i]);
+  }
+  return finite;
+}
+// the upper triangle of V_xx[t] (the rows costate_row_eval takes) from a value stack
+template <int NX>
+DEV void costate_load_triangle(const double *vb, double *vt) {
+  int k = 0;
+#pragma unroll
+  for (int i = 0; i < NX; ++i)
+#pragma unroll
+    for (int j = i; j < NX; ++j) vt[k++] = vb[(size_t)(i * NX + j) * kLS];
+}
+
 // Costate trial of ONE trial, every step, on the lane of trajectory b -- the arithmetic of k_costate (kernels_lean.hpp).
 // Only reached when the first-success rule has to move past a trial whose costate was not finite (k_costate stopped at
 // that trial, so the later candidates have no costate rows yet).  Returns false when this trial's costate is not finite either.
@@ -1601,24 +1631,14 @@ DEV bool costate_trial_serial(const DevBuf &d, int b, int cur, int a) {
   const int slot = (a < cur) ? a : a + 1;   // trial_slot
   const double a_pr = d.t_apr[ti];
   if ((d.fail_costate_mask >> a) & 1) return false;   // test hook (DevBuf::fail_costate_mask)
-  bool finite = true;
   for (int t = 0; t <= d.N; ++t) {
-    double xo[NX], lo[NX], vx[NX], xn[NX], lam[NX];
+    double xo[NX], lo[NX], vx[NX], xn[NX], lam[NX], vt[NX * (NX + 1) / 2];
     ld<NX>(d.X + (size_t)cur * d.planeX + GI(t, NX, 0), kLS, xo);
     ld<NX>(d.Lam + (size_t)cur * d.planeX + GI(t, NX, 0), kLS, lo);
     ld<NX>(d.Vx + GI(t, NX, 0), kLS, vx);
     ld<NX>(d.X + (size_t)slot * d.planeX + GI(t, NX, 0), kLS, xn);
-    const double *vb = d.Vxx + GI(t, NX * NX, 0);
-    for (int i = 0; i < NX; ++i) {
-      double s = 0.0;
-      for (int j = 0; j < NX; ++j) {
-        const int lo_ = i < j ? i : j, hi_ = i < j ? j : i;   // upper triangle, as k_costate reads it
-        s += vb[(size_t)(lo_ * NX + hi_) * kLS] * (xn[j] - xo[j]);
-      }
-      lam[i] = (lo[i] + a_pr * vx[i]) + s;
-      finite = finite && dfinite(lam[i]);
-    }
-    if (!finite) return false;
+    costate_load_triangle<NX>(d.Vxx + GI(t, NX * NX, 0), vt);
+    if (!costate_row_eval<NX>(lo, vx, vt, xo, xn, a_pr, lam)) return false;
     st<NX>(d.Lam + (size_t)slot * d.planeX + GI(t, NX, 0), kLS, lam);
   }
   return true;
@@ -1722,6 +1742,9 @@ __global__ __launch_bounds__(64) void k_update(DevBuf d, const ProblemDev *__res
         d.n_fwd[b] = nf;
         d.n_fwd_steps[b] = ns;
         d.cur[b] = trial_slot(old_cur, win);
+        if (d.cs_mode && ipddp) {   // shadow costate: what the deferred evaluation needs (costate_shadow_item); the stamp makes the record current
+          d.cs_old[b] = old_cur; d.cs_new[b] = trial_slot(old_cur, win); d.cs_apr[b] = w_apr; d.cs_stampv[b] = d.cs_stamp;
+        }
         d.cost[b] = w_cost;
         d.merit[b] = w_merit;
         d.alpha_pr[b] = w_apr;

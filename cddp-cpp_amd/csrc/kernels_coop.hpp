@@ -250,6 +250,14 @@ __global__ __launch_bounds__(64 * (1 + NH)) void k_backward_ipddp_coop(DevBuf d,
     }
   };
   if constexpr (ROLES) {
+    // Shadow costate (kernels_lean.hpp::costate_shadow_item): the blocks beyond the sweep's own (the highest indices, dispatched last)
+    // evaluate the costate rows of the trials accepted in the previous outer iteration, one (tile, step) per wavefront and turn.
+    if (d.cs_extra > 0 && (int)blockIdx.x >= (int)gridDim.x - d.cs_extra) {
+      const int nw = d.cs_extra * (1 + NH), items = d.NB * (N + 1);
+      for (int it = ((int)blockIdx.x - ((int)gridDim.x - d.cs_extra)) * (1 + NH) + wave; it < items; it += nw)
+        costate_shadow_item<NX>(d, (it % d.NB) * 64 + lane, it / d.NB);
+      return;
+    }
     // (this launch replaces k_condense<.., true>, the first kernel of an outer iteration: see k_derivs)
     if (blockIdx.x == 0 && threadIdx.x == 0 && !force) *d.n_active = 0;
     const bool act = (b < d.B) && (force || d.phase[b] == PH_ACTIVE);
@@ -921,6 +929,7 @@ __global__ __launch_bounds__(64 * (1 + NH)) void k_backward_ipddp_coop(DevBuf d,
   d.reg[b] = reg;
   d.n_bwd[b] += nb;
   d.bwd_ok[b] = ok ? 1 : 0;
+  if constexpr (ROLES) { if (d.cs_vbuf) d.cs_vbuf[b] = d.cs_vsel; }   // which value stack this trajectory's last sweep wrote (k_value_merge)
   if constexpr (ROLES) { d.apr_max[b] = apr_cap; d.adu_max[b] = adu_cap; }   // the helpers' minima over the horizon (1.0: no step taken)
   else { d.apr_max[b] = 1.0; d.adu_max[b] = 1.0; }        // K3 lowers them by atomic min
   if (ok) {

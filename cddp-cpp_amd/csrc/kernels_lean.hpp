@@ -627,14 +627,7 @@ __global__ __launch_bounds__(64) void k_costate(DevBuf d, int a0, int na, int ph
   ld<NX>(d.X + (size_t)cur * d.planeX + GI(t, NX, 0), kLS, xo);
   ld<NX>(d.Lam + (size_t)cur * d.planeX + GI(t, NX, 0), kLS, lo);
   ld<NX>(d.Vx + GI(t, NX, 0), kLS, vx);
-  {
-    const double *vb = d.Vxx + GI(t, NX * NX, 0);
-    int k = 0;
-#pragma unroll
-    for (int i = 0; i < NX; ++i)
-#pragma unroll
-      for (int j = i; j < NX; ++j) vt[k++] = vb[(size_t)(i * NX + j) * kLS];
-  }
+  costate_load_triangle<NX>(d.Vxx + GI(t, NX * NX, 0), vt);
   // first_only == 2 (best-merit rule, cddp_solver_base.cpp:264-317): the only costate rows anybody reads are the WINNER's, and
   // the winner is the successful trial of least merit.  Its candidate is picked here exactly as k_update picks it (same order, strict
   // <) among the trials that passed every other test -- flag 1 or 2, so that a block which already sees another block's "costate not
@@ -654,18 +647,7 @@ __global__ __launch_bounds__(64) void k_costate(DevBuf d, int a0, int na, int ph
     const double a_pr = d.t_apr[ti];
     double xn[NX], lam[NX];
     ld<NX>(d.X + (size_t)slot * d.planeX + GI(t, NX, 0), kLS, xn);
-    bool finite = true;
-#pragma unroll
-    for (int i = 0; i < NX; ++i) {
-      double s = 0.0;
-#pragma unroll
-      for (int j = 0; j < NX; ++j) {
-        const int lo_ = i < j ? i : j, hi_ = i < j ? j : i;   // V_xx[i][j] from the stored upper triangle
-        s += vt[lo_ * NX - lo_ * (lo_ - 1) / 2 + (hi_ - lo_)] * (xn[j] - xo[j]);
-      }
-      lam[i] = (lo[i] + a_pr * vx[i]) + s;
-      finite = finite && dfinite(lam[i]);
-    }
+    const bool finite = costate_row_eval<NX>(lo, vx, vt, xo, xn, a_pr, lam);
     // A non-finite costate fails the trial (ipddp_solver.cpp:1613-1616).  The flag value 2 ("passed every other
     // test, costate not finite") is the ONLY mutation of t_success in this grid-wide kernel and is still non-zero:
     // the blocks of the other steps pick the same trial whether or not they have seen it, so the launch is free of
@@ -676,6 +658,51 @@ __global__ __launch_bounds__(64) void k_costate(DevBuf d, int a0, int na, int ph
   }
 }
 
+// ================================================================================ K4b, deferred ("shadow")
+// The same costate trial taken OFF the iteration's chain (capi.hip::SolveRun).  On the layouts of the role-split sweep
+// nothing reads Lambda during a solve and the only thing the iteration needs from K4b is the "not finite" verdict, which a healthy solve
+// never gives.  So k_update accepts the first trial flagged 1 at once and records (old slot, new slot, alpha_pr, stamp of the outer
+// iteration); the rows are evaluated by extra workgroups of the NEXT sweep launch (k_backward_ipddp_coop, blocks beyond the sweep's own),
+// which read the previous sweep's value stack (Vx_prev / Vxx_prev: the sweeps alternate between two stacks) while the sweep writes the
+// other; what is still pending after the last iteration is evaluated by k_costate_flush.  A non-finite row sets *cs_bad: the host then
+// discards the solve and runs it again with K4b on the chain.  One (trajectory, step) per lane; returns nothing.
+template <int NX>
+DEV void costate_shadow_item(const DevBuf &d, const int b, const int t) {
+  if (b >= d.B) return;
+  if (d.cs_stampv[b] != d.cs_want) return;   // no trial accepted in that iteration (irrespective of the phase: a trajectory that converged on the accept still gets its rows)
+  const int cur = d.cs_old[b], slot = d.cs_new[b];
+  const double a_pr = d.cs_apr[b];
+  double xo[NX], lo[NX], vx[NX], xn[NX], lam[NX], vt[NX * (NX + 1) / 2];
+  ld<NX>(d.X + (size_t)cur * d.planeX + GI(t, NX, 0), kLS, xo);
+  ld<NX>(d.Lam + (size_t)cur * d.planeX + GI(t, NX, 0), kLS, lo);
+  ld<NX>(d.Vx_prev + GI(t, NX, 0), kLS, vx);
+  costate_load_triangle<NX>(d.Vxx_prev + GI(t, NX * NX, 0), vt);
+  ld<NX>(d.X + (size_t)slot * d.planeX + GI(t, NX, 0), kLS, xn);
+  const bool finite = costate_row_eval<NX>(lo, vx, vt, xo, xn, a_pr, lam);
+  if (!finite || (d.cs_fail_stamp != 0 && d.cs_fail_stamp == (d.cs_want | 1))) *d.cs_bad = 1;   // (every writer stores the same value)
+  else st<NX>(d.Lam + (size_t)slot * d.planeX + GI(t, NX, 0), kLS, lam);
+}
+
+// what is still pending after the last iteration of a shadow solve (DevBuf::cs_want = its stamp, Vx_prev / Vxx_prev = the last sweep's stack)
+template <class Model>
+__global__ __launch_bounds__(64) void k_costate_flush(DevBuf d) {
+  costate_shadow_item<Model::NX>(d, blockIdx.x * 64 + threadIdx.x, blockIdx.y);
+}
+
+// After a shadow solve: the value rows of the trajectories whose LAST sweep wrote the other stack (they finished on an iteration of the
+// other parity) are brought over, so that Vx / Vxx hold every trajectory's last sweep as they do with one stack.  d.Vx2 / d.Vxx2 = the
+// other stack, d.cs_vsel = the current one.  Grid (tiles, N + 1).  The host then fills cs_vbuf with the current stack's number (a stream
+// operation behind this launch, so that no block of the merge still reads the words).
+template <int NX>
+__global__ __launch_bounds__(64) void k_value_merge(DevBuf d) {
+  const int b = blockIdx.x * 64 + threadIdx.x, t = blockIdx.y;
+  if (b >= d.B || d.cs_vbuf[b] == d.cs_vsel) return;
+  double vx[NX], vxx[NX * NX];
+  ld<NX>(d.Vx2 + GI(t, NX, 0), kLS, vx);
+  ld<NX * NX>(d.Vxx2 + GI(t, NX * NX, 0), kLS, vxx);
+  st<NX>(d.Vx + GI(t, NX, 0), kLS, vx);
+  st<NX * NX>(d.Vxx + GI(t, NX * NX, 0), kLS, vxx);
+}
 // ================================================================================ K4 (two-role)
 // Line-searched IPDDP rollout for path-constrained problems without terminal constraints, as a PRODUCER /
 // CONSUMER pair of wavefronts per (64-trajectory tile, alpha).  Only x_{t+1} = f(x_t, u_t(x_t)) is a true serial

@@ -48,6 +48,11 @@ struct Knobs {
   bool pingpong = env_first("CDDP_HIP_PINGPONG") == '1';         // two groups whose rollouts alternate
   bool xcd_map = env_first("CDDP_HIP_XCD_MAP") != '0';           // XCD_MAP=0: no XCD-aware block -> tile map of the G = 16 sweeps
   int fail_costate = env_num("CDDP_HIP_TEST_FAIL_COSTATE", 0, INT_MIN, INT_MAX);   // test hook: DevBuf::fail_costate_mask
+  // K4b schedule (capi.hip::shadow_eligible): COSTATE=sync: the costate kernel on the iteration's chain everywhere; COSTATE=shadow: deferred
+  // into the next sweep launch on every eligible layout; unset: deferred where the sweep launch leaves a second workgroup place free on its CUs (shadow_eligible)
+  enum Costate { kCostateAuto, kCostateSync, kCostateShadow };
+  int costate = env_is("CDDP_HIP_COSTATE", "sync") ? kCostateSync : env_is("CDDP_HIP_COSTATE", "shadow") ? kCostateShadow : kCostateAuto;
+  int fail_shadow = env_num("CDDP_HIP_TEST_FAIL_SHADOW", 0, 1, INT_MAX);   // test hook: the deferred costate of that outer iteration reports "not finite" (DevBuf::cs_fail_stamp)
 };
 
 }  // namespace cddp_dev

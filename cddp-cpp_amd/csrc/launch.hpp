@@ -1,5 +1,6 @@
 // Host-side launch table: one KernelSet per (plant, constraint layout) instantiation.
 #pragma once
+#include <algorithm>
 #include <vector>
 #include "knobs.hpp"
 #include "kernels_te.hpp"
@@ -61,6 +62,9 @@ struct KernelSet {
   void (*update)(const DevBuf &, const Route &, int stage, int n1, int is_last, int do_count, hipStream_t);
   void (*init)(const DevBuf &, int mode, hipStream_t);
   void (*stage)(const DevBuf &, int copy_xu, int ipddp, hipStream_t);
+  int (*sweep_blocks)(const DevBuf &);                                      // workgroups of the cooperative sweep launch
+  int (*shadow_extra)(const DevBuf &, const Route &);                       // shadow costate: extra workgroups of the sweep launch (0: the layout has no role-split sweep)
+  void (*shadow_flush)(const DevBuf &, const DevBuf *, hipStream_t);        // ... the rows of the stamp DevBuf::cs_want at once (and, end of a solve, the value-stack merge)
   bool logddp_ddp;   // LogDDP with use_ilqr = 0: the plant has explicit Hessian tensors (Model::kHasHess)
   bool has_msipddp;  // the MSIPDDP kernels (kernels_msipddp.hpp) are instantiated for this layout: nx <= 8, no terminal set, and -- with path
                      // constraints -- nu = 1 or nx = nu (the shapes msipddp_solver.cpp:1398 defines)
@@ -262,6 +266,7 @@ struct Launcher {
         } else if (r.roles_nh > 0) {
           if constexpr (kRoles) {
             const hipStream_t ss = sweep_hop_in(s);
+            const dim3 gridC(coop_grid<CoopCfg<Model>::TPW>(d.B, d.xcd_map) + (unsigned)(d.cs_extra > 0 ? d.cs_extra : 0));   // + the shadow costate's blocks (shadow_extra)
             // ring depth: helpers + the block being consumed + one of slack, while two workgroups still fit a CU
             if (r.roles_nh == 1) {
               if constexpr (roles_fit<3>()) hipLaunchKernelGGL((k_backward_ipddp_coop<Model, Cons, 1, 3>), gridC, dim3(128), 0, ss, d, d.P, d.xref_traj, force, count_iter);
@@ -367,6 +372,27 @@ struct Launcher {
     }
     hipLaunchKernelGGL((k_costate<Model>), dim3((d.B + 63) / 64, d.N + 1), dim3(64), 0, s, d, a0, na, phase_req, force, force ? 0 : first_only);
   }
+  // Shadow costate (kernels_lean.hpp, "K4b, deferred"): extra workgroups of a sweep launch -- enough wavefronts to take the (tiles x N + 1)
+  // items in a few turns each, at most two per sweep workgroup (the sweep's LDS lets one of them share a CU with a sweep workgroup);
+  // shadow_flush: the rows still pending after the last iteration, then the value rows of trajectories that finished on the other stack.
+  static int shadow_extra(const DevBuf &d, const Route &r) {
+    if constexpr (kRoles) {
+      if (r.roles_nh <= 0) return 0;
+      const int items = d.NB * (d.N + 1), per = 4 * (1 + r.roles_nh);
+      const int own = (int)coop_grid<CoopCfg<Model>::TPW>(d.B, d.xcd_map);
+      return std::max(1, std::min((items + per - 1) / per, 2 * own));
+    }
+    return 0;
+  }
+  static int sweep_blocks(const DevBuf &d) { return (int)coop_grid<CoopCfg<Model>::TPW>(d.B, d.xcd_map); }   // workgroups of the cooperative sweep launch
+  static void shadow_flush(const DevBuf &d, const DevBuf *dm, hipStream_t s) {   // dm = nullptr: the pending rows only
+    if constexpr (kRoles) {
+      const dim3 grid((d.B + 63) / 64, d.N + 1);
+      if (d.cs_want > 0) hipLaunchKernelGGL((k_costate_flush<Model>), grid, dim3(64), 0, s, d);
+      if (!dm) return;
+      hipLaunchKernelGGL((k_value_merge<Model::NX>), grid, dim3(64), 0, s, *dm);
+    }
+  }
   static void update(const DevBuf &d, const Route &r, int stage, int n1, int is_last, int do_count, hipStream_t s) {
     if (d.lg) {
       if constexpr (kLog) hipLaunchKernelGGL((k_update_logddp<Model, Cons>), gridB(d), dim3(64), 0, s, d, d.P, stage, n1, is_last, do_count);
@@ -398,7 +424,7 @@ struct Launcher {
     KernelSet k;
     k.model = Model::ID; k.nx = Model::NX; k.nu = Model::NU; k.m = Cons::M; k.name = name; k.cst_size = cst_size(); k.te_rec_size = te_rec_size(); k.te_group = CoopCfg<Model>::G;
     k.matches = &matches; k.route = &route; k.derivs = &derivs; k.backward = &backward; k.forward = &forward;
-    k.costate = &costate; k.update = &update; k.init = &init; k.stage = &stage; k.has_logddp = kLog; k.logddp_ddp = Model::kHasHess; k.has_msipddp = kMs; k.ms_cst_size = ms_cst_size();
+    k.costate = &costate; k.update = &update; k.init = &init; k.stage = &stage; k.shadow_extra = &shadow_extra; k.sweep_blocks = &sweep_blocks; k.shadow_flush = &shadow_flush; k.has_logddp = kLog; k.logddp_ddp = Model::kHasHess; k.has_msipddp = kMs; k.ms_cst_size = ms_cst_size();
     return k;
   }
 };

@@ -787,6 +787,7 @@ EXPORTED_SYMBOLS = [
     "cddp_hip_backward_stacks", "cddp_hip_stacks_create_abi", "cddp_hip_stacks_destroy", "cddp_hip_set_stacks", "cddp_hip_set_defect_stack", "cddp_hip_set_control_box", "cddp_hip_set_hessian_stacks", "cddp_hip_set_constraint_stacks",
     "cddp_hip_stacks_backward", "cddp_hip_stacks_last_kernel_ms", "cddp_hip_stacks_last_sweep_form", "cddp_hip_stacks_factor_cache", "cddp_hip_stacks_get_gains", "cddp_hip_stacks_get_constraint_gains",
     "cddp_hip_stacks_get_scalars", "cddp_hip_set_terminal_equality", "cddp_hip_stacks_get_terminal", "cddp_hip_plugin_solve", "cddp_hip_plugin_solve_terminal", "cddp_hip_plugin_set_host_threads", "cddp_hip_plugin_last_stats", "cddp_hip_model_eval", "cddp_hip_set_options", "cddp_hip_set_initial_state", "cddp_hip_forget_solver_state", "cddp_hip_set_duals", "cddp_hip_set_terminal",
+    "cddp_hip_costate_mode", "cddp_hip_costate_redos",
 ]
 
 
@@ -825,6 +826,14 @@ class HipBatchSolver:
     def concurrency(self):
         """Groups cddp_hip_solve keeps in flight at once (2 = the static two-way CU partition of round 5)."""
         return int(self.lib.cddp_hip_concurrency(self.h))
+
+    def costate_mode(self):
+        """1: the last solve (before the first: the next) evaluates the IPDDP costate trial in the shadow of the next sweep launch; 0: on the chain."""
+        return int(self.lib.cddp_hip_costate_mode(self.h))
+
+    def costate_redos(self):
+        """Shadow solves of this handle that were discarded (non-finite deferred costate) and run again on the chain."""
+        return int(self.lib.cddp_hip_costate_redos(self.h))
 
     def set_stream(self, stream_ptr):
         self._check(self.lib.cddp_hip_set_stream(self.h, C.c_void_p(stream_ptr)))

@@ -452,6 +452,13 @@ int cddp_hip_forward(cddp_hip_handle *h, const double *alphas, int n_alphas,
 /* ISolverAlgorithm::solve for the batch: cddp_solver_base.cpp:29-186 as a per-trajectory
  * device state machine.  Calls cddp_hip_initialize first.  stats may be NULL. */
 int cddp_hip_solve(cddp_hip_handle *h, cddp_hip_stats *stats);
+/* How the last cddp_hip_solve scheduled the IPDDP costate trial (before the first solve: how the next one would): 1 = deferred into the
+ * next sweep launch ("shadow": path-constrained IPDDP on the role-split sweep, no terminal set, Gauss-Newton, first-success rule, a
+ * restartable solve), 0 = on the iteration's chain.  CDDP_HIP_COSTATE=sync | shadow (read at create) overrides the default.  Results
+ * are bitwise the same either way. */
+int cddp_hip_costate_mode(cddp_hip_handle *h);
+/* Deferred solves of this handle that met a non-finite costate row, were discarded and run again on the chain (0 on healthy problems). */
+int cddp_hip_costate_redos(cddp_hip_handle *h);
 
 /* ---- getters (host buffers, batch-major) -------------------------------- */
 int cddp_hip_get_results(cddp_hip_handle *h, cddp_hip_result *results /* batch */);
