@@ -11,11 +11,32 @@
 //   Manipulator         : central finite differences, h = 2e-5 (manipulator.cpp:53-70, helper.hpp:95-118)
 //   LTI                 : (A - I)/dt, B/dt (lti_system.cpp:78-92)
 #pragma once
+#include <type_traits>
 #include "dev_linalg.hpp"
 #include "dev_trig.hpp"
 #include "../../include/cddp_hip.h"
 
 namespace cddp_dev {
+
+// ---- trig policy of a plant's f (a template parameter of Model::f of the plants that carry `kTrigPolicy`) --------------------
+// TrigChecked: what every caller gets by default -- plant_sincos, i.e. (shared-arithmetic build) the fast routine with its own range
+// test, ballot and libm fallback per call.  TrigFlagged: the fast result only, the range verdict ORed into the caller's flag
+// (dev_trig.hpp::sincos_fast_flag); the caller tests the flag once per integrator step and redoes the step with the checked path
+// (RollStep below).  Only meaningful where plant_sincos IS the fast routine: kTrigFlaggable.
+struct TrigChecked {
+  DEV void sincos(double a, double *s, double *c) const { plant_sincos(a, s, c); }
+};
+struct TrigFlagged {
+  bool *out_of_range;
+  DEV void sincos(double a, double *s, double *c) const { const SinCosPair r = sincos_fast_flag(a, *out_of_range); *s = r.s; *c = r.c; }
+};
+#ifdef CDDP_TRIG_SHARED
+constexpr bool kTrigFlaggable = true;
+#else
+constexpr bool kTrigFlaggable = false;
+#endif
+template <class Model, class = void> struct HasTrigPolicy { static constexpr bool value = false; };
+template <class Model> struct HasTrigPolicy<Model, typename std::enable_if<Model::kTrigPolicy>::type> { static constexpr bool value = kTrigFlaggable; };
 
 // ---- forward-mode dual number with NP compile-time seeds (register resident) ------------
 template <int NP>
@@ -253,11 +274,13 @@ struct PendulumModel {   // pendulum.cpp:29-66; params: length, mass, damping, g
 struct CartPoleModel {   // cartpole.cpp:38-103; params: cart_mass, pole_mass, pole_length, gravity, damping
   static constexpr int ID = CDDP_HIP_MODEL_CARTPOLE, NX = 4, NU = 1;
   static constexpr bool kDiscrete = false;
-  DEV static void f(const double *p, const double *x, const double *u, double *xd) {
+  static constexpr bool kTrigPolicy = true;
+  template <class Trig = TrigChecked>
+  DEV static void f(const double *p, const double *x, const double *u, double *xd, const Trig tg = Trig()) {
     // double path (cartpole.cpp:38-67): NO damping term
     const double mc = p[0], mp = p[1], l = p[2], g = p[3];
     const double theta_dot = x[3], force = u[0];
-    double s, c; plant_sincos(x[1], &s, &c);
+    double s, c; tg.sincos(x[1], &s, &c);
     const double total_mass = mc + mp;
     const double den = mc + mp * s * s;
     xd[0] = x[2];
@@ -344,8 +367,10 @@ struct CartPoleModel {   // cartpole.cpp:38-103; params: cart_mass, pole_mass, p
 struct UnicycleModel {   // unicycle.cpp:28-66
   static constexpr int ID = CDDP_HIP_MODEL_UNICYCLE, NX = 3, NU = 2;
   static constexpr bool kDiscrete = false;
-  DEV static void f(const double *, const double *x, const double *u, double *xd) {
-    double s, c; plant_sincos(x[2], &s, &c);
+  static constexpr bool kTrigPolicy = true;
+  template <class Trig = TrigChecked>
+  DEV static void f(const double *, const double *x, const double *u, double *xd, const Trig tg = Trig()) {
+    double s, c; tg.sincos(x[2], &s, &c);
     xd[0] = u[0] * c; xd[1] = u[0] * s; xd[2] = u[1];
   }
   DEV static void jac(const double *, const double *x, const double *u, double *Fx, double *Fu) {
@@ -1458,5 +1483,65 @@ template <class Model> struct Stepper<Model, false> {
     for (int i = 0; i < NX; ++i) xn[i] = x[i] + c.dt6 * (((k1[i] + 2.0 * k2[i]) + 2.0 * k3[i]) + k4[i]);
   }
 };
+
+// ---- one step of the two-role rollout's producer (kernels_lean.hpp::k_forward_ipddp_pc) ----------------------------------------
+// The integrator is a TEMPLATE parameter: the producer switches on ProblemDev::integrator once, in front of its step loop, so the
+// loop holds one integrator's code and no test of it.  Each integrator is the expressions of Stepper::step(const DynCtx &, ...)
+// above, in the same order.  A plant with a trig policy takes its sines and cosines through TrigFlagged: the step is then ONE
+// basic block, and `*redo` tells the caller that some angle of the step was outside the fast routine's range (or not finite), in
+// which case the caller evaluates the step again with Stepper::step, whose plant_sincos serves such angles from the libm -- lanes
+// in range get the values they had, lanes out of range the values the checked path always gave them.  A plant without the policy
+// (or a caller that passes FLAGGED = false) keeps the per-call checks and never sets the flag.
+template <class Model, bool FLAGGED, class Trig>
+DEV void roll_f(const double *p, const double *x, const double *u, double *xd, const Trig tg) {
+  if constexpr (FLAGGED) Model::f(p, x, u, xd, tg);
+  else Model::f(p, x, u, xd);
+}
+template <class Model, int INTEG, bool FLAGGED = HasTrigPolicy<Model>::value>
+DEV void roll_step(const DynCtx &c, const double *x, const double *u, double *xn, bool *redo) {
+  if constexpr (Model::kDiscrete) {
+    Stepper<Model>::step(c, x, u, xn);
+  } else {
+    constexpr int NX = Model::NX;
+    const double *p = c.mp;
+    const TrigFlagged tg{redo};
+    double k1[NX];
+    roll_f<Model, FLAGGED>(p, x, u, k1, tg);
+    if constexpr (INTEG == CDDP_HIP_EULER) {
+#pragma unroll
+      for (int i = 0; i < NX; ++i) xn[i] = x[i] + c.dt * k1[i];
+    } else if constexpr (INTEG == CDDP_HIP_HEUN) {
+      double xt[NX], k2[NX];
+#pragma unroll
+      for (int i = 0; i < NX; ++i) xt[i] = x[i] + c.dt * k1[i];
+      roll_f<Model, FLAGGED>(p, xt, u, k2, tg);
+#pragma unroll
+      for (int i = 0; i < NX; ++i) xn[i] = x[i] + c.hdt * (k1[i] + k2[i]);
+    } else if constexpr (INTEG == CDDP_HIP_RK3) {
+      double xt[NX], k2[NX], k3[NX];
+#pragma unroll
+      for (int i = 0; i < NX; ++i) xt[i] = x[i] + c.hdt * k1[i];
+      roll_f<Model, FLAGGED>(p, xt, u, k2, tg);
+#pragma unroll
+      for (int i = 0; i < NX; ++i) xt[i] = (x[i] - c.dt * k1[i]) + c.dt2 * k2[i];
+      roll_f<Model, FLAGGED>(p, xt, u, k3, tg);
+#pragma unroll
+      for (int i = 0; i < NX; ++i) xn[i] = x[i] + c.dt6 * ((k1[i] + 4.0 * k2[i]) + k3[i]);
+    } else {
+      double xt[NX], k2[NX], k3[NX], k4[NX];
+#pragma unroll
+      for (int i = 0; i < NX; ++i) xt[i] = x[i] + c.hdt * k1[i];
+      roll_f<Model, FLAGGED>(p, xt, u, k2, tg);
+#pragma unroll
+      for (int i = 0; i < NX; ++i) xt[i] = x[i] + c.hdt * k2[i];
+      roll_f<Model, FLAGGED>(p, xt, u, k3, tg);
+#pragma unroll
+      for (int i = 0; i < NX; ++i) xt[i] = x[i] + c.dt * k3[i];
+      roll_f<Model, FLAGGED>(p, xt, u, k4, tg);
+#pragma unroll
+      for (int i = 0; i < NX; ++i) xn[i] = x[i] + c.dt6 * (((k1[i] + 2.0 * k2[i]) + 2.0 * k3[i]) + k4[i]);
+    }
+  }
+}
 
 }  // namespace cddp_dev

@@ -66,6 +66,49 @@ DEV SinCosPair sincos_fast(double x) {
   return o;
 }
 
+// The fast result AND the range verdict, for a caller that tests the range ONCE for several calls (the two-role rollout's producer:
+// one ballot per integrator step instead of one per stage, kernels_lean.hpp): returns the bits of sincos_fast(x) and ORs "|x| >= 1e9,
+// NaN or inf" into the caller's flag -- no ballot, no call, so consecutive calls stay in one basic block.  A set flag obliges the caller
+// to redo the work with sincos_n, which serves such arguments from the libm.  Same reduction and kernels as sincos_fast, expression for
+// expression; only the quadrant signs are applied as integer operations on the high word (-v flips bit 63 of every double, NaN included,
+// so the bits are the same; an xor costs one instruction where the compare-and-select form costs four).  sincos_fast itself stays as it
+// is: it is also the oracle's routine.  tests/cpp/test_dev_trig_flag.cpp checks both properties on the host.
+DEV SinCosPair sincos_fast_flag(double x, bool &out_of_range) {
+  const double TWO_OVER_PI = 0x1.45f306dc9c883p-1;
+  const double P1 = 0x1.921fb54442d18p+0, P2 = 0x1.1a62633145c07p-54, P3 = -0x1.f1976b7ed8fbcp-110;
+  const double dn = __builtin_rint(x * TWO_OVER_PI);
+  const double r0 = __builtin_fma(-dn, P1, x);
+  const double p = dn * P2;
+  const double pe = __builtin_fma(dn, P2, -p);
+  const double r = r0 - p;
+  const double bb = r - r0;
+  const double e1 = (r0 - (r - bb)) + (-p - bb);
+  const double y = __builtin_fma(-dn, P3, e1 - pe);
+  const double z = r * r, w = z * z;
+  const double S1 = -1.66666666666666324348e-01, S2 = 8.33333333332248946124e-03, S3 = -1.98412698298579493134e-04,
+               S4 = 2.75573137070700676789e-06, S5 = -2.50507602534068634195e-08, S6 = 1.58969099521155010221e-10;
+  const double rs = S2 + z * (S3 + z * S4) + z * w * (S5 + z * S6);
+  const double v = z * r;
+  const double ks = r - ((z * (0.5 * y - v * rs) - y) - v * S1);
+  const double C1 = 4.16666666666666019037e-02, C2 = -1.38888888888741095749e-03, C3 = 2.48015872894767294178e-05,
+               C4 = -2.75573143513906633035e-07, C5 = 2.08757232129817482790e-09, C6 = -1.13596475577881948265e-11;
+  const double rc = z * (C1 + z * (C2 + z * C3)) + (w * w) * (C4 + z * (C5 + z * C6));
+  const double hz = 0.5 * z;
+  const double w1 = 1.0 - hz;
+  const double kc = w1 + (((1.0 - w1) - hz) + (z * rc - r * y));
+  const int n = (int)dn;
+  const bool swap = (n & 1) != 0;
+  const double s = swap ? kc : ks, c = swap ? ks : kc;
+  unsigned long long us, uc;
+  __builtin_memcpy(&us, &s, 8); __builtin_memcpy(&uc, &c, 8);
+  us ^= (unsigned long long)((unsigned)n & 2u) << 62;          // n & 2: bit 1 -> bit 63
+  uc ^= (unsigned long long)(((unsigned)n + 1u) & 2u) << 62;
+  SinCosPair o;
+  __builtin_memcpy(&o.s, &us, 8); __builtin_memcpy(&o.c, &uc, 8);
+  out_of_range = out_of_range || !(__builtin_fabs(x) < kTrigFastLimit);   // also true for NaN / inf
+  return o;
+}
+
 #ifndef CDDP_TRIG_HOST
 // The libm fallback as a real function call: inlined N times it put N copies of the Payne-Hanek reduction into the calling
 // kernel and its register demand (the largest of the whole rollout kernel) set the kernel's allocation.

@@ -743,6 +743,21 @@ __device__ unsigned long long g_k4_times[16384 * 4];
 // the filter test.  A consumer whose 64 trials have all failed posts the step at which it saw that (s_abort); the other finishes its own steps
 // below that step (an earlier failure it alone can see decides the step count of the trial) and stops.  Bitwise the one-consumer kernel
 // (tests/test_gpu_parity.py::test_two_consumer_rollout_agrees_bitwise); NC = 1 is unchanged code.
+// The producer's step is straight-line code (dev_models.hpp::roll_step): the integrator is chosen once per launch and the range test of the
+// fast sin / cos is made once per step, on a flag.  When any lane's flag is set the wave evaluates that step again HERE, with the checked
+// Stepper::step (per-call range test, libm for the angles that need it).  A real call, by value in and out, behind a wave-uniform branch:
+// inlined, the checked step -- and through it the device libm's Payne-Hanek reduction -- joined the loop's register allocation and cut
+// the loop into blocks again (the lesson of dev_trig.hpp::sincos_libm).  The plant parameters are read from the problem record, the
+// values DynCtx holds; 0.5 dt, dt / 6 and 2 dt are formed from dt as DynCtx::load forms them.
+template <int NX, int NU> struct RollIn { double x[NX], u[NU]; };
+template <int NX> struct RollOut { double xn[NX]; };
+template <class Model>
+__device__ __attribute__((noinline)) RollOut<Model::NX> roll_step_checked(int integrator, double dt, const double *mp, RollIn<Model::NX, Model::NU> in) {
+  RollOut<Model::NX> o;
+  Stepper<Model>::step(integrator, dt, mp, in.x, in.u, o.xn);
+  return o;
+}
+
 template <class Model, class Cons, bool TERM = false, int NC = 1>
 __global__ __launch_bounds__(64 * (1 + NC)) void k_forward_ipddp_pc(DevBuf d, const ProblemDev *__restrict__ Pk, const double *__restrict__ xrt,
                                                                     int a0, int phase_req, int force) {
@@ -807,11 +822,28 @@ __global__ __launch_bounds__(64 * (1 + NC)) void k_forward_ipddp_pc(DevBuf d, co
     ld<NX>(Xc + GI(0, NX, 0), kLS, x);
     st<NX>(Xn + GI(0, NX, 0), kLS, x);
     struct StepIn { double xo[NX], uo[NU], kk[NU], KK[NU * NX]; };
-    auto load_step = [&](int tt, StepIn &r) {
+    // Running row pointers (round 10).  GI(t, E, 0) = GI(0, E, 0) + t * (NB * E * 64): every row base the step touches advances by a
+    // constant stride per step -- one 64-bit add each -- where GI(t, ...) re-derived it from t with 64-bit scalar multiplies, once for
+    // the prefetch and once for the stores (~45 scalar instructions per cart-pole step).  Same addresses: ld_* stand at the row of
+    // min(t + 1, N - 1) once step t has advanced them (the clamped prefetch), st_U at row t, st_X at row t + 1.
+    const size_t rs1 = (size_t)d.NB * 64;   // row stride of a one-entry element, doubles
+    const double *ld_X = Xc + GI(0, NX, 0), *ld_U = Uc + GI(0, NU, 0), *ld_k = d.k + GI(0, NU, 0), *ld_K = d.K + GI(0, NU * NX, 0);
+    double *st_U = Un + GI(0, NU, 0), *st_X = Xn + GI(1, NX, 0);
+    auto load_step = [&](int tt, StepIn &r) {   // (the layouts that keep the round-9 step, see kPing below)
       ld<NX>(Xc + GI(tt, NX, 0), kLS, r.xo);
       ld<NU>(Uc + GI(tt, NU, 0), kLS, r.uo);
       ld<NU>(d.k + GI(tt, NU, 0), kLS, r.kk);
       ld<NU * NX>(d.K + GI(tt, NU * NX, 0), kLS, r.KK);
+    };
+    auto load_row = [&](StepIn &r) {
+      ld<NX>(ld_X, kLS, r.xo);
+      ld<NU>(ld_U, kLS, r.uo);
+      ld<NU>(ld_k, kLS, r.kk);
+      ld<NU * NX>(ld_K, kLS, r.KK);
+    };
+    auto advance_ld = [&](const int t) {   // to the row of step t + 1, or stay on the last row
+      const size_t s = t + 1 < N ? rs1 : 0;
+      ld_X += s * NX; ld_U += s * NU; ld_k += s * NU; ld_K += s * (NU * NX);
     };
     DynCtx dc;   // loop-invariant constants in scalar registers
     dc.load(P->integrator, P->dt, P->mp);
@@ -846,6 +878,9 @@ __global__ __launch_bounds__(64 * (1 + NC)) void k_forward_ipddp_pc(DevBuf d, co
     // u_old[i], k[i] -- two chunk buffers; x_old of step t + 1 and its first chunk are fetched behind the integrator (42
     // doubles live there instead of 126).  Same sums.  With the consumer's chunks (below) the kernel fits two wavefronts per SIMD.
     constexpr bool kChunkP = !kPing && !kEarly;
+    // The straight-line step of round 10 (loop per integrator, flagged trig, running row pointers) is the ping-pong form's.  The
+    // larger records keep the step they had: built with it, the nx = 12 quadrotor's producer went from 408 to 500 registers and the 7-joint
+    // arm's from 420 to 436, with no measured gain to set against that (profiles/r10_rollout_step.md section 3).
     struct PChunk { double K[NX], uo, kk; };
     auto load_pchunk = [&](int tt, const int i, PChunk &c) {
       ld<NX>(d.K + GI(tt, NU * NX, i * NX), kLS, c.K);
@@ -853,10 +888,14 @@ __global__ __launch_bounds__(64 * (1 + NC)) void k_forward_ipddp_pc(DevBuf d, co
     };
     PChunk pk0, pk1;
     double xo_c[NX];
-    auto step = [&](const int t, StepIn &cs, StepIn &nxt) {
+    // (NC = 2 keeps the per-call range tests: its producer also sums the running cost, and with the flagged step and the call its frame
+    //  grew from 32 to 112 B of scratch -- profiles/r10_rollout_step.md section 3)
+    constexpr bool kFlagged = kPing && HasTrigPolicy<Model>::value && NC == 1;
+    auto step = [&](auto integ, const int t, StepIn &cs, StepIn &nxt) {
+      constexpr int INTEG = decltype(integ)::value;
       if constexpr (kPing) {
-        const int tn = t + 1 < N ? t + 1 : N - 1;   // unconditional (clamped) prefetch
-        load_step(tn, nxt);
+        advance_ld(t);   // unconditional (clamped) prefetch
+        load_row(nxt);
       }
       PIPELINE_FENCE();
       double dx[NX], u[NU], xn[NX];
@@ -917,38 +956,71 @@ __global__ __launch_bounds__(64 * (1 + NC)) void k_forward_ipddp_pc(DevBuf d, co
         load_pchunk(tn, 0, pk0);
         PIPELINE_FENCE();
       }
-      Stepper<Model>::step(dc, x, u, xn);
+      [[maybe_unused]] bool redo = false;
+      if constexpr (kPing) roll_step<Model, INTEG, kFlagged>(dc, x, u, xn, &redo);
+      else Stepper<Model>::step(dc, x, u, xn);
+      // (The ballot takes every lane, dead and padding lanes included: a frozen lane whose stages leave the range makes the wave redo each
+      //  later step, where the per-call form paid one libm call per bad stage.  Masking with `alive` would leave fast-path values in the
+      //  X rows of dead trials, and those rows are kept what they were -- the same reason their stores stay with the producer.)
+      if constexpr (kFlagged) {   // one range test per step (see roll_step_checked)
+        if (__builtin_expect(__builtin_amdgcn_ballot_w64(redo) != 0ull, 0)) {
+          RollIn<NX, NU> in;
+#pragma unroll
+          for (int i = 0; i < NX; ++i) in.x[i] = x[i];
+#pragma unroll
+          for (int i = 0; i < NU; ++i) in.u[i] = u[i];
+          const RollOut<NX> o = roll_step_checked<Model>(dc.integrator, dc.dt, P->mp, in);
+#pragma unroll
+          for (int i = 0; i < NX; ++i) xn[i] = o.xn[i];
+        }
+      }
 #pragma unroll
       for (int i = 0; i < NX; ++i) finite = finite && dfinite(xn[i]);
       if (alive && !finite) { s_pstat[lane] = t; alive = false; }
-      st<NU>(Un + GI(t, NU, 0), kLS, u);
-      st<NX>(Xn + GI(t + 1, NX, 0), kLS, xn);
+      if constexpr (kPing) {
+        st<NU>(st_U, kLS, u);
+        st<NX>(st_X, kLS, xn);
+        st_U += rs1 * NU; st_X += rs1 * NX;
+      } else {
+        st<NU>(Un + GI(t, NU, 0), kLS, u);
+        st<NX>(Xn + GI(t + 1, NX, 0), kLS, xn);
+      }
       if (alive) {
 #pragma unroll
         for (int i = 0; i < NX; ++i) x[i] = xn[i];
       }
     };
-    StepIn ra;
     int t = 0;
-    if constexpr (kPing) {
-      StepIn R[2];   // step t lives in R[t % 2]; every index below is a compile-time constant
+    // The step loop, instantiated per integrator (round 10): ONE wave-uniform switch in front of it instead of Stepper::step's tests of
+    // DynCtx::integrator inside every step, which compiled all four integrators into the loop and cut the step into basic blocks.
+    auto walk = [&](auto integ) {
+      if constexpr (kPing) {
+        StepIn R[2];   // step t lives in R[t % 2]; every index below is a compile-time constant
+        load_row(R[0]);   // row 0 (N >= 1)
+        prime();
+        for (; t + 1 < N; t += 2) {
 #pragma unroll
-      for (int j = 0; j < 1; ++j) load_step(j < N ? j : N - 1, R[j]);
-      prime();
-      for (; t + 1 < N; t += 2) {
+          for (int j = 0; j <= 1; ++j) step(integ, t + j, R[j], R[(j + 1) % 2]);
+          if (__builtin_amdgcn_ballot_w64(alive) == 0ull) { t = N; break; }   // nothing downstream reads the rows any more
+        }
 #pragma unroll
-        for (int j = 0; j <= 1; ++j) step(t + j, R[j], R[(j + 1) % 2]);
-        if (__builtin_amdgcn_ballot_w64(alive) == 0ull) { t = N; break; }   // nothing downstream reads the rows any more
+        for (int j = 0; j <= 1; ++j) if (t + j < N) step(integ, t + j, R[j], R[(j + 1) % 2]);
+      } else {
+        StepIn ra;
+        if constexpr (kChunkP) { ld<NX>(Xc + GI(0, NX, 0), kLS, xo_c); load_pchunk(0, 0, pk0); } else load_step(0, ra);
+        prime();
+        for (; t < N; ++t) {
+          step(integ, t, ra, ra);
+          if (__builtin_amdgcn_ballot_w64(alive) == 0ull) break;
+        }
       }
-#pragma unroll
-      for (int j = 0; j <= 1; ++j) if (t + j < N) step(t + j, R[j], R[(j + 1) % 2]);
-    } else {
-      if constexpr (kChunkP) { ld<NX>(Xc + GI(0, NX, 0), kLS, xo_c); load_pchunk(0, 0, pk0); } else load_step(0, ra);
-      prime();
-      for (; t < N; ++t) {
-        step(t, ra, ra);
-        if (__builtin_amdgcn_ballot_w64(alive) == 0ull) break;
-      }
+    };
+    if constexpr (Model::kDiscrete || !kPing) walk(std::integral_constant<int, CDDP_HIP_RK4>());   // (no integrator / Stepper::step tests it: ONE loop)
+    else switch (dc.integrator) {
+      case CDDP_HIP_EULER: walk(std::integral_constant<int, CDDP_HIP_EULER>()); break;
+      case CDDP_HIP_HEUN: walk(std::integral_constant<int, CDDP_HIP_HEUN>()); break;
+      case CDDP_HIP_RK3: walk(std::integral_constant<int, CDDP_HIP_RK3>()); break;
+      default: walk(std::integral_constant<int, CDDP_HIP_RK4>()); break;
     }
     if (alive) s_pcost[lane] = Obj::terminal_cost(P, x);
     if constexpr (NC > 1) s_prun[lane] = run_cost_p;
