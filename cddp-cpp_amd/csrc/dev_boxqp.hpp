@@ -187,7 +187,9 @@ DEV int boxqp_solve1(const cddp_hip_options &o, const double H, const double g, 
 // The routine evaluates exactly the statements of those traces (same operands, same order, selects instead of branches) and
 // returns their result; when ANY lane of the wavefront leaves them (a shortened step, a third pass, no descent, an out-of-range
 // gradient square, fewer than two passes allowed) every lane redoes the call with the loop -- a prefix of the same trace, so the
-// answer is the loop's in both cases.  tests/test_boxqp.py replays the reference-held inputs through both.
+// answer is the loop's in both cases.  tests/test_boxqp.py runs both forms on the device (tests/hip/dev_probe.hip) over every exit and
+// over wavefronts that mix fast and slow lanes.  Device only: the ballot has no host side.
+#ifndef CDDP_HOST_MODELS
 DEV int boxqp_solve1_fast(const BoxQPConst &o, const double H, const double g, const double lower, const double upper, double &x, int &free_) {
   const double xw = x;
   const double x0 = dmin(dmax(xw, lower), upper);
@@ -223,5 +225,6 @@ DEV int boxqp_solve1_fast(const BoxQPConst &o, const double H, const double g, c
   free_ = (exitA || exitD) ? 0 : 1;
   return (exitA || exitD) ? BQ_ALL_CLAMPED : BQ_SUCCESS;
 }
+#endif
 
 }  // namespace cddp_dev

@@ -371,6 +371,34 @@ DEV double min_real_eig(const double *M) {
   return mn;
 }
 
+// Largest and smallest singular value of the leading n x n block of A (leading dimension NMAXP) by one-sided Jacobi: the
+// regularisation floor of the terminal-equality reduced system (ipddp_solver.cpp:556-617).  ONE text for the solver core's
+// te_backward (kernels.hpp, NMAXP = kPTMax) and the stack-fed sweep (stacks_te.hpp, NMAXP = kPTS); kernels_te.hpp::singular_minmax_mem
+// is the same loop on memory operands with a run-time leading dimension.
+template <int NMAXP>
+DEV void singular_minmax(const double *A, int n, double &smax, double &smin) {
+  double U[NMAXP * NMAXP];
+  for (int i = 0; i < n; ++i) for (int j = 0; j < n; ++j) U[i * NMAXP + j] = A[i * NMAXP + j];
+  for (int sweep = 0; sweep < 80; ++sweep) {
+    bool rotated = false;
+    for (int p = 0; p < n; ++p)
+      for (int q = p + 1; q < n; ++q) {
+        double alpha = 0, beta = 0, gamma = 0;
+        for (int i = 0; i < n; ++i) { alpha += U[i * NMAXP + p] * U[i * NMAXP + p]; beta += U[i * NMAXP + q] * U[i * NMAXP + q]; gamma += U[i * NMAXP + p] * U[i * NMAXP + q]; }
+        if (fabs(gamma) <= 1e-300 || fabs(gamma) <= 1e-16 * sqrt(alpha * beta)) continue;
+        rotated = true;
+        double zeta = (beta - alpha) / (2.0 * gamma);
+        double t = (zeta >= 0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
+        double cs = 1.0 / sqrt(1.0 + t * t), sn = cs * t;
+        for (int i = 0; i < n; ++i) { double up = U[i * NMAXP + p], uq = U[i * NMAXP + q]; U[i * NMAXP + p] = cs * up - sn * uq; U[i * NMAXP + q] = sn * up + cs * uq; }
+      }
+    if (!rotated) break;
+  }
+  smax = 0.0; smin = INFINITY;
+  for (int j = 0; j < n; ++j) { double s2 = 0; for (int i = 0; i < n; ++i) s2 += U[i * NMAXP + j] * U[i * NMAXP + j]; double sv = sqrt(s2); smax = dmax(smax, sv); smin = dmin(smin, sv); }
+  if (n == 0) { smax = 0.0; smin = 0.0; }
+}
+
 // ---- tiny GEMM helpers, row-major, compile-time sizes, k-ascending accumulation ----------
 // C(RxC) = A^T(RxK) * B(KxC) where A is stored KxR
 template <int R, int K, int C>

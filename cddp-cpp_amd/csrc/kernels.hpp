@@ -459,29 +459,7 @@ DEV void lin_rollout_caps(const DevBuf &d, const ProblemDev *__restrict__ P, int
 // p x p regularised normal-equation solve for the terminal multipliers (solveTerminalEqualityLQR
 // :478-639) and the recombination of k, p.  One lane does all variants of its trajectory.
 // ---------------------------------------------------------------------------------------------
-template <int NMAXP>
-DEV void singular_minmax(const double *A, int n, double &smax, double &smin) {   // one-sided Jacobi
-  double U[NMAXP * NMAXP];
-  for (int i = 0; i < n; ++i) for (int j = 0; j < n; ++j) U[i * NMAXP + j] = A[i * NMAXP + j];
-  for (int sweep = 0; sweep < 80; ++sweep) {
-    bool rotated = false;
-    for (int p = 0; p < n; ++p)
-      for (int q = p + 1; q < n; ++q) {
-        double alpha = 0, beta = 0, gamma = 0;
-        for (int i = 0; i < n; ++i) { alpha += U[i * NMAXP + p] * U[i * NMAXP + p]; beta += U[i * NMAXP + q] * U[i * NMAXP + q]; gamma += U[i * NMAXP + p] * U[i * NMAXP + q]; }
-        if (fabs(gamma) <= 1e-300 || fabs(gamma) <= 1e-16 * sqrt(alpha * beta)) continue;
-        rotated = true;
-        double zeta = (beta - alpha) / (2.0 * gamma);
-        double t = (zeta >= 0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
-        double cs = 1.0 / sqrt(1.0 + t * t), sn = cs * t;
-        for (int i = 0; i < n; ++i) { double up = U[i * NMAXP + p], uq = U[i * NMAXP + q]; U[i * NMAXP + p] = cs * up - sn * uq; U[i * NMAXP + q] = sn * up + cs * uq; }
-      }
-    if (!rotated) break;
-  }
-  smax = 0.0; smin = INFINITY;
-  for (int j = 0; j < n; ++j) { double s2 = 0; for (int i = 0; i < n; ++i) s2 += U[i * NMAXP + j] * U[i * NMAXP + j]; double sv = sqrt(s2); smax = dmax(smax, sv); smin = dmin(smin, sv); }
-  if (n == 0) { smax = 0.0; smin = 0.0; }
-}
+// (singular_minmax<NMAXP>, the one-sided Jacobi of the reduced system's singular values: dev_linalg.hpp)
 
 template <class Model, class Cons>
 DEV bool te_backward(const DevBuf &d, int b, const double *Xc, const double *Uc, const double *Sc, const double *Yc,

@@ -27,30 +27,6 @@ struct StackTeArgs {
   double *dX;             // [(N+1)][nx][Bp]
 };
 
-template <int NMAXP>
-DEV void te_singular_minmax(const double *A, int n, double &smax, double &smin) {   // one-sided Jacobi (kernels.hpp::singular_minmax)
-  double U[NMAXP * NMAXP];
-  for (int i = 0; i < n; ++i) for (int j = 0; j < n; ++j) U[i * NMAXP + j] = A[i * NMAXP + j];
-  for (int sweep = 0; sweep < 80; ++sweep) {
-    bool rotated = false;
-    for (int p = 0; p < n; ++p)
-      for (int q = p + 1; q < n; ++q) {
-        double alpha = 0, beta = 0, gamma = 0;
-        for (int i = 0; i < n; ++i) { alpha += U[i * NMAXP + p] * U[i * NMAXP + p]; beta += U[i * NMAXP + q] * U[i * NMAXP + q]; gamma += U[i * NMAXP + p] * U[i * NMAXP + q]; }
-        if (fabs(gamma) <= 1e-300 || fabs(gamma) <= 1e-16 * sqrt(alpha * beta)) continue;
-        rotated = true;
-        double zeta = (beta - alpha) / (2.0 * gamma);
-        double t = (zeta >= 0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
-        double cs = 1.0 / sqrt(1.0 + t * t), sn = cs * t;
-        for (int i = 0; i < n; ++i) { double up = U[i * NMAXP + p], uq = U[i * NMAXP + q]; U[i * NMAXP + p] = cs * up - sn * uq; U[i * NMAXP + q] = sn * up + cs * uq; }
-      }
-    if (!rotated) break;
-  }
-  smax = 0.0; smin = INFINITY;
-  for (int j = 0; j < n; ++j) { double s2 = 0; for (int i = 0; i < n; ++i) s2 += U[i * NMAXP + j] * U[i * NMAXP + j]; double sv = sqrt(s2); smax = dmax(smax, sv); smin = dmin(smin, sv); }
-  if (n == 0) { smax = 0.0; smin = 0.0; }
-}
-
 // One pass at regularisation `reg`; false where the reference's backwardPass returns false (failed factorisation, non-finite recursion).
 template <int NX, int NU, bool T4>   // T4: SI() on tile-minor stacks (the nx = 6 handles, whose default sweep is the cooperative one)
 DEV bool te_sweep(const StackArgs &a, const StackTeArgs &e, int b, double reg, double &inf_du, double &step_norm) {
@@ -168,7 +144,7 @@ DEV bool te_sweep(const StackArgs &a, const StackTeArgs &e, int b, double reg, d
   const double trace_term = (tr > 1.0 ? tr / (pT > 1 ? pT : 1) : 1.0);
   const double regv = dmax(e.floor_[b], 1e-6 * trace_term);
   double smax, smin;
-  te_singular_minmax<kPTS>(As, pT, smax, smin);
+  singular_minmax<kPTS>(As, pT, smax, smin);
   const double svd_reg = dmax(1e-8 * smax - smin, 0.0);
   const double reg_base = dmax(regv, svd_reg);
   double rn = 0.0; for (int r = 0; r < pT; ++r) rn += rhs[r] * rhs[r];
