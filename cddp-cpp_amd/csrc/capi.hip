@@ -43,6 +43,92 @@ static __global__ void k_gather_plan_head(DevBuf d, int nx, int nu, double *out)
   for (int i = 0; i < nx; ++i) o[nu + i] = Xc[((((size_t)1 * d.NB + (size_t)(b >> 6)) * nx + i) * 64) + (size_t)(b & 63)];
 }
 
+// ---- device-resident MPC step (cddp_hip_mpc_advance / cddp_hip_mpc_run) ----------------------------------------
+// The shifted seed of the next solve is a row permutation of every trajectory's CURRENT iterate (slot cur[b]): it never leaves the device.
+//
+// k_mpc_shift: one lane per (trajectory b, element e); blockIdx.x = 64-trajectory tile, blockIdx.y = element over [X | U | S | Y].  The lane
+// walks t UPWARDS for its own (b, e): it reads row t + 1 of the live slot and writes row t of the seed copy (Xinit / Uinit, what restore_initial
+// reads) AND row t of the live slot itself, so cur[b] and everything else a warm re-initialisation stages from the live slot (slack / dual /
+// costate rows, k_stage) stay where they are and the getters, which read slot cur[b], return the shifted plan.  Race-free: the addresses of
+// (b, e, any t) in the live slot and in the seed are touched by this one lane only, and within the lane row t + 1 is read before the same
+// iteration of the walk writes row t and before the NEXT iteration overwrites row t + 1 (program order of one thread) -- no second launch, no
+// grid-wide ordering.  A grid that spread t over blocks would read row t + 1 while another block writes it.
+// Coalescing: the 64 lanes of a wavefront are the 64 trajectories of one tile, so a row access is one 512-B line per slot value present among them.
+// The last row repeats (X_shifted[N] = X[N], U_shifted[N - 1] = U[N - 1]).  Padding lanes (b >= B) of X / U are left alone: the seed keeps what
+// cddp_hip_set_initial put there.  S / Y (shift_duals): row t of EVERY slot receives the shifted row and padding lanes zeros, as cddp_hip_set_duals writes them.
+static __global__ __launch_bounds__(64) void k_mpc_shift(DevBuf d, int nx, int nu, int m, int shift_duals, double *Xinit, double *Uinit) {
+  const int b = blockIdx.x * 64 + threadIdx.x;
+  int e = blockIdx.y;
+  const size_t tile = (size_t)(b >> 6), lane = (size_t)(b & 63), NB = (size_t)d.NB;
+  const int N = d.N;
+  const int cur = b < d.B ? d.cur[b] : 0;
+  if (e < nx) {
+    if (b >= d.B) return;
+    double *Xc = d.X + (size_t)cur * d.planeX;
+    for (int t = 0; t <= N; ++t) {
+      const size_t dst = (((size_t)t * NB + tile) * nx + e) * 64 + lane, src = (((size_t)(t < N ? t + 1 : N) * NB + tile) * nx + e) * 64 + lane;
+      const double v = Xc[src];
+      Xc[dst] = v; Xinit[dst] = v;
+    }
+    return;
+  }
+  e -= nx;
+  if (e < nu) {
+    if (b >= d.B) return;
+    double *Uc = d.U + (size_t)cur * d.planeU;
+    for (int t = 0; t < N; ++t) {
+      const size_t dst = (((size_t)t * NB + tile) * nu + e) * 64 + lane, src = (((size_t)(t < N - 1 ? t + 1 : N - 1) * NB + tile) * nu + e) * 64 + lane;
+      const double v = Uc[src];
+      Uc[dst] = v; Uinit[dst] = v;
+    }
+    return;
+  }
+  e -= nu;
+  if (!shift_duals || e >= 2 * m) return;
+  double *base = e < m ? d.S : d.Y;
+  if (e >= m) e -= m;
+  const double *live = base + (size_t)cur * d.planeM;
+  for (int t = 0; t < N; ++t) {
+    const size_t dst = (((size_t)t * NB + tile) * m + e) * 64 + lane, src = (((size_t)(t < N - 1 ? t + 1 : N - 1) * NB + tile) * m + e) * 64 + lane;
+    const double v = b < d.B ? live[src] : 0.0;   // (read before the slot loop below overwrites row t of the live slot; row t + 1 is still the old one)
+    for (int sl = 0; sl < d.n_slots; ++sl) base[(size_t)sl * d.planeM + dst] = v;
+  }
+}
+
+// k_mpc_state: row 0 of the seed from the measured state x_next (batch-major, on the device) or, x_next == NULL and every_slot, from row 1 of
+// the live slot.  every_slot = 1 (KEEP_PLAN): row 0 of Xinit and of EVERY slot, padding lanes zero, as cddp_hip_set_initial_state writes them;
+// every_slot = 0 (after k_mpc_shift): row 0 of Xinit and of the live slot, X_[0] = initial_state as cddp_hip_set_initial writes it.
+static __global__ void k_mpc_state(DevBuf d, int nx, const double *x_next, int every_slot, double *Xinit) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= d.Bp || (b >= d.B && !every_slot)) return;
+  const size_t tile = (size_t)(b >> 6), lane = (size_t)(b & 63), NB = (size_t)d.NB;
+  const int cur = b < d.B ? d.cur[b] : 0;
+  for (int e = 0; e < nx; ++e) {
+    const size_t r0 = (((size_t)0 * NB + tile) * nx + e) * 64 + lane, r1 = (((size_t)1 * NB + tile) * nx + e) * 64 + lane;
+    const double v = b >= d.B ? 0.0 : (x_next ? x_next[(size_t)b * nx + e] : d.X[(size_t)cur * d.planeX + r1]);
+    Xinit[r0] = v;
+    if (every_slot) for (int sl = 0; sl < d.n_slots; ++sl) d.X[(size_t)sl * d.planeX + r0] = v;
+    else d.X[(size_t)cur * d.planeX + r0] = v;
+  }
+}
+
+// the closed-loop log of cddp_hip_mpc_run, in the layout of its outputs: u_0 and x_1 (k_gather_plan_head's addressing), iteration count and
+// status of MPC step k of every trajectory; k < 0: the initial state of the first solve (row 0 of the seed) into X_visited[:, 0]
+static __global__ void k_mpc_log(DevBuf d, int nx, int nu, int steps, int k, const double *Xinit, double *Ulog, double *Xlog, int32_t *itlog, int32_t *stlog) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= d.B) return;
+  const size_t tile = (size_t)(b >> 6), lane = (size_t)(b & 63), NB = (size_t)d.NB;
+  if (k < 0) {
+    for (int i = 0; i < nx; ++i) Xlog[((size_t)b * (steps + 1)) * nx + i] = Xinit[(((size_t)0 * NB + tile) * nx + i) * 64 + lane];
+    return;
+  }
+  const int cur = d.cur[b];
+  const double *Xc = d.X + (size_t)cur * d.planeX, *Uc = d.U + (size_t)cur * d.planeU;
+  for (int i = 0; i < nu; ++i) Ulog[((size_t)b * steps + k) * nu + i] = Uc[(((size_t)0 * NB + tile) * nu + i) * 64 + lane];
+  for (int i = 0; i < nx; ++i) Xlog[((size_t)b * (steps + 1) + k + 1) * nx + i] = Xc[(((size_t)1 * NB + tile) * nx + i) * 64 + lane];
+  itlog[(size_t)b * steps + k] = d.iter[b]; stlog[(size_t)b * steps + k] = d.status[b];
+}
+
 // CDDPOptions::max_cpu_time expired (cddp_solver_base.cpp:77-90): the check sits after ++iter and before the
 // backward pass, so every trajectory still running reports the iteration the check fired in.
 static __global__ void k_mark_cpu_time(DevBuf d) {
@@ -137,6 +223,10 @@ struct Inner {
   bool last_shadow = false;      // the last solve ran (and kept) the shadow schedule (cddp_hip_costate_mode)
   bool ever_solved = false;
   int *h_bad = nullptr;          // pinned host copy of DevBuf::cs_bad
+  // device-resident MPC step (cddp_hip_mpc_advance / cddp_hip_mpc_run)
+  bool has_plan = false;         // an initialize() or solve() has run: slot cur[b] holds every trajectory's current plan
+  double *d_xnext = nullptr;     // staging of a host x_next (B * nx doubles, batch-major): the one upload of an MPC step
+  double *d_log_u = nullptr, *d_log_x = nullptr; int32_t *d_log_it = nullptr, *d_log_st = nullptr; int log_steps = 0;   // closed-loop log of cddp_hip_mpc_run
 };
 
 namespace {
@@ -652,6 +742,8 @@ static int in_destroy(Inner *h) {
   if (h->h_bad) hipHostFree(h->h_bad);
   if (h->d_head) hipFree(h->d_head);
   if (h->h_head) hipHostFree(h->h_head);
+  if (h->d_xnext) hipFree(h->d_xnext);
+  if (h->d_log_u) { hipFree(h->d_log_u); hipFree(h->d_log_x); hipFree(h->d_log_it); hipFree(h->d_log_st); }
   if (h->own_stream && h->stream) hipStreamDestroy(h->stream);
   if (h->cu.fwd) hipStreamDestroy(h->cu.fwd);
   if (h->cu.sweep) hipStreamDestroy(h->cu.sweep);
@@ -748,6 +840,7 @@ static int run_initialize(Inner *h) {
   } else
   h->ks->init(h->d, mode, h->stream);
   h->has_state = true;
+  h->has_plan = true;
   h->initial_dirty = false;
   h->initialized = true;
   return 0;
@@ -1515,6 +1608,89 @@ static int in_write_gather_records_device(Inner *h, void *device_ptr) {
   return 0;
 }
 
+// ---- device-resident MPC step ---------------------------------------------------------------------------------------
+// the refusals of cddp_hip_mpc_advance, tested for EVERY group before any group launches anything
+static int in_mpc_check(Inner *h, int mode, int flags, bool need_plan = true) {
+  if (!h) return fail(-1, "null handle");
+  if (mode != CDDP_HIP_MPC_KEEP_PLAN && mode != CDDP_HIP_MPC_SHIFT_EXISTING && mode != CDDP_HIP_MPC_SHIFT_PROVIDED)
+    return fail(-2, "cddp_hip_mpc_advance: unknown mode %d", mode);
+  if (flags & ~(CDDP_HIP_MPC_SHIFT_DUALS | CDDP_HIP_MPC_X_DEVICE)) return fail(-2, "cddp_hip_mpc_advance: unknown flag bits 0x%x", flags);
+  if (need_plan && (!h->have_initial || !h->has_plan))
+    return fail(-1, "cddp_hip_mpc_advance needs a current plan: call cddp_hip_set_initial and cddp_hip_solve (or cddp_hip_initialize) first");
+  if (flags & CDDP_HIP_MPC_SHIFT_DUALS) {
+    if (mode != CDDP_HIP_MPC_SHIFT_EXISTING) return fail(-2, "cddp_hip_mpc_advance: CDDP_HIP_MPC_SHIFT_DUALS goes with CDDP_HIP_MPC_SHIFT_EXISTING only (the other modes keep or re-initialise the duals)");
+    if (h->P.solver != CDDP_HIP_SOLVER_IPDDP || h->P.m <= 0) return fail(-1, "cddp_hip_mpc_advance: CDDP_HIP_MPC_SHIFT_DUALS: the problem has no path duals");
+    if (need_plan && !h->has_state) return fail(-1, "cddp_hip_mpc_advance: CDDP_HIP_MPC_SHIFT_DUALS needs an initialised handle");
+  }
+  return 0;
+}
+
+// one group's MPC step (checked by in_mpc_check): kernels on the group's stream, host flags as the host sequence of the mode leaves them
+static int in_mpc_advance(Inner *h, int mode, int flags, const double *x_next, bool sync_device_x) {
+  HIPCHK(hipSetDevice(h->device));
+  const DevBuf &d = h->d;
+  const int nx = h->P.nx, nu = h->P.nu, m = h->P.m;
+  const double *xdev = nullptr;
+  const bool host_x = x_next && !(flags & CDDP_HIP_MPC_X_DEVICE);
+  if (host_x) {   // the step's only upload: B * nx doubles into the staging buffer, tiled by k_mpc_state
+    if (!h->d_xnext) HIPCHK(hipMalloc((void **)&h->d_xnext, (size_t)d.B * nx * sizeof(double)));
+    HIPCHK(hipMemcpyAsync(h->d_xnext, x_next, (size_t)d.B * nx * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    xdev = h->d_xnext;
+  } else if (x_next) xdev = x_next;
+  if (mode == CDDP_HIP_MPC_KEEP_PLAN) {
+    hipLaunchKernelGGL(k_mpc_state, dim3((d.Bp + 255) / 256), dim3(256), 0, h->stream, d, nx, xdev, 1, h->d_Xinit);
+  } else {
+    const int sd = (flags & CDDP_HIP_MPC_SHIFT_DUALS) ? 1 : 0;
+    hipLaunchKernelGGL(k_mpc_shift, dim3(d.NB, nx + nu + (sd ? 2 * m : 0)), dim3(64), 0, h->stream, d, nx, nu, m, sd, h->d_Xinit, h->d_Uinit);
+    if (xdev) hipLaunchKernelGGL(k_mpc_state, dim3((d.Bp + 255) / 256), dim3(256), 0, h->stream, d, nx, xdev, 0, h->d_Xinit);
+  }
+  HIPCHK(hipGetLastError());
+  // the caller's buffer is free again on return (a device x_next of a handle on the caller's own stream is ordered by that stream instead)
+  if (host_x || (x_next && sync_device_x)) HIPCHK(hipStreamSynchronize(h->stream));
+  h->initialized = false;
+  if (mode != CDDP_HIP_MPC_KEEP_PLAN) { h->have_initial = true; h->initial_dirty = true; }
+  if (mode == CDDP_HIP_MPC_SHIFT_PROVIDED) h->has_state = false;
+  return 0;
+}
+
+// the log of cddp_hip_mpc_run: allocated on first use, grown when a longer run asks for it, cleared at the start of every run
+static int in_mpc_log_begin(Inner *h, int steps) {
+  HIPCHK(hipSetDevice(h->device));
+  const size_t B = (size_t)h->d.B, nx = (size_t)h->P.nx, nu = (size_t)h->P.nu;
+  if (h->log_steps < steps) {
+    if (h->d_log_u) { hipFree(h->d_log_u); hipFree(h->d_log_x); hipFree(h->d_log_it); hipFree(h->d_log_st); }
+    h->d_log_u = h->d_log_x = nullptr; h->d_log_it = h->d_log_st = nullptr; h->log_steps = 0;
+    HIPCHK(hipMalloc((void **)&h->d_log_u, B * steps * nu * sizeof(double)));
+    HIPCHK(hipMalloc((void **)&h->d_log_x, B * (steps + 1) * nx * sizeof(double)));
+    HIPCHK(hipMalloc((void **)&h->d_log_it, B * steps * sizeof(int32_t)));
+    HIPCHK(hipMalloc((void **)&h->d_log_st, B * steps * sizeof(int32_t)));
+    h->log_steps = steps;
+  }
+  HIPCHK(hipMemsetAsync(h->d_log_u, 0, B * steps * nu * sizeof(double), h->stream));
+  HIPCHK(hipMemsetAsync(h->d_log_x, 0, B * (steps + 1) * nx * sizeof(double), h->stream));
+  HIPCHK(hipMemsetAsync(h->d_log_it, 0, B * steps * sizeof(int32_t), h->stream));
+  HIPCHK(hipMemsetAsync(h->d_log_st, 0, B * steps * sizeof(int32_t), h->stream));
+  return 0;
+}
+static int in_mpc_log(Inner *h, int steps, int k) {
+  HIPCHK(hipSetDevice(h->device));
+  hipLaunchKernelGGL(k_mpc_log, dim3((h->d.B + 255) / 256), dim3(256), 0, h->stream, h->d, h->P.nx, h->P.nu, steps, k, h->d_Xinit,
+                     h->d_log_u, h->d_log_x, h->d_log_it, h->d_log_st);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+// ONE copy per output: the log is kept in the outputs' own layout (batch-major, this group's trajectories contiguous)
+static int in_mpc_log_fetch(Inner *h, int steps, double *U_applied, double *X_visited, int32_t *iterations, int32_t *status) {
+  HIPCHK(hipSetDevice(h->device));
+  const size_t B = (size_t)h->d.B, nx = (size_t)h->P.nx, nu = (size_t)h->P.nu;
+  if (U_applied) HIPCHK(hipMemcpyAsync(U_applied, h->d_log_u, B * steps * nu * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  if (X_visited) HIPCHK(hipMemcpyAsync(X_visited, h->d_log_x, B * (steps + 1) * nx * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  if (iterations) HIPCHK(hipMemcpyAsync(iterations, h->d_log_it, B * steps * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+  if (status) HIPCHK(hipMemcpyAsync(status, h->d_log_st, B * steps * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  return 0;
+}
+
 
 // ================================================================================================================
 // Public handle: the batch is cut into tile GROUPS (whole 64-trajectory tiles), each an independent Inner solver
@@ -1866,6 +2042,55 @@ int cddp_hip_solve(cddp_hip_handle *h, cddp_hip_stats *stats) {
     }
   }
   return 0;
+}
+
+// ---- device-resident MPC step: the seed of the next solve is made from the current plan where it lies (k_mpc_shift, k_mpc_state) ----
+int cddp_hip_mpc_advance(cddp_hip_handle *h, int mode, int flags, const double *x_next) {
+  if (!h) return fail(-1, "null handle");
+  for (Inner *q : h->g) { int rc = in_mpc_check(q, mode, flags); if (rc) return rc; }   // refusals first: no kernel launched, no state changed
+  { int rc = fork_from_user(h); if (rc) return rc; }
+  for (size_t gi = 0; gi < h->g.size(); ++gi) {
+    int rc = in_mpc_advance(h->g[gi], mode, flags, x_next ? x_next + (size_t)h->b0[gi] * (size_t)h->nx : nullptr, !h->have_user_stream);
+    if (rc) return rc;
+  }
+  return join_to_user(h);
+}
+
+int cddp_hip_mpc_run(cddp_hip_handle *h, int steps, int mode, int flags, double *U_applied, double *X_visited, int32_t *iterations, int32_t *status,
+                     cddp_hip_stats *stats_sum) {
+  if (!h) return fail(-1, "null handle");
+  if (steps <= 0) return fail(-1, "cddp_hip_mpc_run: steps must be positive (got %d)", steps);
+  for (Inner *q : h->g) { int rc = in_mpc_check(q, mode, flags, false); if (rc) return rc; }   // mode and flags are refused before the first solve, not after it
+  for (Inner *q : h->g) if (!q->have_initial) return fail(-1, "cddp_hip_set_initial must be called before cddp_hip_mpc_run");
+  if (stats_sum) std::memset(stats_sum, 0, sizeof(*stats_sum));
+  { int rc = fork_from_user(h); if (rc) return rc; }
+  for (Inner *q : h->g) { int rc = in_mpc_log_begin(q, steps); if (rc) return rc; rc = in_mpc_log(q, steps, -1); if (rc) return rc; }
+  int rc_run = 0;
+  std::string err_run;
+  for (int k = 0; k < steps && !rc_run; ++k) {
+    cddp_hip_stats st;
+    rc_run = cddp_hip_solve(h, stats_sum ? &st : nullptr);
+    if (rc_run) break;
+    if (stats_sum) {
+      stats_sum->solve_ms += st.solve_ms; stats_sum->backward_ms += st.backward_ms; stats_sum->forward_ms += st.forward_ms; stats_sum->update_ms += st.update_ms;
+      stats_sum->sweeps += st.sweeps; stats_sum->rollouts += st.rollouts; stats_sum->rollouts_launched += st.rollouts_launched;
+      stats_sum->traj_iterations += st.traj_iterations; stats_sum->outer_iterations += st.outer_iterations; stats_sum->n_converged += st.n_converged;
+      stats_sum->kernel_launches += st.kernel_launches; stats_sum->timing_detail = st.timing_detail; stats_sum->rollout_steps += st.rollout_steps;
+    }
+    for (Inner *q : h->g) { rc_run = in_mpc_log(q, steps, k); if (rc_run) break; }
+    if (rc_run) break;
+    rc_run = cddp_hip_mpc_advance(h, mode, flags, nullptr);
+  }
+  if (rc_run) err_run = g_err;
+  // the steps completed so far come back even when a solve failed
+  for (size_t gi = 0; gi < h->g.size(); ++gi) {
+    const size_t b0 = (size_t)h->b0[gi];
+    int rc = in_mpc_log_fetch(h->g[gi], steps, U_applied ? U_applied + b0 * steps * h->nu : nullptr, X_visited ? X_visited + b0 * (steps + 1) * h->nx : nullptr,
+                              iterations ? iterations + b0 * steps : nullptr, status ? status + b0 * steps : nullptr);
+    if (rc && !rc_run) return rc;
+  }
+  if (rc_run) { g_err = err_run; return rc_run; }
+  return join_to_user(h);
 }
 
 }  // extern "C"

@@ -781,6 +781,21 @@ class HipBatchSolver : public ISolverAlgorithm {
   }
   // NEW (no reference counterpart): one device-resident batch.
   std::vector<CDDPSolution> solveBatch(CDDP &ctx, const std::vector<Vector> &x0s) { create(ctx, x0s); return collect(ctx, (int)x0s.size()); }
+  // NEW: the device-resident MPC step on the batch of the last initialize() / solveBatch() (cddp_hip_mpc_advance, cddp_hip_mpc_run; mode =
+  // CDDP_HIP_MPC_*, flags = CDDP_HIP_MPC_SHIFT_DUALS | CDDP_HIP_MPC_X_DEVICE).  x_next: batch * nx measured states, or nullptr = x_1 of the plan.
+  void mpcAdvance(int mode, int flags = 0, const double *x_next = nullptr) {
+    if (!h_) throw std::runtime_error("cddp_hip: mpcAdvance needs a resident batch (the plug-in route keeps no plan on the device)");
+    check(cddp_hip_mpc_advance(h_, mode, flags, x_next));
+  }
+  struct MpcLog { std::vector<double> U_applied, X_visited; std::vector<int32_t> iterations, status; cddp_hip_stats stats_sum{}; };   // [b][k][nu], [b][k][nx] (k <= steps), [b][k]
+  MpcLog mpcRun(int steps, int mode, int flags = 0) {
+    if (!h_) throw std::runtime_error("cddp_hip: mpcRun needs a resident batch (the plug-in route keeps no plan on the device)");
+    MpcLog g;
+    const size_t B = (size_t)batch_, K = (size_t)std::max(steps, 0);
+    g.U_applied.assign(B * K * nu_, 0.0); g.X_visited.assign(B * (K + 1) * nx_, 0.0); g.iterations.assign(B * K, 0); g.status.assign(B * K, 0);
+    check(cddp_hip_mpc_run(h_, steps, mode, flags, g.U_applied.data(), g.X_visited.data(), g.iterations.data(), g.status.data(), &g.stats_sum));
+    return g;
+  }
   cddp_hip_stats stats{};
   // Route of LogDDP / MSIPDDP problems (round 5): Auto = an eligible problem (built-in plant with nx <= 8, built-in
   // objective / constraints; MSIPDDP also: no terminal set, and nu = 1 or nx = nu once a path constraint is present) runs on the resident

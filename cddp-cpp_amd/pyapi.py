@@ -162,6 +162,9 @@ GATHER_DTYPE = np.dtype([("final_objective", "f8"), ("iterations", "i4"), ("stat
 
 
 TIMING_ROLLOUT, TIMING_ALL, TIMING_SWEEP = 0, 1, 2
+# cddp_hip_mpc_advance / cddp_hip_mpc_run (include/cddp_hip.h, "device-resident MPC step")
+MPC_KEEP_PLAN, MPC_SHIFT_EXISTING, MPC_SHIFT_PROVIDED = 0, 1, 2
+MPC_SHIFT_DUALS, MPC_X_DEVICE = 1, 2
 
 
 class Stats(C.Structure):
@@ -768,6 +771,8 @@ def load_hip(trig=None):
         lib.cddp_hip_last_error.restype = C.c_char_p
         lib.cddp_hip_status_string.restype = C.c_char_p
         lib.cddp_hip_create.argtypes = [C.POINTER(ProblemStruct), C.c_int, C.c_int, C.POINTER(C.c_void_p)]
+        lib.cddp_hip_mpc_advance.argtypes = MPC_ADVANCE_ARGTYPES; lib.cddp_hip_mpc_advance.restype = C.c_int
+        lib.cddp_hip_mpc_run.argtypes = MPC_RUN_ARGTYPES; lib.cddp_hip_mpc_run.restype = C.c_int
         _hip_libs["lib"] = lib
     lib = _hip_libs["lib"]
     if (trig == "shared") != bool(lib.cddp_hip_trig_shared()):
@@ -775,6 +780,10 @@ def load_hip(trig=None):
                            (trig, HIP_LIB_PATH, "with" if lib.cddp_hip_trig_shared() else "without"))
     return lib
 
+
+# (x_next is a host OR a device address: passed as a plain pointer value)
+MPC_ADVANCE_ARGTYPES = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+MPC_RUN_ARGTYPES = [C.c_void_p, C.c_int, C.c_int, C.c_int, _dp, _dp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(Stats)]
 
 EXPORTED_SYMBOLS = [
     "cddp_hip_default_options", "cddp_hip_abi_version", "cddp_hip_trig_shared", "cddp_hip_last_error", "cddp_hip_device_count",
@@ -787,7 +796,7 @@ EXPORTED_SYMBOLS = [
     "cddp_hip_backward_stacks", "cddp_hip_stacks_create_abi", "cddp_hip_stacks_destroy", "cddp_hip_set_stacks", "cddp_hip_set_defect_stack", "cddp_hip_set_control_box", "cddp_hip_set_hessian_stacks", "cddp_hip_set_constraint_stacks",
     "cddp_hip_stacks_backward", "cddp_hip_stacks_last_kernel_ms", "cddp_hip_stacks_last_sweep_form", "cddp_hip_stacks_factor_cache", "cddp_hip_stacks_get_gains", "cddp_hip_stacks_get_constraint_gains",
     "cddp_hip_stacks_get_scalars", "cddp_hip_set_terminal_equality", "cddp_hip_stacks_get_terminal", "cddp_hip_plugin_solve", "cddp_hip_plugin_solve_terminal", "cddp_hip_plugin_set_host_threads", "cddp_hip_plugin_last_stats", "cddp_hip_model_eval", "cddp_hip_set_options", "cddp_hip_set_initial_state", "cddp_hip_forget_solver_state", "cddp_hip_set_duals", "cddp_hip_set_terminal",
-    "cddp_hip_costate_mode", "cddp_hip_costate_redos",
+    "cddp_hip_costate_mode", "cddp_hip_costate_redos", "cddp_hip_mpc_advance", "cddp_hip_mpc_run",
 ]
 
 
@@ -805,6 +814,7 @@ class HipBatchSolver:
         rc = self.lib.cddp_hip_create(C.byref(problem.c), batch, device, C.byref(self.h))
         self._check(rc)
         self.m = self.lib.cddp_hip_dual_dim(self.h)
+        self._user_stream = False; self._device = int(device)
 
     def _check(self, rc):
         if rc != 0:
@@ -837,6 +847,7 @@ class HipBatchSolver:
 
     def set_stream(self, stream_ptr):
         self._check(self.lib.cddp_hip_set_stream(self.h, C.c_void_p(stream_ptr)))
+        self._user_stream = True
 
     def set_timing_detail(self, detail):
         """TIMING_ROLLOUT (default): solve() brackets the rollout launches only; TIMING_ALL: every class;
@@ -910,6 +921,42 @@ class HipBatchSolver:
         u0 = np.zeros((self.B, self.p.nu)); x1 = np.zeros((self.B, self.p.nx))
         self._check(self.lib.cddp_hip_get_plan_head(self.h, _ptr(u0), _ptr(x1)))
         return u0, x1
+
+    def mpc_advance(self, mode, x_next=None, shift_duals=False):
+        """One MPC step on the device (cddp_hip_mpc_advance): the seed of the next solve from the current plan, without a host copy of it.
+        mode: MPC_KEEP_PLAN (== set_initial_state(x_next)), MPC_SHIFT_EXISTING (== set_initial(x_next, U shifted, X shifted)) or
+        MPC_SHIFT_PROVIDED (== forget_solver_state + the same).  x_next: None = x_1 of the plan; a numpy array (B, nx) = the measured state,
+        uploaded (the step's only transfer); a torch tensor on the handle's device = read in place (float64, contiguous), ordered on the
+        stream given to set_stream, or after a synchronisation of the tensor's current stream when there is none."""
+        flags = MPC_SHIFT_DUALS if shift_duals else 0
+        keep = None
+        if x_next is None:
+            ptr = None
+        elif isinstance(x_next, np.ndarray) or not hasattr(x_next, "data_ptr"):
+            keep = _arr(x_next).reshape(self.B, self.p.nx); ptr = keep.ctypes.data
+        else:
+            import torch
+            if not x_next.is_cuda or x_next.dtype != torch.float64 or tuple(x_next.shape) != (self.B, self.p.nx):
+                raise ValueError("x_next: a float64 device tensor of shape (%d, %d) is expected" % (self.B, self.p.nx))
+            if x_next.device.index != self._device:   # its address would be read as one of the handle's device
+                raise ValueError("x_next lives on device %s, the handle on device %d" % (x_next.device.index, self._device))
+            keep = x_next.contiguous(); ptr = keep.data_ptr(); flags |= MPC_X_DEVICE
+            if not self._user_stream:
+                torch.cuda.current_stream(keep.device).synchronize()
+        self._check(self.lib.cddp_hip_mpc_advance(self.h, int(mode), flags, ptr))
+
+    def mpc_run(self, steps, mode, shift_duals=False):
+        """`steps` closed-loop MPC steps with the model as the plant (cddp_hip_mpc_run): solve, record, advance -- one call, one copy per
+        output.  Returns a dict: U_applied (B, steps, nu), X_visited (B, steps + 1, nx), iterations and status (B, steps, int32), stats
+        (the per-solve Stats added up)."""
+        steps = int(steps)
+        U = np.zeros((self.B, max(steps, 0), self.p.nu)); X = np.zeros((self.B, max(steps, 0) + 1, self.p.nx))
+        it = np.zeros((self.B, max(steps, 0)), dtype=np.int32); st = np.zeros((self.B, max(steps, 0)), dtype=np.int32)
+        stats = Stats()
+        i32 = C.POINTER(C.c_int32)
+        self._check(self.lib.cddp_hip_mpc_run(self.h, steps, int(mode), MPC_SHIFT_DUALS if shift_duals else 0, _ptr(U), _ptr(X),
+                                              it.ctypes.data_as(i32), st.ctypes.data_as(i32), C.byref(stats)))
+        return {"U_applied": U, "X_visited": X, "iterations": it, "status": st, "stats": stats}
 
     def gains(self):
         K = np.zeros((self.B, self.p.N, self.p.nu, self.p.nx)); k = np.zeros((self.B, self.p.N, self.p.nu))

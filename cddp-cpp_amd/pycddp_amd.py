@@ -1065,6 +1065,60 @@ class CDDP:                         # cddp_core.hpp:214-423 / bind_solver.cpp:57
         name = solver_type.value if isinstance(solver_type, SolverType) else str(solver_type)
         return self._solve(name, list(x0s), resident_batch=True)
 
+    def _resident_kind(self, name):
+        """The C-ABI solver id when `_solve` runs `name` on the resident kernels, None when it sends the problem to the plug-in route
+        (the same tests, in the same order, as `_solve`)."""
+        api = _api()
+        if name not in ("CLDDP", "IPDDP", "LogDDP", "MSIPDDP") or self._sys is None or self._needs_host_plugins():
+            return None
+        if name == "LogDDP" and (self._sys.state_dim > 8 or self.logddp_route == "plugin"):
+            return None
+        if name == "MSIPDDP":
+            ms_nx_cap = 13 if self.msipddp_route == "resident" else 8
+            ok = (self._sys.state_dim <= ms_nx_cap and not self._terms
+                  and (not self._cons or self._sys.control_dim == 1 or self._sys.state_dim == self._sys.control_dim))
+            if not ok or self.msipddp_route == "plugin":
+                return None
+        return {"CLDDP": api.SOLVER_CLDDP, "IPDDP": api.SOLVER_IPDDP, "LogDDP": api.SOLVER_LOGDDP, "MSIPDDP": api.SOLVER_MSIPDDP}[name]
+
+    def solve_mpc_batch(self, x0s, steps, solver_type=SolverType.IPDDP, warm_start="provided", shift_duals=False):
+        """NEW (no reference counterpart): `steps` closed-loop MPC steps of one device-resident batch, the model as the plant -- solve, apply
+        u_0, start the next solve at x_1 -- without the plan leaving the device between solves (cddp_hip_mpc_run).  Trajectory i starts at
+        x0s[i]; the first solve is seeded as solve_batch seeds it.  warm_start names how every later solve is seeded:
+          "provided": a NEW solver object given the previous plan shifted by one step (the reference's "warm start with provided trajectory");
+          "existing": the same solver object -- duals, gains, regularisation kept -- given the shifted plan; shift_duals shifts S and Y too;
+          "keep":     the same solver object and the unshifted plan, only the initial state replaced.
+        options.warm_start is switched on for the run (that is what makes a seed a warm start).  Returns a dict: state_trajectory
+        (B, steps + 1, nx) and control_trajectory (B, steps, nu) as executed, iterations (B, steps), status_message (B lists of `steps`
+        strings), solve_time_ms (device time of the solves, added up).  Problems that solve_batch sends to the plug-in route are refused:
+        they have no resident handle to advance."""
+        api = _api()
+        name = solver_type.value if isinstance(solver_type, SolverType) else str(solver_type)
+        modes = {"provided": api.MPC_SHIFT_PROVIDED, "existing": api.MPC_SHIFT_EXISTING, "keep": api.MPC_KEEP_PLAN}
+        if warm_start not in modes:
+            raise ValueError("warm_start must be 'provided', 'existing' or 'keep' (got %r)" % (warm_start,))
+        if self._sys is None:
+            raise RuntimeError("Dynamical system must be set before solving.")
+        kind = self._resident_kind(name)
+        if kind is None:
+            raise NotImplementedError("solve_mpc_batch needs a problem of the resident route (built-in plant, objective and constraints): "
+                                      "solver '%s' with this problem runs on the plug-in route, which keeps no plan on the device" % name)
+        p = self._problem(kind)
+        p.options.warm_start = 1
+        x0s = list(x0s); B = len(x0s)
+        x0 = np.ascontiguousarray(np.stack([np.asarray(x, dtype=np.float64) for x in x0s]))
+        U0 = None if self._U is None else np.ascontiguousarray(np.tile(self._U, (B, 1, 1)))
+        X0 = None if self._X is None else np.ascontiguousarray(np.tile(self._X, (B, 1, 1)))
+        hs = api.HipBatchSolver(p, B)
+        try:
+            hs.set_initial(x0, U0, X0)
+            r = hs.mpc_run(int(steps), modes[warm_start], shift_duals=shift_duals)
+        finally:
+            hs.close()
+        return {"state_trajectory": r["X_visited"], "control_trajectory": r["U_applied"], "iterations": r["iterations"],
+                "status_message": [[api.STATUS_STRINGS[int(s)] for s in row] for row in r["status"]],
+                "solve_time_ms": float(r["stats"].solve_ms)}
+
 
 __all__ = [n for n in dir() if not n.startswith("_") and n not in ("enum", "importlib", "os", "sys", "np")]
 __version__ = "0.1.0"

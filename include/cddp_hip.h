@@ -460,6 +460,41 @@ int cddp_hip_costate_mode(cddp_hip_handle *h);
 /* Deferred solves of this handle that met a non-finite costate row, were discarded and run again on the chain (0 on healthy problems). */
 int cddp_hip_costate_redos(cddp_hip_handle *h);
 
+/* ---- device-resident MPC step --------------------------------------------
+ * Between two solves of a receding-horizon loop the plan does not leave the device: cddp_hip_mpc_advance makes the seed of the next
+ * solve from every trajectory's CURRENT iterate where it lies (a row permutation of the wave-tiled stacks), with no host copy of a
+ * trajectory and no host transposition.  Each mode is, bit for bit, the host sequence named next to it -- the next cddp_hip_solve's
+ * results, trajectory, duals and work counters; in between, cddp_hip_get_trajectory returns the shifted plan (the seed the host sequence
+ * uploads) and, with CDDP_HIP_MPC_SHIFT_DUALS, cddp_hip_get_duals the shifted rows.  An advance is meant to be FOLLOWED BY A SOLVE: the
+ * shift is made in place in every trajectory's live slot, so a second advance without a solve in between shifts the plan a second
+ * time, where the host sequence run twice (it reads the live slot, which only the solve rewrites) would seed the same plan twice.
+ * With x_next NULL, or a device x_next on a stream given by cddp_hip_set_stream, the call returns once its kernels are enqueued on the
+ * handle's stream; the next solve and the getters are ordered behind them as behind every other setter.
+ * "Shifted", per trajectory: X_shifted[t] = X[t+1] (t < N), X_shifted[N] = X[N]; U_shifted[t] = U[t+1] (t < N-1), U_shifted[N-1] = U[N-1];
+ * S and Y like U.  x_next: NULL = X[1] of the current plan (the plant is the model); otherwise the measured state, batch*nx, which
+ * replaces row 0 as cddp_hip_set_initial writes X_[0] = initial_state -- a host pointer (the step's only upload, batch*nx doubles) or,
+ * with CDDP_HIP_MPC_X_DEVICE, a device pointer read on the handle's stream.
+ * Refused, with nothing launched and nothing changed: a handle without a current plan (no cddp_hip_set_initial, or never initialised /
+ * solved), an unknown mode or flag, CDDP_HIP_MPC_SHIFT_DUALS outside CDDP_HIP_MPC_SHIFT_EXISTING or on a problem without path duals.
+ * Not shifted: gains, costates, the MSIPDDP factor cache, filter entries.  (Added after cddp_hip_get_costates; ABI version unchanged.) */
+enum cddp_hip_mpc_mode {
+  CDDP_HIP_MPC_KEEP_PLAN = 0,      /* == cddp_hip_set_initial_state(x_next): plan, duals, gains untouched                    */
+  CDDP_HIP_MPC_SHIFT_EXISTING = 1, /* == cddp_hip_set_initial(x_next, U_shifted, X_shifted): solver state kept               */
+  CDDP_HIP_MPC_SHIFT_PROVIDED = 2  /* == cddp_hip_forget_solver_state + cddp_hip_set_initial(x_next, U_shifted, X_shifted)   */
+};
+enum { CDDP_HIP_MPC_SHIFT_DUALS = 1,   /* SHIFT_EXISTING, IPDDP with path rows: also == cddp_hip_set_duals(S_shifted, Y_shifted) */
+       CDDP_HIP_MPC_X_DEVICE   = 2 };  /* x_next is a DEVICE pointer (batch-major, batch*nx), read on the handle's stream   */
+int cddp_hip_mpc_advance(cddp_hip_handle *h, int mode, int flags, const double *x_next /* batch*nx or NULL */);
+/* The closed loop with the model as the plant: `steps` times { cddp_hip_solve; record u_0, x_1, iterations, status of every trajectory;
+ * cddp_hip_mpc_advance(mode, flags, NULL) }.  The records accumulate in a device log and come back in one copy per output at the end
+ * (any output may be NULL): U_applied[b][k][nu], X_visited[b][k][nx] with X_visited[b][0] the initial state of the first solve and
+ * X_visited[b][k+1] the x_1 of solve k, iterations[b][k], status[b][k].  stats_sum (optional) adds up the per-solve counters and times.
+ * Bitwise the hand-written loop over cddp_hip_solve, cddp_hip_get_plan_head and cddp_hip_mpc_advance.  An error from a solve ends the
+ * run and is returned; the steps completed so far stay in the outputs. */
+int cddp_hip_mpc_run(cddp_hip_handle *h, int steps, int mode, int flags,
+                     double *U_applied /* B*steps*nu */, double *X_visited /* B*(steps+1)*nx */,
+                     int32_t *iterations /* B*steps */, int32_t *status /* B*steps */, cddp_hip_stats *stats_sum);
+
 /* ---- getters (host buffers, batch-major) -------------------------------- */
 int cddp_hip_get_results(cddp_hip_handle *h, cddp_hip_result *results /* batch */);
 /* Head of the plan (round 4): u_0[batch][nu] and x_1[batch][nx] of every trajectory's current iterate -- what a receding-horizon

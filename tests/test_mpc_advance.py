@@ -1,0 +1,354 @@
+"""The device-resident MPC step (cddp_hip_mpc_advance, cddp_hip_mpc_run): between two solves of a receding-horizon loop the plan stays on
+the device.  The contract is BITWISE equality with the host sequence each mode stands for (include/cddp_hip.h):
+  KEEP_PLAN      == set_initial_state(x_next)
+  SHIFT_EXISTING == set_initial(x_next, U shifted, X shifted)                 [+ SHIFT_DUALS == set_duals(S shifted, Y shifted)]
+  SHIFT_PROVIDED == forget_solver_state + set_initial(x_next, U shifted, X shifted)
+Every test runs two handles on one problem, cold-solved from the same x0 / U0: handle A does the host sequence, handle B calls the new entry
+point; every comparison is np.array_equal.  B = 70 is two tiles, the second partial (padding lanes, tile indexing)."""
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+RESULT_FIELDS = ("iterations", "status", "n_backward", "n_forward", "final_objective")
+
+
+def shift(A):
+    """rows 1 .. end, the last one repeated"""
+    return np.ascontiguousarray(np.concatenate([A[:, 1:], A[:, -1:]], axis=1))
+
+
+def same(a, b):
+    return np.array_equal(np.asarray(a), np.asarray(b), equal_nan=np.asarray(a).dtype.kind == "f")
+
+
+def pair(api, p, B, seed, spread=None):
+    """two handles of one problem, cold-solved from the same seed, then warm start switched on (the flag lives in the shared problem object)"""
+    import test_gpu_parity as T
+    x0 = api.batch_x0(p, B, seed, T.spread_for(p) if spread is None else spread)
+    U0 = api.batch_U0(p, B)
+    hs = []
+    for _ in range(2):
+        h = api.HipBatchSolver(p, B); h.set_initial(x0, U0); h.solve(); hs.append(h)
+    assert_same_solve(hs[0], hs[1], "cold")
+    for h in hs:
+        h.set_warm_start(True)
+    return hs[0], hs[1], x0, U0
+
+
+def assert_same_solve(a, b, where, duals=False):
+    ra, rb = a.results(), b.results()
+    for name in RESULT_FIELDS:
+        assert same(ra[name], rb[name]), (where, name)
+    Xa, Ua = a.trajectory(); Xb, Ub = b.trajectory()
+    assert same(Xa, Xb) and same(Ua, Ub), where
+    if duals:
+        for da, db, name in zip(a.duals(), b.duals(), "SYG"):
+            assert same(da, db), (where, name)
+    return ra
+
+
+def host_shift(a, provided, x_next=None, shift_duals=False):
+    """the host sequence of SHIFT_EXISTING / SHIFT_PROVIDED on handle `a`; returns the seed it uploaded"""
+    X, U = a.trajectory()
+    Xs, Us = shift(X), shift(U)
+    if x_next is not None:
+        Xs[:, 0] = x_next
+    if shift_duals:
+        S, Y, _ = a.duals()
+        a.set_duals(shift(S), shift(Y))
+    if provided:
+        a.forget_solver_state()
+    a.set_initial(np.ascontiguousarray(Xs[:, 0]), Us, Xs)
+    return Xs, Us
+
+
+def is_ipddp(api, p):
+    return p.c.solver == api.SOLVER_IPDDP
+
+
+SHIFT_CASES = ["pendulum_ipddp_box", "unicycle_ipddp_box_ball", "pendulum_clddp_box"]
+# x0 spreads of the shift tests.  At the spreads of the parity tests (test_gpu_parity.spread_for) every trajectory of these batches ends its
+# solve on the full step, so all of them would sit in slots 0 / 1.  These wider ones (pendulum: +-3 rad, +-3 rad/s around the start;
+# unicycle: +-0.6 m around the start, clear of the obstacle) leave about one trajectory in seven on a shorter last step (0.5, 0.25, ...), and a
+# shorter step is a trial slot further up (kernels.hpp::trial_slot): the batch holds trajectories in three or more live slots.
+WIDE_SPREAD = {"pendulum_ipddp_box": [3.0, 3.0], "pendulum_clddp_box": [3.0, 3.0], "unicycle_ipddp_box_ball": [0.6, 0.6, 0.1]}
+
+
+def run_shift_rounds(api, case, provided, rounds=3, B=70):
+    import test_gpu_parity as T
+    p = T.make(api, case)
+    a, b, _, _ = pair(api, p, B, 20261201, spread=np.array(WIDE_SPREAD[case]))
+    mode = api.MPC_SHIFT_PROVIDED if provided else api.MPC_SHIFT_EXISTING
+    mixed = []                                 # per advance: the last accepted step sizes present in the batch that advance shifts
+    for k in range(rounds):
+        mixed.append(np.unique(b.results()["alpha_pr"]).tolist())
+        Xs, Us = host_shift(a, provided)
+        b.mpc_advance(mode)
+        Xb, Ub = b.trajectory()
+        assert same(Xb, Xs) and same(Ub, Us), (case, k, "the getter returns the shifted plan")
+        a.solve(); b.solve()
+        assert_same_solve(a, b, (case, k), duals=(not provided) and is_ipddp(api, p))
+    a.close(); b.close()
+    print("%s: accepted step sizes in the batch before each advance: %s" % (case, mixed))
+    # the live slot of a trajectory is the trial slot of its last accepted step (trial_slot(previous slot, index of the step size)): two different
+    # last step sizes WITHIN the batch one advance shifts = trajectories in different live slots in that launch, i.e. the per-lane slot addressing
+    # of the shift kernel is exercised (different values in different rounds only would not show it)
+    assert any(len(m) >= 2 for m in mixed), (case, mixed)
+
+
+@pytest.mark.parametrize("case", SHIFT_CASES)
+def test_shift_provided_is_forget_plus_set_initial(api, case):
+    run_shift_rounds(api, case, provided=True)
+
+
+@pytest.mark.parametrize("case", SHIFT_CASES)
+def test_shift_existing_is_set_initial_of_the_shifted_plan(api, case):
+    run_shift_rounds(api, case, provided=False)
+
+
+@pytest.mark.parametrize("case", ["unicycle_ipddp_box_ball", "pendulum_clddp_box"])
+def test_keep_plan_is_set_initial_state(api, case):
+    import test_gpu_parity as T
+    p = T.make(api, case)
+    a, b, _, _ = pair(api, p, 70, 20261202)
+    for k in range(3):
+        Xa, Ua = a.trajectory()
+        a.set_initial_state(a.plan_head()[1])
+        b.mpc_advance(api.MPC_KEEP_PLAN)
+        Xb, Ub = b.trajectory()
+        Xa[:, 0] = Xa[:, 1]
+        assert same(Xb, Xa) and same(Ub, Ua), (case, k)      # the plan is kept, row 0 is the predicted state
+        a.solve(); b.solve()
+        assert_same_solve(a, b, (case, k), duals=is_ipddp(api, p))
+    a.close(); b.close()
+
+
+def test_shift_duals_is_set_duals_of_the_shifted_rows(api):
+    import test_gpu_parity as T
+    p = T.make(api, "unicycle_ipddp_box_ball")
+    a, b, _, _ = pair(api, p, 70, 20261203)
+    for k in range(3):
+        S, Y, _ = a.duals()
+        host_shift(a, provided=False, shift_duals=True)
+        b.mpc_advance(api.MPC_SHIFT_EXISTING, shift_duals=True)
+        Sb, Yb, _ = b.duals(); Sa, Ya, _ = a.duals()
+        assert same(Sb, shift(S)) and same(Yb, shift(Y)), k
+        assert same(Sb, Sa) and same(Yb, Ya), k
+        a.solve(); b.solve()
+        assert_same_solve(a, b, k, duals=True)
+    a.close(); b.close()
+
+
+@pytest.mark.parametrize("carrier", ["numpy", "torch"])
+def test_measured_state_replaces_row_zero(api, carrier):
+    import test_gpu_parity as T
+    p = T.make(api, "unicycle_ipddp_box_ball")
+    B = 70
+    a, b, _, _ = pair(api, p, B, 20261204)
+    rng = np.random.default_rng(20261204)
+    for k, provided in enumerate((True, False, True)):
+        x1 = a.plan_head()[1]
+        x_next = np.ascontiguousarray(x1 + 1e-3 * rng.standard_normal(x1.shape))
+        Xs, Us = host_shift(a, provided, x_next=x_next)
+        mode = api.MPC_SHIFT_PROVIDED if provided else api.MPC_SHIFT_EXISTING
+        if carrier == "torch":
+            import torch
+            b.mpc_advance(mode, x_next=torch.from_numpy(x_next).to("cuda:0"))
+        else:
+            b.mpc_advance(mode, x_next=x_next)
+        Xb, Ub = b.trajectory()
+        assert same(Xb, Xs) and same(Ub, Us) and same(Xb[:, 0], x_next), k
+        a.solve(); b.solve()
+        assert_same_solve(a, b, k, duals=True)
+    # KEEP_PLAN with a measured state
+    x_next = np.ascontiguousarray(a.plan_head()[1] + 1e-3 * rng.standard_normal((B, p.nx)))
+    a.set_initial_state(x_next)
+    if carrier == "torch":
+        import torch
+        b.mpc_advance(api.MPC_KEEP_PLAN, x_next=torch.from_numpy(x_next).to("cuda:0"))
+    else:
+        b.mpc_advance(api.MPC_KEEP_PLAN, x_next=x_next)
+    assert same(b.trajectory()[0][:, 0], x_next)
+    a.solve(); b.solve()
+    assert_same_solve(a, b, "keep", duals=True)
+    a.close(); b.close()
+
+
+@pytest.mark.parametrize("solver,provided", [("logddp", True), ("msipddp", True), ("msipddp", False)])
+def test_logddp_and_msipddp_handles(api, solver, provided):
+    if solver == "logddp":
+        import test_logddp_device as LG
+        p = LG.make(api, "pendulum_box")
+    else:
+        import test_msipddp_device as MS
+        p, _ = MS.make(api, "pendulum_box")
+    a, b, _, _ = pair(api, p, 70, 20261205, spread=0.1 * np.ones(p.nx))
+    mode = api.MPC_SHIFT_PROVIDED if provided else api.MPC_SHIFT_EXISTING
+    for k in range(2):
+        Xs, Us = host_shift(a, provided)
+        b.mpc_advance(mode)
+        Xb, Ub = b.trajectory()
+        assert same(Xb, Xs) and same(Ub, Us), (solver, k)
+        a.solve(); b.solve()
+        assert_same_solve(a, b, (solver, k), duals=(solver == "msipddp"))
+    a.close(); b.close()
+
+
+def test_two_tile_groups_offset_the_measured_state(api, monkeypatch):
+    import test_gpu_parity as T
+    monkeypatch.setenv("CDDP_HIP_GROUPS", "2")
+    p = T.make(api, "pendulum_ipddp_box")
+    B = 130
+    a, b, _, _ = pair(api, p, B, 20261206)
+    assert a.num_groups() == 2 and b.num_groups() == 2
+    rng = np.random.default_rng(20261206)
+    for k in range(2):
+        x_next = np.ascontiguousarray(a.plan_head()[1] + 1e-3 * rng.standard_normal((B, p.nx)))
+        Xs, Us = host_shift(a, True, x_next=x_next)
+        b.mpc_advance(api.MPC_SHIFT_PROVIDED, x_next=x_next)
+        Xb, Ub = b.trajectory()
+        assert same(Xb, Xs) and same(Ub, Us), k
+        a.solve(); b.solve()
+        assert_same_solve(a, b, k, duals=True)
+    a.close(); b.close()
+
+
+def hand_loop(api, h, steps, mode, shift_duals=False):
+    """cddp_hip_mpc_run written out over solve / get_plan_head / mpc_advance; also returns the seed of every solve after the first"""
+    U = np.zeros((h.B, steps, h.p.nu)); X = np.zeros((h.B, steps + 1, h.p.nx))
+    it = np.zeros((h.B, steps), dtype=np.int32); st = np.zeros((h.B, steps), dtype=np.int32)
+    seeds = []
+    for k in range(steps):
+        h.solve()
+        u0, x1 = h.plan_head(); r = h.results()
+        U[:, k] = u0; X[:, k + 1] = x1; it[:, k] = r["iterations"]; st[:, k] = r["status"]
+        Xp, Up = h.trajectory()
+        seeds.append((shift(Xp), shift(Up)))
+        h.mpc_advance(mode, shift_duals=shift_duals)
+    return U, X, it, st, seeds
+
+
+@pytest.mark.parametrize("case,B,mode_name,shift_duals", [("pendulum_ipddp_box", 4, "provided", False), ("unicycle_ipddp_box_ball", 70, "existing", True),
+                                                          ("pendulum_clddp_box", 70, "keep", False)])
+def test_mpc_run_is_the_hand_written_loop(api, oracle_built, case, B, mode_name, shift_duals):
+    import test_gpu_parity as T
+    p = T.make(api, case)
+    p.options.warm_start = 1
+    mode = {"provided": api.MPC_SHIFT_PROVIDED, "existing": api.MPC_SHIFT_EXISTING, "keep": api.MPC_KEEP_PLAN}[mode_name]
+    steps = 3
+    x0 = api.batch_x0(p, B, 20261207, T.spread_for(p)); U0 = api.batch_U0(p, B)
+    a = api.HipBatchSolver(p, B); a.set_initial(x0, U0)
+    b = api.HipBatchSolver(p, B); b.set_initial(x0, U0)
+    U, X, it, st, seeds = hand_loop(api, a, steps, mode, shift_duals)
+    X[:, 0] = x0
+    r = b.mpc_run(steps, mode, shift_duals=shift_duals)
+    assert same(r["U_applied"], U) and same(r["X_visited"], X) and same(r["iterations"], it) and same(r["status"], st)
+    assert same(r["X_visited"][:, 0], x0)
+    Xa, Ua = a.trajectory(); Xb, Ub = b.trajectory()
+    assert same(Xa, Xb) and same(Ua, Ub)
+    assert r["stats"].traj_iterations == int(it.sum()) and r["stats"].solve_ms > 0.0
+    a.close(); b.close()
+    if case == "pendulum_ipddp_box" and B == 4:
+        # every step of the "provided" loop is a NEW solver object given the shifted plan: the oracle driven the same way
+        for k in range(steps):
+            for i in range(B):
+                o = api.Oracle(p); o.set_warm_start(True)
+                if k == 0:     # (the handle's seed written out: x0 replicated along the horizon, zero controls)
+                    o.set_initial(x0[i], np.zeros((p.N, p.nu)) if U0 is None else U0[i], np.tile(x0[i], (p.N + 1, 1)))
+                else:
+                    Xs, Us = seeds[k - 1]
+                    o.set_initial(Xs[i, 0], Us[i], Xs[i])
+                q = o.solve()
+                assert q["iterations"] == r["iterations"][i, k] and q["status"] == r["status"][i, k], (k, i, q["iterations"], r["iterations"][i, k])
+
+
+def test_refusals_change_nothing(api):
+    import test_gpu_parity as T
+    lib = api.load_hip()
+    p = T.make(api, "pendulum_ipddp_box")
+    B = 70
+    x0 = api.batch_x0(p, B, 20261208, T.spread_for(p)); U0 = api.batch_U0(p, B)
+    a = api.HipBatchSolver(p, B); a.set_initial(x0, U0); a.solve()
+
+    def refused(h, *args, **kw):
+        with pytest.raises(api.HipError):
+            h.mpc_advance(*args, **kw)
+        assert len(lib.cddp_hip_last_error()) > 0
+
+    b = api.HipBatchSolver(p, B)
+    refused(b, api.MPC_SHIFT_PROVIDED)                       # no initial trajectory yet
+    b.set_initial(x0, U0)
+    refused(b, api.MPC_SHIFT_PROVIDED)                       # never solved / initialised: no current plan
+    b.solve()
+    assert_same_solve(a, b, "after the early refusals", duals=True)
+    refused(b, api.MPC_KEEP_PLAN, shift_duals=True)          # SHIFT_DUALS goes with SHIFT_EXISTING only
+    refused(b, api.MPC_SHIFT_PROVIDED, shift_duals=True)
+    refused(b, 7)                                            # unknown mode
+    with pytest.raises(api.HipError):
+        b._check(lib.cddp_hip_mpc_advance(b.h, api.MPC_KEEP_PLAN, 8, None))     # unknown flag
+    with pytest.raises(api.HipError):
+        b.mpc_run(2, 7)
+    a.solve(); b.solve()
+    assert_same_solve(a, b, "after the refusals", duals=True)
+    a.close(); b.close()
+    pc = T.make(api, "pendulum_clddp_box")
+    a = api.HipBatchSolver(pc, B); a.set_initial(x0, U0); a.solve()
+    b = api.HipBatchSolver(pc, B); b.set_initial(x0, U0); b.solve()
+    refused(b, api.MPC_SHIFT_EXISTING, shift_duals=True)     # no path duals on a CLDDP handle
+    a.solve(); b.solve()
+    assert_same_solve(a, b, "clddp after the refusal")
+    a.close(); b.close()
+
+
+def _facade():
+    import importlib.util, os, sys
+    name = "pycddp_amd"
+    if name in sys.modules:
+        return sys.modules[name]
+    spec = importlib.util.spec_from_file_location(name, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "cddp-cpp_amd", "pycddp_amd.py"))
+    mod = importlib.util.module_from_spec(spec); sys.modules[name] = mod; spec.loader.exec_module(mod)
+    return mod
+
+
+def test_facade_solve_mpc_batch(api):
+    import test_gpu_parity as T
+    pycddp = _facade()
+    p = T.make(api, "pendulum_ipddp_box")
+    B, steps = 8, 3
+    x0 = api.batch_x0(p, B, 20261209, T.spread_for(p))
+    o = pycddp.CDDPOptions(); o.verbose = False; o.print_solver_header = False
+    o.max_iterations = p.options.max_iterations; o.tolerance = p.options.tolerance; o.acceptable_tolerance = p.options.acceptable_tolerance
+    o.regularization.initial_value = p.options.reg_initial_value
+    sv = pycddp.CDDP(x0[0], p.x_ref, p.N, p.dt, o)
+    sv.set_dynamical_system(pycddp.Pendulum(p.dt, *list(p.c.model_params)[:3], "euler"))
+    sv.set_objective(pycddp.QuadraticObjective(p.Q, p.R, p.Qf, p.x_ref, [], p.dt))
+    sv.add_constraint("ControlConstraint", pycddp.ControlConstraint(np.array([-20.0]), np.array([20.0])))
+    pp = sv._problem(api.SOLVER_IPDDP); pp.options.warm_start = 1
+    for ws, mode in (("provided", api.MPC_SHIFT_PROVIDED), ("existing", api.MPC_SHIFT_EXISTING), ("keep", api.MPC_KEEP_PLAN)):
+        out = sv.solve_mpc_batch(list(x0), steps, pycddp.SolverType.IPDDP, warm_start=ws)
+        h = api.HipBatchSolver(pp, B); h.set_initial(x0)
+        r = h.mpc_run(steps, mode); h.close()
+        assert same(out["state_trajectory"], r["X_visited"]) and same(out["control_trajectory"], r["U_applied"]) and same(out["iterations"], r["iterations"])
+        assert out["status_message"] == [[api.STATUS_STRINGS[int(s)] for s in row] for row in r["status"]]
+        assert out["state_trajectory"].shape == (B, steps + 1, p.nx) and out["control_trajectory"].shape == (B, steps, p.nu)
+        if ws != "provided":
+            continue
+        # "provided": every step is a fresh solver object seeded with the shifted plan of the one before
+        seed = (x0, None, None)
+        for k in range(steps):
+            f = api.HipBatchSolver(pp, B); f.set_initial(*seed); f.solve()
+            rf = f.results(); X, U = f.trajectory(); f.close()
+            assert same(rf["iterations"], r["iterations"][:, k]) and same(rf["status"], r["status"][:, k]), k
+            assert same(X[:, 1], r["X_visited"][:, k + 1]) and same(U[:, 0], r["U_applied"][:, k]), k
+            Xs, Us = shift(X), shift(U)
+            seed = (np.ascontiguousarray(Xs[:, 0]), Us, Xs)
+    with pytest.raises(ValueError):
+        sv.solve_mpc_batch(list(x0), steps, pycddp.SolverType.IPDDP, warm_start="shifted")
+
+    class HostPendulum(pycddp.Pendulum):     # a Python plant: solve_batch sends it to the plug-in route, which keeps no plan on the device
+        def __init__(self, *a):
+            super().__init__(*a); self.model = None
+    sv.set_dynamical_system(HostPendulum(p.dt, *list(p.c.model_params)[:3], "euler"))
+    with pytest.raises(NotImplementedError):
+        sv.solve_mpc_batch(list(x0), steps, pycddp.SolverType.IPDDP)
