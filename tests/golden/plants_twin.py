@@ -17,12 +17,12 @@ import math
 
 import numpy as np
 
-from spacecraft_twin import HyperDual, _Plant, _mv, cos, cs_jacobian, fd_jacobian, hd_hessian, sin, sqrt, tan, val  # noqa: F401
+from spacecraft_twin import HyperDual, _Plant, _mp, _mv, cos, cs_jacobian, fd_jacobian, hd_hessian, is_mpf, mpow15, msqrt, sin, sqrt, tan, val, vec  # noqa: F401
 
 
 class _AdPlant(_Plant):
     def f(self, x, u, t):
-        return np.array([val(v) for v in self._ad(list(x), list(u))], dtype=np.float64)
+        return vec(self._ad(list(x), list(u)))
 
 
 class DubinsCar(_AdPlant):   # dubins_car.cpp: state [x, y, theta], control [omega]
@@ -78,6 +78,7 @@ class Usv3Dof(_AdPlant):   # usv_3dof.cpp: state [x, y, psi, u, v, r], control [
         X_udot, Y_vdot, Y_rdot, N_vdot, N_rdot = -10.0, -50.0, -5.0, -5.0, -5.0
         X_u, Y_v, Y_r, N_v, N_r = -20.0, -100.0, 0.0, 0.0, -20.0
         M = np.diag([m, m, Iz]) + np.array([[-X_udot, 0.0, 0.0], [0.0, -Y_vdot, -Y_rdot], [0.0, -N_vdot, -N_rdot]])
+        self.M = M
         self.Minv = np.linalg.inv(M).tolist()
         self.D = [[-X_u, 0.0, 0.0], [0.0, -Y_v, -Y_r], [0.0, -N_v, -N_r]]
         self.m_x, self.m_y, self.m_yr = m - X_udot, m - Y_vdot, -Y_rdot
@@ -88,7 +89,8 @@ class Usv3Dof(_AdPlant):   # usv_3dof.cpp: state [x, y, psi, u, v, r], control [
         nu = [u, v, r]
         C = [[0.0, 0.0, -self.m_y * v - self.m_yr * r], [0.0, 0.0, self.m_x * u], [self.m_y * v + self.m_yr * r, -self.m_x * u, 0.0]]
         Cnu, Dnu = _mv(C, nu), _mv(self.D, nu)
-        return [c * u - s * v, s * u + c * v, r] + _mv(self.Minv, [tau[i] - Cnu[i] - Dnu[i] for i in range(3)])
+        Minv = (_mp.matrix(self.M.tolist()) ** -1).tolist() if is_mpf(list(x) + list(tau)) else self.Minv   # 60 digits: the exact inverse
+        return [c * u - s * v, s * u + c * v, r] + _mv(Minv, [tau[i] - Cnu[i] - Dnu[i] for i in range(3)])
 
     def hess(self, x, u, t):   # the control Hessian is a zero override (:237-246)
         Fxx, _, Fux = _Plant.hess(self, x, u, t)
@@ -108,7 +110,7 @@ class Forklift(_Plant):   # forklift.cpp: DISCRETE; state [x, y, theta, v, delta
         return [x[0] + h * v * cos(x[2]), x[1] + h * v * sin(x[2]), x[2] + h * v * tan(self.sign * x[4]) / L, x[3] + h * u[0], x[4] + h * u[1]]
 
     def step(self, x, u, t):
-        return np.array([val(v) for v in self._ad(list(x), list(u))], dtype=np.float64)
+        return vec(self._ad(list(x), list(u)))
 
     def jac(self, x, u, t):   # :50-87
         A, B = _Plant.jac(self, x, u, t)
@@ -128,8 +130,8 @@ class SpacecraftLinearFuel:   # spacecraft_linear_fuel.cpp: state [x, y, z, vx, 
     def f(self, x, u, t):
         n = self.n; n2 = n * n; mass = x[6]
         t2 = u[0] * u[0] + u[1] * u[1] + u[2] * u[2]
-        return np.array([x[3], x[4], x[5], 2.0 * n * x[4] + 3.0 * n2 * x[0] + u[0] / mass, -2.0 * n * x[3] + u[1] / mass,
-                         -n2 * x[2] + u[2] / mass, -math.sqrt(t2 + self.eps) / (self.isp * self.g0), 0.5 * t2], dtype=np.float64)
+        return vec([x[3], x[4], x[5], 2.0 * n * x[4] + 3.0 * n2 * x[0] + u[0] / mass, -2.0 * n * x[3] + u[1] / mass,
+                    -n2 * x[2] + u[2] / mass, -msqrt(t2 + self.eps) / (self.isp * self.g0), 0.5 * t2])
 
     def jac(self, x, u, t):
         return fd_jacobian(lambda s: self.f(s, u, t), x), fd_jacobian(lambda c: self.f(x, c, t), u)
@@ -167,15 +169,15 @@ class SpacecraftNonlinear:   # spacecraft_nonlinear.cpp: state [p, v, r0, theta,
         self.mass, self.mu = float(mass), float(mu)
 
     def f(self, x, u, t):
-        px, py, pz, vx, vy, vz, r0, _, dr0, dth = (float(v) for v in x)
+        px, py, pz, vx, vy, vz, r0, _, dr0, dth = x if is_mpf(x) else (float(v) for v in x)
         mu = self.mu
-        den = math.pow((r0 + px) ** 2 + py * py + pz * pz, 1.5)
+        den = mpow15((r0 + px) ** 2 + py * py + pz * pz)
         ddr0 = -mu / (r0 * r0) + r0 * dth * dth
         ddth = -2.0 * dr0 * dth / r0
-        return np.array([vx, vy, vz,
-                         2.0 * dth * vy + ddth * py + dth * dth * px - mu * (px + r0) / den + mu / (r0 * r0) + u[0] / self.mass,
-                         -2.0 * dth * vx - ddth * px + dth * dth * py - mu * py / den + u[1] / self.mass,
-                         -mu * pz / den + u[2] / self.mass, dr0, dth, ddr0, ddth], dtype=np.float64)
+        return vec([vx, vy, vz,
+                    2.0 * dth * vy + ddth * py + dth * dth * px - mu * (px + r0) / den + mu / (r0 * r0) + u[0] / self.mass,
+                    -2.0 * dth * vx - ddth * px + dth * dth * py - mu * py / den + u[1] / self.mass,
+                    -mu * pz / den + u[2] / self.mass, dr0, dth, ddr0, ddth])
 
     def jac(self, x, u, t):
         return fd_jacobian(lambda s: self.f(s, u, t), x), fd_jacobian(lambda c: self.f(x, c, t), u)

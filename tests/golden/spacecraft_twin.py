@@ -7,10 +7,18 @@ Derivatives, as the reference takes them:
     subtraction, no truncation error: autodiff's value to rounding), Hessians by hyper-dual numbers (exact second derivatives);
   * finite-difference plants (two-body, 2-D lander): central differences, h = 2e-5 (helper.hpp:96), of this module's own f;
     the lander's cross Hessian is the base-class autodiff default on ITS autodiff expression (thrust = u0, no max_thrust factor).
+On mpmath numbers f, jac and hess give the same quantities at the working precision: the autodiff expression on Jets (second-order
+Taylor numbers of mpmath components), the central differences at h = 1e-20, i.e. the derivative they approximate.
 """
 import math
 
 import numpy as np
+
+try:   # the arbitrary-precision branch of the dispatch below (tests/plant_probe.py: the plants' values at 60 digits)
+    import mpmath as _mp
+    _MPF = _mp.mpf
+except ImportError:   # the twin itself needs numpy only
+    _mp, _MPF = None, ()
 
 
 class HyperDual:
@@ -54,34 +62,149 @@ class HyperDual:
         return HyperDual.lift(o) / self
 
 
+class Jet:
+    """Value, gradient and Hessian of an expression carried forward together (second-order Taylor arithmetic), sparse: g and h hold
+    only the variables an intermediate depends on, h the pairs (i, j) with i <= j.  The components are of any scalar type: on mpmath
+    numbers one evaluation gives every first and second derivative at the working precision (the hyper-dual rules, all pairs at once)."""
+    __slots__ = ("a", "g", "h")
+    __array_ufunc__ = None
+
+    def __init__(self, a, g=None, h=None):
+        self.a, self.g, self.h = a, g or {}, h or {}
+
+    @staticmethod
+    def _sum(p, q):
+        r = dict(p)
+        for k, v in q.items():
+            r[k] = r[k] + v if k in r else v
+        return r
+
+    def __add__(self, o):
+        if not isinstance(o, Jet):
+            return Jet(self.a + o, self.g, self.h)
+        return Jet(self.a + o.a, Jet._sum(self.g, o.g), Jet._sum(self.h, o.h))
+    __radd__ = __add__
+
+    def __neg__(self):
+        return Jet(-self.a, {k: -v for k, v in self.g.items()}, {k: -v for k, v in self.h.items()})
+
+    def __sub__(self, o):
+        return self + (-o)
+
+    def __rsub__(self, o):
+        return (-self) + o
+
+    def __mul__(self, o):
+        if not isinstance(o, Jet):
+            return Jet(self.a * o, {k: v * o for k, v in self.g.items()}, {k: v * o for k, v in self.h.items()})
+        g = Jet._sum({k: v * o.a for k, v in self.g.items()}, {k: self.a * v for k, v in o.g.items()})
+        h = Jet._sum({k: v * o.a for k, v in self.h.items()}, {k: self.a * v for k, v in o.h.items()})
+        for i, p in self.g.items():
+            for j, q in o.g.items():
+                k = (i, j) if i <= j else (j, i)
+                t = 2.0 * (p * q) if i == j else p * q
+                h[k] = h[k] + t if k in h else t
+        return Jet(self.a * o.a, g, h)
+    __rmul__ = __mul__
+
+    def unary(self, f0, f1, f2):
+        h = {k: f1 * v for k, v in self.h.items()}
+        for i, p in self.g.items():
+            for j, q in self.g.items():
+                if i <= j:
+                    t = f2 * (p * q)
+                    h[(i, j)] = h[(i, j)] + t if (i, j) in h else t
+        return Jet(f0, {k: f1 * v for k, v in self.g.items()}, h)
+
+    def __truediv__(self, o):
+        if not isinstance(o, Jet):
+            return self * (1.0 / o)
+        return self * o.unary(1.0 / o.a, -1.0 / (o.a * o.a), 2.0 / (o.a * o.a * o.a))
+
+    def __rtruediv__(self, o):
+        return self.unary(1.0 / self.a, -1.0 / (self.a * self.a), 2.0 / (self.a * self.a * self.a)) * o
+
+
 def val(v):
-    if isinstance(v, HyperDual):
+    if isinstance(v, (HyperDual, Jet)):
         return v.a
+    if isinstance(v, _MPF):
+        return v
     return v.real if isinstance(v, complex) or np.iscomplexobj(v) else v
 
 
 def sin(v):
+    if isinstance(v, _MPF):
+        return _mp.sin(v)
+    if isinstance(v, Jet):
+        s, c = msin(v.a), mcos(v.a); return v.unary(s, c, -s)
     if isinstance(v, HyperDual):
         return v.unary(math.sin(v.a), math.cos(v.a), -math.sin(v.a))
     return np.sin(v)
 
 
 def cos(v):
+    if isinstance(v, _MPF):
+        return _mp.cos(v)
+    if isinstance(v, Jet):
+        s, c = msin(v.a), mcos(v.a); return v.unary(c, -s, -c)
     if isinstance(v, HyperDual):
         return v.unary(math.cos(v.a), -math.sin(v.a), -math.cos(v.a))
     return np.cos(v)
 
 
 def tan(v):
+    if isinstance(v, _MPF):
+        return _mp.tan(v)
+    if isinstance(v, Jet):
+        t = mtan(v.a); return v.unary(t, 1.0 + t * t, 2.0 * t * (1.0 + t * t))
     if isinstance(v, HyperDual):
         t = math.tan(v.a); return v.unary(t, 1.0 + t * t, 2.0 * t * (1.0 + t * t))
     return np.tan(v)
 
 
 def sqrt(v):
+    if isinstance(v, _MPF):
+        return _mp.sqrt(v)
+    if isinstance(v, Jet):
+        r = msqrt(v.a); return v.unary(r, 0.5 / r, -0.25 / (v.a * r))
     if isinstance(v, HyperDual):
         r = math.sqrt(v.a); return v.unary(r, 0.5 / r, -0.25 / (v.a * r))
     return np.sqrt(v)
+
+
+def is_mpf(seq):
+    return any(isinstance(val(v), _MPF) for v in seq)
+
+
+def vec(vals):
+    """The plants' return value: a float64 vector, or -- on mpmath numbers -- the list as it stands."""
+    vals = [val(v) for v in vals]
+    return vals if is_mpf(vals) else np.array(vals, dtype=np.float64)
+
+
+# Two families on purpose: sin / cos / tan / sqrt above are what the autodiff expressions (_ad) are written in -- numpy's functions on
+# float64 and complex128 (the complex step needs them), the derivative rules on HyperDual and Jet.  msin / mcos / mtan / msqrt / mpow15
+# are what the plain value expressions (f of the finite-difference plants, originally math.sin ...) and the derivative rules themselves
+# are written in: the C library's functions on a float, so that those values stay what they were, mpmath's on an mpf.
+def msin(v):
+    return _mp.sin(v) if isinstance(v, _MPF) else math.sin(v)
+
+
+def mcos(v):
+    return _mp.cos(v) if isinstance(v, _MPF) else math.cos(v)
+
+
+def mtan(v):
+    return _mp.tan(v) if isinstance(v, _MPF) else math.tan(v)
+
+
+def msqrt(v):
+    return _mp.sqrt(v) if isinstance(v, _MPF) else math.sqrt(v)
+
+
+def mpow15(v):
+    return v * _mp.sqrt(v) if isinstance(v, _MPF) else math.pow(v, 1.5)
 
 
 def _mv(M, v):
@@ -116,8 +239,30 @@ def hd_hessian(f, z):
     return out
 
 
+def jet_derivs(f, z):
+    """J[i, a] and H[i, a, b] of every output of f w.r.t. z from one evaluation on Jets, in the type of z's entries (object arrays of
+    mpmath numbers, exact zeros as 0)."""
+    n = len(z)
+    r = [v if isinstance(v, Jet) else Jet(v) for v in f([Jet(v, {j: 1.0}) for j, v in enumerate(z)])]
+    dt = object if is_mpf(z) else np.float64
+    J, H = np.zeros((len(r), n), dtype=dt), np.zeros((len(r), n, n), dtype=dt)
+    for i, v in enumerate(r):
+        for a, d in v.g.items():
+            J[i, a] = d
+        for (a, b), d in v.h.items():
+            H[i, a, b] = H[i, b, a] = d
+    return J, H
+
+
 def fd_jacobian(f, z, h=2e-5):
-    """helper.hpp:96 finite_difference_jacobian, central differences."""
+    """helper.hpp:96 finite_difference_jacobian, central differences.  On mpmath numbers: the derivative those differences approximate
+    (h = 1e-20 at 60 digits: truncation and rounding both below 1e-38 of the function's scale)."""
+    if is_mpf(z):
+        z = list(z); h = _MPF(10) ** -20; cols = []
+        for i in range(len(z)):
+            fp = f(z[:i] + [z[i] + h] + z[i + 1:]); fm = f(z[:i] + [z[i] - h] + z[i + 1:])
+            cols.append([(p - m) / (2 * h) for p, m in zip(fp, fm)])
+        return np.array(cols, dtype=object).T
     z = np.asarray(z, dtype=np.float64); zp = z.copy(); cols = []
     for i in range(z.size):
         zp[i] = z[i] + h; fp = np.asarray(f(zp), dtype=np.float64)
@@ -135,11 +280,13 @@ class _Plant:
         x, u = self._split(z); return self._ad(x, u)
 
     def jac(self, x, u, t):
-        J = cs_jacobian(self._adz, np.concatenate([x, u]))
+        z = list(x) + list(u)
+        J = jet_derivs(self._adz, z)[0] if is_mpf(z) else cs_jacobian(self._adz, np.concatenate([x, u]))
         return J[:, :self.nx], J[:, self.nx:]
 
     def hess(self, x, u, t):
-        H = hd_hessian(self._adz, np.concatenate([x, u]))
+        z = list(x) + list(u)
+        H = jet_derivs(self._adz, z)[1] if is_mpf(z) else hd_hessian(self._adz, np.concatenate([x, u]))
         n = self.nx
         return H[:, :n, :n].copy(), H[:, n:, n:].copy(), H[:, n:, :n].copy()
 
@@ -150,12 +297,16 @@ class _Attitude(_Plant):
         self.Iinv = np.linalg.inv(self.I)
 
     def _rates(self, w, tau):   # I^-1 (-skew(w) (I w) + tau)
+        if is_mpf(list(w) + list(tau)):   # 60 digits: the inverse of the float64 inertia itself, not its float64 rounding
+            I = _mp.matrix(self.I.tolist()); h = _mv(I.tolist(), w)
+            v = [w[2] * h[1] - w[1] * h[2] + tau[0], w[0] * h[2] - w[2] * h[0] + tau[1], w[1] * h[0] - w[0] * h[1] + tau[2]]
+            return _mv((I ** -1).tolist(), v)
         h = _mv(self.I.tolist(), w)
         v = [w[2] * h[1] - w[1] * h[2] + tau[0], w[0] * h[2] - w[2] * h[0] + tau[1], w[1] * h[0] - w[0] * h[1] + tau[2]]
         return _mv(self.Iinv.tolist(), v)
 
     def f(self, x, u, t):
-        return np.array([val(v) for v in self._ad(list(x), list(u))], dtype=np.float64)
+        return vec(self._ad(list(x), list(u)))
 
 
 class EulerAttitude(_Attitude):   # euler_attitude.cpp:33-52 / .hpp:159-180, ZYX [psi, theta, phi]
@@ -181,6 +332,10 @@ class QuaternionAttitude(_Attitude):   # quaternion_attitude.cpp:33-62 (value: n
         return self._kin(x[0:4], x[4:7]) + self._rates(x[4:7], u)
 
     def f(self, x, u, t):
+        if is_mpf(x):
+            n = _mp.sqrt(x[0] * x[0] + x[1] * x[1] + x[2] * x[2] + x[3] * x[3])
+            q = [v / n for v in x[0:4]] if n > 1e-9 else [_MPF(1), _MPF(0), _MPF(0), _MPF(0)]
+            return self._kin(q, list(x[4:7])) + self._rates(list(x[4:7]), list(u))
         q = np.asarray(x[0:4], dtype=np.float64)
         n = float(np.linalg.norm(q))
         q = q / n if n > 1e-9 else np.array([1.0, 0.0, 0.0, 0.0])
@@ -205,9 +360,9 @@ class SpacecraftTwobody:   # spacecraft_twobody.cpp:15-74
         self.mu, self.mass = float(mu), float(mass)
 
     def f(self, x, u, t):
-        r = math.sqrt(x[0] * x[0] + x[1] * x[1] + x[2] * x[2])
+        r = msqrt(x[0] * x[0] + x[1] * x[1] + x[2] * x[2])
         r3 = r * r * r
-        return np.array([x[3], x[4], x[5]] + [-self.mu * x[i] / r3 + u[i] / self.mass for i in range(3)], dtype=np.float64)
+        return vec([x[3], x[4], x[5]] + [-self.mu * x[i] / r3 + u[i] / self.mass for i in range(3)])
 
     def jac(self, x, u, t):
         return fd_jacobian(lambda s: self.f(s, u, t), x), fd_jacobian(lambda c: self.f(x, c, t), u)
@@ -227,8 +382,8 @@ class SpacecraftLanding2D(_Plant):   # spacecraft_landing2d.cpp:20-112, state [x
     def f(self, x, u, t):
         a = u[1] + x[4]
         thrust = self.max_thrust * u[0]
-        T = -self.length / 2.0 * thrust * math.sin(u[1])
-        return np.array([x[1], thrust * math.sin(a) / self.mass, x[3], thrust * math.cos(a) / self.mass - self.g, x[5], T / self.inertia])
+        T = -self.length / 2.0 * thrust * msin(u[1])
+        return vec([x[1], thrust * msin(a) / self.mass, x[3], thrust * mcos(a) / self.mass - self.g, x[5], T / self.inertia])
 
     def _ad(self, x, u):   # :112+, the expression the base-class cross Hessian differentiates
         a = u[1] + x[4]
