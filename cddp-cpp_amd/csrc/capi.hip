@@ -13,6 +13,7 @@
 #include <map>
 
 #include "launch.hpp"
+#include "plant.hpp"
 
 // 1 when a[0] > a[1] > ... > a[n - 1] (NaN-free): the ladders cddp_hip_build_alphas makes; DevBuf::ladder_sorted
 static int ladder_strictly_decreasing(const double *a, int n) {
@@ -2090,6 +2091,249 @@ int cddp_hip_mpc_run(cddp_hip_handle *h, int steps, int mode, int flags, double 
     if (rc && !rc_run) return rc;
   }
   if (rc_run) { g_err = err_run; return rc_run; }
+  return join_to_user(h);
+}
+
+}  // extern "C" (reopened below)
+
+// ================================================================================================================
+// Device-resident plant (include/cddp_hip.h "closed loop against a separate plant"; kernels: inst_plant.hip).
+// The object owns the derived parameter blocks, the saturation box and the staging buffers of its entry points; a handle it is
+// used with is only read (cddp_hip_track_plan) or driven through its own entries (cddp_hip_mpc_run_plant).
+// ================================================================================================================
+struct cddp_hip_plant {
+  PlantDev pd;                       // params / lower / upper point into d_params / d_box
+  int B = 0, device = 0;
+  hipStream_t stream = nullptr;      // cddp_hip_plant_step
+  double *d_params = nullptr, *d_box = nullptr;
+  double *d_stage = nullptr;         // [B][nx] batch-major: x_next of an MPC step (what k_mpc_state consumes) / x0 of a tracking rollout
+  double *d_io = nullptr;            // cddp_hip_plant_step with host pointers: x | u | w | x_next
+  double *d_W = nullptr; size_t W_cap = 0;                       // disturbances of a run / a tracking rollout, uploaded once
+  double *d_trX = nullptr, *d_trU = nullptr; int tr_N = -1;      // wave-tiled logs of cddp_hip_track_plan (whole batch)
+};
+
+namespace {
+
+// the descriptor checks of cddp_hip_plant_create, in the documented order; none of them looks at a device.
+// blocks: the derived parameter blocks, 32 doubles each (one, or one per trajectory)
+int plant_check(const cddp_hip_plant_desc *c, int batch, std::vector<double> &blocks) {
+  const char *who = "cddp_hip_plant_create";
+  if (c->abi_version != CDDP_HIP_ABI_VERSION) return fail(-2, "%s: ABI version mismatch: got %d want %d", who, c->abi_version, CDDP_HIP_ABI_VERSION);
+  int mnx = 0, mnu = 0, discrete = 0;
+  if (plant_model_dims(c->model, &mnx, &mnu, &discrete)) return fail(-2, "%s: unknown model id %d", who, c->model);
+  if (c->integrator < CDDP_HIP_EULER || c->integrator > CDDP_HIP_RK4) return fail(-2, "%s: unknown integrator %d", who, c->integrator);
+  const bool lti = c->model == CDDP_HIP_MODEL_LTI;
+  if (lti) {
+    if (!plant_lti_has(c->nx, c->nu)) return fail(-2, "%s: the LTI plant exists for (nx, nu) = (1, 1) and (2, 1) (got nx = %d, nu = %d)", who, c->nx, c->nu);
+  } else if (c->nx != mnx || c->nu != mnu) {
+    return fail(-2, "%s: model id %d has nx = %d, nu = %d (got nx = %d, nu = %d)", who, c->model, mnx, mnu, c->nx, c->nu);
+  }
+  if (c->substeps < 1) return fail(-2, "%s: substeps must be at least 1 (got %d)", who, c->substeps);
+  if (c->substeps > 1 && discrete) return fail(-2, "%s: substeps = %d on a discrete plant (model id %d): its step is h = dt by definition", who, c->substeps, c->model);
+  if (!(c->dt > 0.0)) return fail(-2, "%s: dt must be positive (got %g)", who, c->dt);
+  if ((c->u_lower == nullptr) != (c->u_upper == nullptr)) return fail(-2, "%s: u_lower and u_upper come as a pair (u_%s is NULL)", who, c->u_lower ? "upper" : "lower");
+  if (c->u_lower)
+    for (int i = 0; i < c->nu; ++i)
+      if (!(c->u_lower[i] <= c->u_upper[i])) return fail(-2, "%s: u_lower[%d] = %g is not below u_upper[%d] = %g", who, i, c->u_lower[i], i, c->u_upper[i]);
+  if (lti) {
+    if (!c->lti_A || !c->lti_B) return fail(-2, "%s: LTI plant needs lti_A and lti_B", who);
+    if (c->params_per_trajectory) return fail(-2, "%s: LTI plant: lti_A / lti_B are shared by the batch (params_per_trajectory is not available)", who);
+    blocks.assign(32, 0.0);
+    for (int i = 0; i < c->nx * c->nx; ++i) blocks[i] = c->lti_A[i];
+    for (int i = 0; i < c->nx * c->nu; ++i) blocks[c->nx * c->nx + i] = c->lti_B[i];
+    blocks[c->nx * c->nx + c->nx * c->nu] = c->dt;
+    return 0;
+  }
+  if (!c->model_params) return fail(-2, "%s: model_params is NULL", who);
+  const int nblk = c->params_per_trajectory ? batch : 1;
+  blocks.assign((size_t)nblk * 32, 0.0);
+  for (int b = 0; b < nblk; ++b) {
+    std::string err;
+    double *mp = &blocks[(size_t)b * 32];
+    if (cddp_host_model_params(c->model, c->nx, c->nu, c->model_params + (size_t)b * CDDP_HIP_MAX_MODEL_PARAMS, mp, err))
+      return c->params_per_trajectory ? fail(-2, "%s: trajectory %d: %s", who, b, err.c_str()) : fail(-2, "%s: %s", who, err.c_str());
+    if (c->model == CDDP_HIP_MODEL_CAR) mp[1] = c->dt;        // discrete plants: the timestep travels in the block (flatten())
+    if (c->model == CDDP_HIP_MODEL_FORKLIFT) mp[3] = c->dt;
+  }
+  return 0;
+}
+
+int plant_free(cddp_hip_plant *p) {
+  hipSetDevice(p->device);
+  if (p->stream) { hipStreamSynchronize(p->stream); hipStreamDestroy(p->stream); }
+  double *bufs[] = {p->d_params, p->d_box, p->d_stage, p->d_io, p->d_W, p->d_trX, p->d_trU};
+  for (double *q : bufs) if (q) hipFree(q);
+  delete p;
+  return 0;
+}
+
+// the refusals the two handle entries share; nothing is launched before they have passed
+int plant_fits(const char *who, cddp_hip_handle *h, cddp_hip_plant *p) {
+  if (!h) return fail(-1, "%s: null handle", who);
+  if (!p) return fail(-1, "%s: null plant", who);
+  if (p->pd.nx != h->nx || p->pd.nu != h->nu) return fail(-2, "%s: the plant has nx = %d, nu = %d, the handle nx = %d, nu = %d", who, p->pd.nx, p->pd.nu, h->nx, h->nu);
+  if (p->B != h->B) return fail(-2, "%s: the plant was created for a batch of %d, the handle for %d", who, p->B, h->B);
+  if (p->device != h->device) return fail(-2, "%s: the plant lives on device %d, the handle on device %d", who, p->device, h->device);
+  return 0;
+}
+
+// disturbances: one synchronous upload into the plant's buffer (grown on demand) before anything of the call is enqueued
+int plant_upload_W(cddp_hip_plant *p, const double *W, size_t n) {
+  if (p->W_cap < n) {
+    if (p->d_W) hipFree(p->d_W);
+    p->d_W = nullptr; p->W_cap = 0;
+    HIPCHK(hipMalloc((void **)&p->d_W, n * sizeof(double)));
+    p->W_cap = n;
+  }
+  HIPCHK(hipMemcpy(p->d_W, W, n * sizeof(double), hipMemcpyHostToDevice));
+  return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int cddp_hip_plant_create(const cddp_hip_plant_desc *desc, int batch, int device, cddp_hip_plant **out) {
+  if (!desc || !out) return fail(-1, "cddp_hip_plant_create: null argument");
+  if (batch <= 0) return fail(-1, "cddp_hip_plant_create: batch must be positive");
+  std::vector<double> blocks;
+  { int rc = plant_check(desc, batch, blocks); if (rc) return rc; }
+  const int ndev = cddp_hip_device_count();
+  if (ndev <= 0) return fail(-20, "no HIP device available: the cddp_hip plant has no CPU fallback (cddp_hip_model_eval is the host plant)");
+  if (device < 0 || device >= ndev) return fail(-1, "device %d out of range (%d devices)", device, ndev);
+  HIPCHK(hipSetDevice(device));
+  cddp_hip_plant *p = new cddp_hip_plant();
+  const int nx = desc->nx, nu = desc->nu, Bp = (batch + 63) / 64 * 64, per = desc->params_per_trajectory ? 1 : 0;
+  p->B = batch; p->device = device;
+  PlantDev &pd = p->pd;
+  std::memset(&pd, 0, sizeof(pd));
+  pd.model = desc->model; pd.integrator = desc->integrator; pd.substeps = desc->substeps; pd.nx = nx; pd.nu = nu; pd.per_traj = per; pd.Bp = Bp;
+  pd.h = desc->dt / (double)desc->substeps;
+  std::vector<double> hp;
+  if (per) {   // parameter-major [32][Bp]: a wavefront loads entry i of its 64 trajectories as one line
+    hp.assign((size_t)32 * Bp, 0.0);
+    for (int b = 0; b < batch; ++b) for (int i = 0; i < 32; ++i) hp[(size_t)i * Bp + b] = blocks[(size_t)b * 32 + i];
+  } else hp = blocks;
+  hipError_t e = hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking);
+  if (e == hipSuccess) e = hipMalloc((void **)&p->d_params, hp.size() * sizeof(double));
+  if (e == hipSuccess) e = hipMemcpy(p->d_params, hp.data(), hp.size() * sizeof(double), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMalloc((void **)&p->d_stage, (size_t)batch * nx * sizeof(double));
+  if (e == hipSuccess && desc->u_lower) {
+    std::vector<double> box((size_t)2 * nu);
+    for (int i = 0; i < nu; ++i) { box[i] = desc->u_lower[i]; box[nu + i] = desc->u_upper[i]; }
+    e = hipMalloc((void **)&p->d_box, box.size() * sizeof(double));
+    if (e == hipSuccess) e = hipMemcpy(p->d_box, box.data(), box.size() * sizeof(double), hipMemcpyHostToDevice);
+  }
+  if (e != hipSuccess) { plant_free(p); return fail(-10, "cddp_hip_plant_create: %s", hipGetErrorString(e)); }
+  pd.params = p->d_params;
+  if (p->d_box) { pd.lower = p->d_box; pd.upper = p->d_box + nu; }
+  *out = p;
+  return 0;
+}
+
+int cddp_hip_plant_destroy(cddp_hip_plant *p) { return p ? plant_free(p) : 0; }
+
+int cddp_hip_plant_step(cddp_hip_plant *p, int flags, const double *x, const double *u, const double *w, double *x_next) {
+  if (!p) return fail(-1, "cddp_hip_plant_step: null plant");
+  if (!x || !u || !x_next) return fail(-1, "cddp_hip_plant_step: null argument");
+  if (flags & ~CDDP_HIP_PLANT_DEVICE) return fail(-2, "cddp_hip_plant_step: unknown flag bits 0x%x", flags);
+  HIPCHK(hipSetDevice(p->device));
+  const size_t nX = (size_t)p->B * p->pd.nx, nU = (size_t)p->B * p->pd.nu;
+  if (flags & CDDP_HIP_PLANT_DEVICE) {
+    HIPCHK(plant_launch_step(p->pd, p->B, 0, x, u, w, x_next, p->stream));
+    HIPCHK(hipStreamSynchronize(p->stream));
+    return 0;
+  }
+  if (!p->d_io) HIPCHK(hipMalloc((void **)&p->d_io, (3 * nX + nU) * sizeof(double)));
+  double *dx = p->d_io, *du = dx + nX, *dw = du + nU, *dn = dw + nX;
+  HIPCHK(hipMemcpyAsync(dx, x, nX * sizeof(double), hipMemcpyHostToDevice, p->stream));
+  HIPCHK(hipMemcpyAsync(du, u, nU * sizeof(double), hipMemcpyHostToDevice, p->stream));
+  if (w) HIPCHK(hipMemcpyAsync(dw, w, nX * sizeof(double), hipMemcpyHostToDevice, p->stream));
+  HIPCHK(plant_launch_step(p->pd, p->B, 0, dx, du, w ? dw : nullptr, dn, p->stream));
+  HIPCHK(hipMemcpyAsync(x_next, dn, nX * sizeof(double), hipMemcpyDeviceToHost, p->stream));
+  HIPCHK(hipStreamSynchronize(p->stream));
+  return 0;
+}
+
+int cddp_hip_mpc_run_plant(cddp_hip_handle *h, cddp_hip_plant *plant, int steps, int mode, int flags, const double *W,
+                           double *U_applied, double *X_visited, int32_t *iterations, int32_t *status, cddp_hip_stats *stats_sum) {
+  { int rc = plant_fits("cddp_hip_mpc_run_plant", h, plant); if (rc) return rc; }
+  if (steps <= 0) return fail(-1, "cddp_hip_mpc_run_plant: steps must be positive (got %d)", steps);
+  for (Inner *q : h->g) { int rc = in_mpc_check(q, mode, flags, false); if (rc) return rc; }
+  for (Inner *q : h->g) if (!q->have_initial) return fail(-1, "cddp_hip_set_initial must be called before cddp_hip_mpc_run_plant");
+  HIPCHK(hipSetDevice(h->device));
+  const size_t nx = (size_t)h->nx, nu = (size_t)h->nu;
+  if (W) { int rc = plant_upload_W(plant, W, (size_t)h->B * steps * nx); if (rc) return rc; }
+  if (stats_sum) std::memset(stats_sum, 0, sizeof(*stats_sum));
+  { int rc = fork_from_user(h); if (rc) return rc; }
+  for (Inner *q : h->g) { int rc = in_mpc_log_begin(q, steps); if (rc) return rc; rc = in_mpc_log(q, steps, -1); if (rc) return rc; }
+  const int aflags = flags | CDDP_HIP_MPC_X_DEVICE;
+  int rc_run = 0;
+  std::string err_run;
+  for (int k = 0; k < steps && !rc_run; ++k) {
+    cddp_hip_stats st;
+    rc_run = cddp_hip_solve(h, stats_sum ? &st : nullptr);
+    if (rc_run) break;
+    if (stats_sum) {
+      stats_sum->solve_ms += st.solve_ms; stats_sum->backward_ms += st.backward_ms; stats_sum->forward_ms += st.forward_ms; stats_sum->update_ms += st.update_ms;
+      stats_sum->sweeps += st.sweeps; stats_sum->rollouts += st.rollouts; stats_sum->rollouts_launched += st.rollouts_launched;
+      stats_sum->traj_iterations += st.traj_iterations; stats_sum->outer_iterations += st.outer_iterations; stats_sum->n_converged += st.n_converged;
+      stats_sum->kernel_launches += st.kernel_launches; stats_sum->timing_detail = st.timing_detail; stats_sum->rollout_steps += st.rollout_steps;
+    }
+    // per group, on its stream: iterations and status (and the model's own head, which the plant's rows then replace), the plant on row 0
+    // of the live slot, the advance from the staged x_next -- no synchronisation, the next solve is ordered behind them
+    for (Inner *q : h->g) { rc_run = in_mpc_check(q, mode, aflags); if (rc_run) break; }
+    for (size_t gi = 0; gi < h->g.size() && !rc_run; ++gi) {
+      Inner *q = h->g[gi];
+      const size_t b0 = (size_t)h->b0[gi];
+      rc_run = in_mpc_log(q, steps, k);
+      if (rc_run) break;
+      double *stage = plant->d_stage + b0 * nx;
+      hipError_t e = plant_launch_head(plant->pd, q->d, (int)b0, W ? plant->d_W + b0 * steps * nx : nullptr, steps, k, stage, q->d_log_u, q->d_log_x, q->stream);
+      if (e != hipSuccess) { rc_run = fail(-10, "cddp_hip_mpc_run_plant: plant step: %s", hipGetErrorString(e)); break; }
+      rc_run = in_mpc_advance(q, mode, aflags, stage, false);
+    }
+  }
+  if (rc_run) err_run = g_err;
+  for (size_t gi = 0; gi < h->g.size(); ++gi) {
+    const size_t b0 = (size_t)h->b0[gi];
+    int rc = in_mpc_log_fetch(h->g[gi], steps, U_applied ? U_applied + b0 * steps * nu : nullptr, X_visited ? X_visited + b0 * (steps + 1) * nx : nullptr,
+                              iterations ? iterations + b0 * steps : nullptr, status ? status + b0 * steps : nullptr);
+    if (rc && !rc_run) return rc;
+  }
+  if (rc_run) { g_err = err_run; return rc_run; }
+  return join_to_user(h);
+}
+
+int cddp_hip_track_plan(cddp_hip_handle *h, cddp_hip_plant *plant, const double *x0, const double *W, double *X_out, double *U_out) {
+  { int rc = plant_fits("cddp_hip_track_plan", h, plant); if (rc) return rc; }
+  for (Inner *q : h->g)
+    if (!q->has_plan) return fail(-1, "cddp_hip_track_plan needs a solved handle: there is no plan and no gain stack to track before cddp_hip_solve (or cddp_hip_initialize and cddp_hip_backward)");
+  HIPCHK(hipSetDevice(h->device));
+  const int N = h->N, nx = h->nx, nu = h->nu, Bp = plant->pd.Bp, NBlog = Bp / 64;
+  const size_t nXl = (size_t)(N + 1) * nx * Bp, nUl = (size_t)N * nu * Bp;
+  if (plant->tr_N != N) {
+    if (plant->d_trX) hipFree(plant->d_trX);
+    if (plant->d_trU) hipFree(plant->d_trU);
+    plant->d_trX = plant->d_trU = nullptr; plant->tr_N = -1;
+    HIPCHK(hipMalloc((void **)&plant->d_trX, nXl * sizeof(double)));
+    HIPCHK(hipMalloc((void **)&plant->d_trU, nUl * sizeof(double)));
+    plant->tr_N = N;
+  }
+  if (W) { int rc = plant_upload_W(plant, W, (size_t)h->B * N * nx); if (rc) return rc; }
+  if (x0) HIPCHK(hipMemcpy(plant->d_stage, x0, (size_t)h->B * nx * sizeof(double), hipMemcpyHostToDevice));
+  { int rc = fork_from_user(h); if (rc) return rc; }
+  for (size_t gi = 0; gi < h->g.size(); ++gi) {
+    Inner *q = h->g[gi];
+    const size_t b0 = (size_t)h->b0[gi];
+    HIPCHK(plant_launch_track(plant->pd, q->d, (int)b0, x0 ? plant->d_stage + b0 * nx : nullptr, W ? plant->d_W + b0 * N * nx : nullptr,
+                              plant->d_trX, plant->d_trU, NBlog, q->stream));
+  }
+  for (Inner *q : h->g) HIPCHK(hipStreamSynchronize(q->stream));
+  // the logs are wave-tiled stacks of the whole batch: one copy each, un-tiled as the getters un-tile theirs
+  std::vector<double> buf;
+  if (X_out) { buf.resize(nXl); HIPCHK(hipMemcpy(buf.data(), plant->d_trX, nXl * sizeof(double), hipMemcpyDeviceToHost)); from_soa(buf.data(), X_out, h->B, Bp, N + 1, nx); }
+  if (U_out) { buf.resize(nUl); HIPCHK(hipMemcpy(buf.data(), plant->d_trU, nUl * sizeof(double), hipMemcpyDeviceToHost)); from_soa(buf.data(), U_out, h->B, Bp, N, nu); }
   return join_to_user(h);
 }
 

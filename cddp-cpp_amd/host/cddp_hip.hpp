@@ -751,6 +751,34 @@ class CDDP {
   std::map<std::string, std::unique_ptr<TerminalConstraint>> terminal_constraint_set_;
 };
 
+// ---- the device-resident plant (cddp_hip_plant; include/cddp_hip.h "closed loop against a separate plant") ------------------------
+// A thin owner of the C handle: the descriptor is the C-ABI's own (fill a cddp_hip_plant_desc; its arrays are copied by the call).
+class Plant {
+ public:
+  Plant(const cddp_hip_plant_desc &desc, int batch, int device = 0) : batch_(batch), nx_(desc.nx), nu_(desc.nu) {
+    if (cddp_hip_plant_create(&desc, batch, device, &p_) != 0) throw std::runtime_error(std::string("cddp_hip: ") + cddp_hip_last_error());
+  }
+  ~Plant() { if (p_) cddp_hip_plant_destroy(p_); }
+  Plant(const Plant &) = delete;
+  Plant &operator=(const Plant &) = delete;
+  Plant(Plant &&o) noexcept : p_(o.p_), batch_(o.batch_), nx_(o.nx_), nu_(o.nu_) { o.p_ = nullptr; }
+  // x_next = plant(x, u) + w for every trajectory: host vectors, batch-major (batch * nx, batch * nu; w empty = none)
+  std::vector<double> step(const std::vector<double> &x, const std::vector<double> &u, const std::vector<double> &w = {}) {
+    if (x.size() != (size_t)batch_ * nx_ || u.size() != (size_t)batch_ * nu_ || (!w.empty() && w.size() != x.size()))
+      throw std::invalid_argument("cddp_hip: Plant::step: x, u, w must hold batch * nx, batch * nu, batch * nx doubles");
+    std::vector<double> xn(x.size());
+    if (cddp_hip_plant_step(p_, 0, x.data(), u.data(), w.empty() ? nullptr : w.data(), xn.data()) != 0)
+      throw std::runtime_error(std::string("cddp_hip: ") + cddp_hip_last_error());
+    return xn;
+  }
+  cddp_hip_plant *get() const { return p_; }
+  int batch() const { return batch_; }
+
+ private:
+  cddp_hip_plant *p_ = nullptr;
+  int batch_ = 0, nx_ = 0, nu_ = 0;
+};
+
 // ---- the GPU solver strategy ----------------------------------------------------------------------
 class HipBatchSolver : public ISolverAlgorithm {
  public:
@@ -795,6 +823,30 @@ class HipBatchSolver : public ISolverAlgorithm {
     g.U_applied.assign(B * K * nu_, 0.0); g.X_visited.assign(B * (K + 1) * nx_, 0.0); g.iterations.assign(B * K, 0); g.status.assign(B * K, 0);
     check(cddp_hip_mpc_run(h_, steps, mode, flags, g.U_applied.data(), g.X_visited.data(), g.iterations.data(), g.status.data(), &g.stats_sum));
     return g;
+  }
+  // NEW: the same loop against a device-resident plant (cddp_hip_mpc_run_plant).  W: batch * steps * nx disturbances, or empty.
+  MpcLog mpcRunPlant(Plant &plant, int steps, int mode, int flags = 0, const std::vector<double> &W = {}) {
+    if (!h_) throw std::runtime_error("cddp_hip: mpcRunPlant needs a resident batch (the plug-in route keeps no plan on the device)");
+    MpcLog g;
+    const size_t B = (size_t)batch_, K = (size_t)std::max(steps, 0);
+    if (!W.empty() && W.size() != B * K * nx_) throw std::invalid_argument("cddp_hip: mpcRunPlant: W must hold batch * steps * nx doubles");
+    g.U_applied.assign(B * K * nu_, 0.0); g.X_visited.assign(B * (K + 1) * nx_, 0.0); g.iterations.assign(B * K, 0); g.status.assign(B * K, 0);
+    check(cddp_hip_mpc_run_plant(h_, plant.get(), steps, mode, flags, W.empty() ? nullptr : W.data(), g.U_applied.data(), g.X_visited.data(),
+                                 g.iterations.data(), g.status.data(), &g.stats_sum));
+    return g;
+  }
+  // NEW: the solved plan's feedback policy on the plant over the horizon (cddp_hip_track_plan).  x0: batch * nx or empty = row 0 of the
+  // plan; W: batch * N * nx or empty.  X: [b][N + 1][nx], U: [b][N][nu], the saturated controls.
+  struct Tracked { std::vector<double> X, U; };
+  Tracked trackPlan(Plant &plant, const std::vector<double> &x0 = {}, const std::vector<double> &W = {}) {
+    if (!h_) throw std::runtime_error("cddp_hip: trackPlan needs a resident batch (the plug-in route keeps no plan on the device)");
+    const size_t B = (size_t)batch_;
+    if ((!x0.empty() && x0.size() != B * nx_) || (!W.empty() && W.size() != B * N_ * nx_))
+      throw std::invalid_argument("cddp_hip: trackPlan: x0 must hold batch * nx and W batch * N * nx doubles");
+    Tracked t;
+    t.X.assign(B * (N_ + 1) * nx_, 0.0); t.U.assign(B * N_ * nu_, 0.0);
+    check(cddp_hip_track_plan(h_, plant.get(), x0.empty() ? nullptr : x0.data(), W.empty() ? nullptr : W.data(), t.X.data(), t.U.data()));
+    return t;
   }
   cddp_hip_stats stats{};
   // Route of LogDDP / MSIPDDP problems (round 5): Auto = an eligible problem (built-in plant with nx <= 8, built-in

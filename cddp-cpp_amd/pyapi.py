@@ -167,6 +167,18 @@ MPC_KEEP_PLAN, MPC_SHIFT_EXISTING, MPC_SHIFT_PROVIDED = 0, 1, 2
 MPC_SHIFT_DUALS, MPC_X_DEVICE = 1, 2
 
 
+# cddp_hip_plant_* / cddp_hip_mpc_run_plant / cddp_hip_track_plan (include/cddp_hip.h, "closed loop against a separate plant")
+PLANT_DEVICE = 1
+
+
+class PlantDesc(C.Structure):   # cddp_hip_plant_desc
+    _fields_ = [
+        ("abi_version", C.c_int32), ("model", C.c_int32), ("integrator", C.c_int32), ("substeps", C.c_int32),
+        ("nx", C.c_int32), ("nu", C.c_int32), ("params_per_trajectory", C.c_int32), ("_pad", C.c_int32),
+        ("dt", C.c_double), ("model_params", _dp), ("lti_A", _dp), ("lti_B", _dp), ("u_lower", _dp), ("u_upper", _dp),
+    ]
+
+
 class Stats(C.Structure):
     _fields_ = [
         ("solve_ms", C.c_double), ("backward_ms", C.c_double), ("forward_ms", C.c_double),
@@ -773,6 +785,8 @@ def load_hip(trig=None):
         lib.cddp_hip_create.argtypes = [C.POINTER(ProblemStruct), C.c_int, C.c_int, C.POINTER(C.c_void_p)]
         lib.cddp_hip_mpc_advance.argtypes = MPC_ADVANCE_ARGTYPES; lib.cddp_hip_mpc_advance.restype = C.c_int
         lib.cddp_hip_mpc_run.argtypes = MPC_RUN_ARGTYPES; lib.cddp_hip_mpc_run.restype = C.c_int
+        for name, at in PLANT_ARGTYPES.items():
+            fn = getattr(lib, name); fn.argtypes = at; fn.restype = C.c_int
         _hip_libs["lib"] = lib
     lib = _hip_libs["lib"]
     if (trig == "shared") != bool(lib.cddp_hip_trig_shared()):
@@ -784,6 +798,14 @@ def load_hip(trig=None):
 # (x_next is a host OR a device address: passed as a plain pointer value)
 MPC_ADVANCE_ARGTYPES = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
 MPC_RUN_ARGTYPES = [C.c_void_p, C.c_int, C.c_int, C.c_int, _dp, _dp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(Stats)]
+# (cddp_hip_plant_step: x, u, w, x_next are host OR device addresses: plain pointer values)
+PLANT_ARGTYPES = {
+    "cddp_hip_plant_create": [C.POINTER(PlantDesc), C.c_int, C.c_int, C.POINTER(C.c_void_p)],
+    "cddp_hip_plant_destroy": [C.c_void_p],
+    "cddp_hip_plant_step": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    "cddp_hip_mpc_run_plant": [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(Stats)],
+    "cddp_hip_track_plan": [C.c_void_p, C.c_void_p, _dp, _dp, _dp, _dp],
+}
 
 EXPORTED_SYMBOLS = [
     "cddp_hip_default_options", "cddp_hip_abi_version", "cddp_hip_trig_shared", "cddp_hip_last_error", "cddp_hip_device_count",
@@ -797,6 +819,7 @@ EXPORTED_SYMBOLS = [
     "cddp_hip_stacks_backward", "cddp_hip_stacks_last_kernel_ms", "cddp_hip_stacks_last_sweep_form", "cddp_hip_stacks_factor_cache", "cddp_hip_stacks_get_gains", "cddp_hip_stacks_get_constraint_gains",
     "cddp_hip_stacks_get_scalars", "cddp_hip_set_terminal_equality", "cddp_hip_stacks_get_terminal", "cddp_hip_plugin_solve", "cddp_hip_plugin_solve_terminal", "cddp_hip_plugin_set_host_threads", "cddp_hip_plugin_last_stats", "cddp_hip_model_eval", "cddp_hip_set_options", "cddp_hip_set_initial_state", "cddp_hip_forget_solver_state", "cddp_hip_set_duals", "cddp_hip_set_terminal",
     "cddp_hip_costate_mode", "cddp_hip_costate_redos", "cddp_hip_mpc_advance", "cddp_hip_mpc_run",
+    "cddp_hip_plant_create", "cddp_hip_plant_destroy", "cddp_hip_plant_step", "cddp_hip_mpc_run_plant", "cddp_hip_track_plan",
 ]
 
 
@@ -958,6 +981,30 @@ class HipBatchSolver:
                                               it.ctypes.data_as(i32), st.ctypes.data_as(i32), C.byref(stats)))
         return {"U_applied": U, "X_visited": X, "iterations": it, "status": st, "stats": stats}
 
+    def mpc_run_plant(self, plant, steps, mode, shift_duals=False, W=None):
+        """`steps` closed-loop MPC steps against a DevicePlant (cddp_hip_mpc_run_plant): solve, plant step on the device from row 0 of the
+        plan and its u_0 (saturated, disturbed by W[:, k]), advance from the plant's state.  W: None or (B, steps, nx), uploaded once.
+        Returns the dict of mpc_run; U_applied holds the saturated controls, X_visited the plant's states."""
+        steps = int(steps)
+        U = np.zeros((self.B, max(steps, 0), self.p.nu)); X = np.zeros((self.B, max(steps, 0) + 1, self.p.nx))
+        it = np.zeros((self.B, max(steps, 0)), dtype=np.int32); st = np.zeros((self.B, max(steps, 0)), dtype=np.int32)
+        Wa = _arr(W).reshape(self.B, max(steps, 0), self.p.nx) if W is not None else None
+        stats = Stats()
+        i32 = C.POINTER(C.c_int32)
+        self._check(self.lib.cddp_hip_mpc_run_plant(self.h, plant.h if plant is not None else None, steps, int(mode), MPC_SHIFT_DUALS if shift_duals else 0,
+                                                    _ptr(Wa), _ptr(U), _ptr(X), it.ctypes.data_as(i32), st.ctypes.data_as(i32), C.byref(stats)))
+        return {"U_applied": U, "X_visited": X, "iterations": it, "status": st, "stats": stats}
+
+    def track_plan(self, plant, x0=None, W=None):
+        """The solved plan's feedback policy u_t = U_t + K_t (x_t - X_t) rolled out on a DevicePlant over the horizon (cddp_hip_track_plan).
+        x0: None = row 0 of the plan, or (B, nx); W: None or (B, N, nx).  Returns (X (B, N + 1, nx), U (B, N, nu), the saturated controls);
+        the handle's state is not modified."""
+        x0a = _arr(x0).reshape(self.B, self.p.nx) if x0 is not None else None
+        Wa = _arr(W).reshape(self.B, self.p.N, self.p.nx) if W is not None else None
+        X = np.zeros((self.B, self.p.N + 1, self.p.nx)); U = np.zeros((self.B, self.p.N, self.p.nu))
+        self._check(self.lib.cddp_hip_track_plan(self.h, plant.h if plant is not None else None, _ptr(x0a), _ptr(Wa), _ptr(X), _ptr(U)))
+        return X, U
+
     def gains(self):
         K = np.zeros((self.B, self.p.N, self.p.nu, self.p.nx)); k = np.zeros((self.B, self.p.N, self.p.nu))
         self._check(self.lib.cddp_hip_get_gains(self.h, _ptr(K), _ptr(k)))
@@ -1014,6 +1061,83 @@ class HipBatchSolver:
 
     def write_gather_records_device(self, device_ptr):
         self._check(self.lib.cddp_hip_write_gather_records_device(self.h, C.c_void_p(device_ptr)))
+
+
+class DevicePlant:
+    """A device-resident plant for a batch of trajectories (cddp_hip_plant): a built-in model with its own parameters (shared, or one row
+    per trajectory: params of shape (batch, n)), integrator, `substeps` steps of dt / substeps per control interval, and an optional
+    control box the commanded control is clipped to.  Used by HipBatchSolver.mpc_run_plant / track_plan, or stepped directly."""
+
+    def __init__(self, model, integrator, dt, nx, nu, batch, params=(), substeps=1, u_lower=None, u_upper=None, lti_A=None, lti_B=None,
+                 device=0, trig=None):
+        self.lib = load_hip(trig)
+        self.B, self.nx, self.nu, self._device = int(batch), int(nx), int(nu), int(device)
+        pv = np.asarray(params, dtype=np.float64)
+        per = pv.ndim == 2
+        mp = np.zeros((self.B if per else 1, MAX_MODEL_PARAMS))
+        if pv.size:
+            mp[:, :pv.shape[-1]] = pv
+        self.keep = [np.ascontiguousarray(mp)]
+        d = PlantDesc()
+        d.abi_version = ABI_VERSION; d.model = int(model); d.integrator = int(integrator); d.substeps = int(substeps)
+        d.nx = self.nx; d.nu = self.nu; d.params_per_trajectory = 1 if per else 0; d.dt = float(dt)
+        d.model_params = _ptr(self.keep[0])
+        for name, v in (("lti_A", lti_A), ("lti_B", lti_B), ("u_lower", u_lower), ("u_upper", u_upper)):
+            if v is not None:
+                a = _arr(v); self.keep.append(a); setattr(d, name, _ptr(a))
+        self.desc = d
+        self.h = C.c_void_p()
+        rc = self.lib.cddp_hip_plant_create(C.byref(d), self.B, self._device, C.byref(self.h))
+        if rc != 0:
+            raise HipError("cddp_hip error %d: %s" % (rc, self.lib.cddp_hip_last_error().decode()))
+
+    @classmethod
+    def of_problem(cls, problem, batch, **over):
+        """The plant of a Problem -- its model, parameters, integrator, dt (and LTI matrices) --, with any of them overridden by keyword."""
+        c = problem.c
+        kw = dict(model=c.model, integrator=c.integrator, dt=c.dt, nx=c.nx, nu=c.nu, params=list(c.model_params),
+                  lti_A=getattr(problem, "lti_A", None), lti_B=getattr(problem, "lti_B", None))
+        kw.update(over)
+        return cls(batch=batch, **kw)
+
+    def _check(self, rc):
+        if rc != 0:
+            raise HipError("cddp_hip error %d: %s" % (rc, self.lib.cddp_hip_last_error().decode()))
+
+    def step(self, x, u, w=None):
+        """x_next = plant(x, u) + w for every trajectory.  numpy arrays (B, nx), (B, nu), (B, nx): uploaded, computed, returned as numpy.
+        torch tensors on the plant's device (float64): read and written in place on the device, after a synchronisation of their
+        current stream (as HipBatchSolver.mpc_advance treats a device x_next); a torch tensor is returned."""
+        if hasattr(x, "data_ptr") and not isinstance(x, np.ndarray):
+            import torch
+            ts = [("x", x, self.nx), ("u", u, self.nu)] + ([("w", w, self.nx)] if w is not None else [])
+            keep = []
+            for name, t, n in ts:
+                if not hasattr(t, "data_ptr") or not t.is_cuda or t.dtype != torch.float64 or tuple(t.shape) != (self.B, n):
+                    raise ValueError("%s: a float64 device tensor of shape (%d, %d) is expected" % (name, self.B, n))
+                if t.device.index != self._device:
+                    raise ValueError("%s lives on device %s, the plant on device %d" % (name, t.device.index, self._device))
+                keep.append(t.contiguous())
+            out = torch.empty_like(keep[0])
+            torch.cuda.current_stream(out.device).synchronize()
+            self._check(self.lib.cddp_hip_plant_step(self.h, PLANT_DEVICE, keep[0].data_ptr(), keep[1].data_ptr(),
+                                                     keep[2].data_ptr() if w is not None else None, out.data_ptr()))
+            return out
+        xa = _arr(x).reshape(self.B, self.nx); ua = _arr(u).reshape(self.B, self.nu)
+        wa = _arr(w).reshape(self.B, self.nx) if w is not None else None
+        out = np.zeros((self.B, self.nx))
+        self._check(self.lib.cddp_hip_plant_step(self.h, 0, xa.ctypes.data, ua.ctypes.data, wa.ctypes.data if wa is not None else None, out.ctypes.data))
+        return out
+
+    def close(self):
+        if self.h:
+            self.lib.cddp_hip_plant_destroy(self.h); self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def model_eval(model, integrator, dt, params, nx, nu, x, u, want=("step",), trig=None):

@@ -1081,7 +1081,7 @@ class CDDP:                         # cddp_core.hpp:214-423 / bind_solver.cpp:57
                 return None
         return {"CLDDP": api.SOLVER_CLDDP, "IPDDP": api.SOLVER_IPDDP, "LogDDP": api.SOLVER_LOGDDP, "MSIPDDP": api.SOLVER_MSIPDDP}[name]
 
-    def solve_mpc_batch(self, x0s, steps, solver_type=SolverType.IPDDP, warm_start="provided", shift_duals=False):
+    def solve_mpc_batch(self, x0s, steps, solver_type=SolverType.IPDDP, warm_start="provided", shift_duals=False, plant=None, disturbances=None):
         """NEW (no reference counterpart): `steps` closed-loop MPC steps of one device-resident batch, the model as the plant -- solve, apply
         u_0, start the next solve at x_1 -- without the plan leaving the device between solves (cddp_hip_mpc_run).  Trajectory i starts at
         x0s[i]; the first solve is seeded as solve_batch seeds it.  warm_start names how every later solve is seeded:
@@ -1091,12 +1091,26 @@ class CDDP:                         # cddp_core.hpp:214-423 / bind_solver.cpp:57
         options.warm_start is switched on for the run (that is what makes a seed a warm start).  Returns a dict: state_trajectory
         (B, steps + 1, nx) and control_trajectory (B, steps, nu) as executed, iterations (B, steps), status_message (B lists of `steps`
         strings), solve_time_ms (device time of the solves, added up).  Problems that solve_batch sends to the plug-in route are refused:
-        they have no resident handle to advance."""
+        they have no resident handle to advance.
+        plant (None = the model, today's call): a dict describing the TRUE plant, a device-resident copy of this problem's own model
+        (cddp_hip_mpc_run_plant): "params" (the model's parameter list, or one row per trajectory, (B, n)), "substeps" (the plant takes
+        that many steps of timestep / substeps per control interval), "integrator" ("euler", "heun", "rk3", "rk4"), "u_lower" / "u_upper"
+        (actuator saturation, as a pair); every key is optional and defaults to the model's value.  disturbances: (B, steps, nx), added
+        to the plant's state after every step; needs a plant ({} = the model itself).  control_trajectory then holds the saturated
+        controls and state_trajectory the plant's states."""
         api = _api()
         name = solver_type.value if isinstance(solver_type, SolverType) else str(solver_type)
         modes = {"provided": api.MPC_SHIFT_PROVIDED, "existing": api.MPC_SHIFT_EXISTING, "keep": api.MPC_KEEP_PLAN}
         if warm_start not in modes:
             raise ValueError("warm_start must be 'provided', 'existing' or 'keep' (got %r)" % (warm_start,))
+        if disturbances is not None and plant is None:
+            raise ValueError("disturbances act on a plant: pass plant={} for a disturbed copy of the model")
+        if plant is not None:
+            unknown = set(plant) - {"params", "substeps", "integrator", "u_lower", "u_upper"}
+            if unknown:
+                raise ValueError("plant: unknown keys %s (known: params, substeps, integrator, u_lower, u_upper)" % sorted(unknown))
+            if "integrator" in plant and plant["integrator"] not in _INTEGRATORS:
+                raise ValueError("Unknown integration type: " + str(plant["integrator"]))
         if self._sys is None:
             raise RuntimeError("Dynamical system must be set before solving.")
         kind = self._resident_kind(name)
@@ -1110,10 +1124,20 @@ class CDDP:                         # cddp_core.hpp:214-423 / bind_solver.cpp:57
         U0 = None if self._U is None else np.ascontiguousarray(np.tile(self._U, (B, 1, 1)))
         X0 = None if self._X is None else np.ascontiguousarray(np.tile(self._X, (B, 1, 1)))
         hs = api.HipBatchSolver(p, B)
+        dp = None
         try:
             hs.set_initial(x0, U0, X0)
-            r = hs.mpc_run(int(steps), modes[warm_start], shift_duals=shift_duals)
+            if plant is None:
+                r = hs.mpc_run(int(steps), modes[warm_start], shift_duals=shift_duals)
+            else:
+                over = {k: plant[k] for k in ("params", "substeps", "u_lower", "u_upper") if k in plant}
+                if "integrator" in plant:
+                    over["integrator"] = _INTEGRATORS[plant["integrator"]]
+                dp = api.DevicePlant.of_problem(p, B, **over)
+                r = hs.mpc_run_plant(dp, int(steps), modes[warm_start], shift_duals=shift_duals, W=disturbances)
         finally:
+            if dp is not None:
+                dp.close()
             hs.close()
         return {"state_trajectory": r["X_visited"], "control_trajectory": r["U_applied"], "iterations": r["iterations"],
                 "status_message": [[api.STATUS_STRINGS[int(s)] for s in row] for row in r["status"]],

@@ -495,6 +495,66 @@ int cddp_hip_mpc_run(cddp_hip_handle *h, int steps, int mode, int flags,
                      double *U_applied /* B*steps*nu */, double *X_visited /* B*(steps+1)*nx */,
                      int32_t *iterations /* B*steps */, int32_t *status /* B*steps */, cddp_hip_stats *stats_sum);
 
+/* ---- closed loop against a separate plant --------------------------------
+ * A cddp_hip_plant is a device-resident plant for a batch of trajectories: one of the built-in models with its OWN parameters (shared by
+ * the batch or one block per trajectory), integrator, integration step (dt / substeps under a zero-order hold of u), actuator
+ * saturation and an additive disturbance.  It closes the MPC loop on the device (cddp_hip_mpc_run_plant), rolls a solved plan's
+ * feedback policy out on the true plant (cddp_hip_track_plan) and can be driven directly (cddp_hip_plant_step).
+ * (New entry points; ABI version unchanged; the descriptor carries its own abi_version, checked as cddp_hip_plugin's is.)
+ *
+ * Arithmetic (the library is built without FMA contraction; the tests of these entries are bitwise):
+ *  - parameters: trajectory b reads its own DERIVED block -- what cddp_hip_create derives from cddp_hip_problem::model_params (inverse
+ *    inertia, the USV matrices, ...) applied to its CDDP_HIP_MAX_MODEL_PARAMS caller entries when the plant is created; for the car and
+ *    the forklift the timestep slot is the plant's dt; LTI: lti_A | lti_B | dt;
+ *  - h = dt / substeps is divided once on the host, in double;
+ *  - one step: u_s[i] = fmin(fmax(u[i], u_lower[i]), u_upper[i]) (only with a box); `substeps` times x <- step(integrator, h, params_b,
+ *    x, u_s), the explicit integrators of the solver's own rollout; x_next[i] = x[i] + w[i] (only with w). */
+typedef struct cddp_hip_plant_desc {
+  int32_t abi_version;           /* CDDP_HIP_ABI_VERSION */
+  int32_t model, integrator;     /* cddp_hip_model, cddp_hip_integrator */
+  int32_t substeps;              /* >= 1: the plant takes `substeps` steps of dt / substeps under a zero-order hold of u */
+  int32_t nx, nu;
+  int32_t params_per_trajectory; /* 0: model_params is CDDP_HIP_MAX_MODEL_PARAMS doubles; 1: batch * CDDP_HIP_MAX_MODEL_PARAMS, batch-major */
+  int32_t _pad;
+  double dt;                     /* control interval */
+  const double *model_params;    /* caller's parameters, laid out as cddp_hip_problem::model_params; derived entries are the library's */
+  const double *lti_A, *lti_B;   /* CDDP_HIP_MODEL_LTI only, shared by the batch */
+  const double *u_lower, *u_upper; /* nu each, or both NULL: the plant receives min(max(u, lower), upper) */
+} cddp_hip_plant_desc;
+typedef struct cddp_hip_plant cddp_hip_plant;
+enum { CDDP_HIP_PLANT_DEVICE = 1 };   /* x, u, w, x_next are device pointers, batch-major as below */
+
+/* The descriptor is checked BEFORE the device is looked at, each refusal with its own message: wrong abi_version; unknown model or
+ * integrator; nx / nu not the model's; substeps < 1; substeps > 1 on a discrete plant (car, forklift, LTI: their step is h = dt by
+ * definition); dt <= 0; one of u_lower / u_upper NULL or lower > upper in a slot; LTI without lti_A / lti_B or with
+ * params_per_trajectory; a parameter block the model refuses (with per-trajectory parameters the message names the trajectory).  Only
+ * then: -20, no HIP device.  The arrays of the descriptor are copied; they need not outlive the call. */
+int cddp_hip_plant_create(const cddp_hip_plant_desc *desc, int batch, int device, cddp_hip_plant **out);
+int cddp_hip_plant_destroy(cddp_hip_plant *p);
+/* One control interval of every trajectory: x_next = plant(x, u) + w.  flags = 0: host pointers (uploaded, computed, downloaded);
+ * CDDP_HIP_PLANT_DEVICE: device pointers of the plant's device, whose contents must be complete when the call is made.  Either way the
+ * call returns after x_next has been written.  x_next may be x. */
+int cddp_hip_plant_step(cddp_hip_plant *p, int flags, const double *x /* B*nx */, const double *u /* B*nu */,
+                        const double *w /* B*nx or NULL */, double *x_next /* B*nx */);
+/* cddp_hip_mpc_run with the plant in the loop: `steps` times { cddp_hip_solve; record iterations and status; x_next = plant(row 0 of every
+ * trajectory's live slot, u_0 of the plan, W[:, k]); record the SATURATED u_0 and x_next; the equivalent of cddp_hip_mpc_advance(mode,
+ * flags | CDDP_HIP_MPC_X_DEVICE, x_next) }.  Outputs, the behaviour on an error (the steps completed so far come back) and stats_sum as
+ * cddp_hip_mpc_run.  W (host, B*steps*nx, W[b][k][nx]) is uploaded once before the first solve; nothing but the final logs crosses the
+ * bus afterwards.  Bitwise the hand-written loop over cddp_hip_solve, cddp_hip_plant_step on row 0 of cddp_hip_get_trajectory and
+ * cddp_hip_mpc_advance.  A handle of several tile groups runs the plant per group, on the group's stream.
+ * Refused, with nothing launched and nothing changed: a NULL handle or plant; nx, nu or batch differing between plant and handle; a
+ * plant on another device; everything cddp_hip_mpc_run refuses. */
+int cddp_hip_mpc_run_plant(cddp_hip_handle *h, cddp_hip_plant *plant, int steps, int mode, int flags,
+                           const double *W /* B*steps*nx or NULL, host */,
+                           double *U_applied, double *X_visited, int32_t *iterations, int32_t *status, cddp_hip_stats *stats_sum);
+/* The solved plan's feedback policy on the plant, over the horizon.  X, U: the live slot of the handle's current plan; K: the stack
+ * cddp_hip_get_gains reads.  Per step t: dx[j] = x_t[j] - X_t[j]; s = 0, for j ascending s += K_t[i][j] * dx[j]; u[i] = U_t[i] + s;
+ * then the plant step as above with W[b][t].  U_out holds the saturated controls; X_out[:, 0] is x0, or row 0 of the plan.  Host
+ * pointers.  The handle's state is not modified.  Refused as cddp_hip_mpc_run_plant refuses a mismatched plant, and on a handle that was
+ * never initialised or solved. */
+int cddp_hip_track_plan(cddp_hip_handle *h, cddp_hip_plant *plant, const double *x0 /* B*nx or NULL = row 0 of the plan */,
+                        const double *W /* B*N*nx or NULL */, double *X_out /* B*(N+1)*nx */, double *U_out /* B*N*nu */);
+
 /* ---- getters (host buffers, batch-major) -------------------------------- */
 int cddp_hip_get_results(cddp_hip_handle *h, cddp_hip_result *results /* batch */);
 /* Head of the plan (round 4): u_0[batch][nu] and x_1[batch][nx] of every trajectory's current iterate -- what a receding-horizon
