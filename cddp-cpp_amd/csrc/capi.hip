@@ -14,6 +14,7 @@
 
 #include "launch.hpp"
 #include "plant.hpp"
+#include "io_kernels.hpp"
 
 // 1 when a[0] > a[1] > ... > a[n - 1] (NaN-free): the ladders cddp_hip_build_alphas makes; DevBuf::ladder_sorted
 static int ladder_strictly_decreasing(const double *a, int n) {
@@ -2055,6 +2056,136 @@ int cddp_hip_mpc_advance(cddp_hip_handle *h, int mode, int flags, const double *
     if (rc) return rc;
   }
   return join_to_user(h);
+}
+
+// ---- device-resident inputs and outputs: batch-major DEVICE arrays <-> the handle's internal layouts (inst_io.hip) ----
+// what cddp_hip_get_field_device reads for one group: the buffer, slot rule, layout and extent of the field's host getter
+struct IoField { int layout; const double *base; size_t plane; int T, E; };
+static int io_field(const Inner *q, int field, IoField *f) {
+  const DevBuf &d = q->d;
+  const int N = d.N, nx = q->P.nx, nu = q->P.nu, m = q->P.m;
+  const bool ipms = q->P.solver == CDDP_HIP_SOLVER_IPDDP || q->P.solver == CDDP_HIP_SOLVER_MSIPDDP;
+  const int stack = q->route.t4 ? cddp_io::kT4 : cddp_io::kTiled;   // (in_get_linearization)
+  switch (field) {
+    case CDDP_HIP_FIELD_X: *f = IoField{cddp_io::kSlotted, d.X, d.planeX, N + 1, nx}; break;
+    case CDDP_HIP_FIELD_U: *f = IoField{cddp_io::kSlotted, d.U, d.planeU, N, nu}; break;
+    case CDDP_HIP_FIELD_K: *f = IoField{cddp_io::kTiled, d.K, 0, N, nu * nx}; break;
+    case CDDP_HIP_FIELD_KFF: *f = IoField{cddp_io::kTiled, d.k, 0, N, nu}; break;
+    case CDDP_HIP_FIELD_VX: *f = IoField{cddp_io::kTiled, d.Vx, 0, N + 1, nx}; break;
+    case CDDP_HIP_FIELD_VXX: *f = IoField{cddp_io::kTiled, d.Vxx, 0, N + 1, nx * nx}; break;
+    case CDDP_HIP_FIELD_A: *f = IoField{stack, d.A, 0, N, nx * nx}; break;
+    case CDDP_HIP_FIELD_B: *f = IoField{stack, d.Bm, 0, N, nx * nu}; break;
+    case CDDP_HIP_FIELD_S: case CDDP_HIP_FIELD_Y: case CDDP_HIP_FIELD_G:
+      if (!ipms || m == 0) return fail(-1, "no slack/dual trajectories for this problem");
+      *f = IoField{cddp_io::kSlotted, field == CDDP_HIP_FIELD_S ? d.S : field == CDDP_HIP_FIELD_Y ? d.Y : d.G, d.planeM, N, m}; break;
+    case CDDP_HIP_FIELD_LAMBDA:
+      if (!ipms) return fail(-1, "no costate trajectory for this solver (IPDDP and MSIPDDP carry one)");
+      *f = IoField{cddp_io::kSlotted, d.Lam, d.planeX, costate_rows(q), nx}; break;
+    default: return fail(-2, "unknown field id %d (cddp_hip_field)", field);
+  }
+  if (!f->base) return fail(-1, "field %d is not kept by this handle", field);
+  return 0;
+}
+
+// A caller's pointer may reach a kernel only as device memory of the handle's device whose allocation holds every byte the call touches.
+static int io_check_pointer(const cddp_hip_handle *h, const void *p, size_t bytes, const char *entry, const char *what) {
+  hipPointerAttribute_t at;
+  std::memset(&at, 0, sizeof(at));
+  const hipError_t e = hipPointerGetAttributes(&at, p);
+  if (e != hipSuccess) { (void)hipGetLastError(); return fail(-2, "%s: %s is not device memory (%s)", entry, what, hipGetErrorString(e)); }
+  if (at.type != hipMemoryTypeDevice)
+    return fail(-2, "%s: %s is not device memory (%s)", entry, what,
+                at.type == hipMemoryTypeHost ? "a pinned host address" : at.type == hipMemoryTypeUnregistered ? "a host address" : "managed or array memory");
+  if (at.device != h->device) return fail(-2, "%s: %s lives on device %d, the handle on device %d", entry, what, at.device, h->device);
+  hipDeviceptr_t base = nullptr; size_t size = 0;
+  const hipError_t e2 = hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p);
+  if (e2 != hipSuccess) { (void)hipGetLastError(); return fail(-2, "%s: the allocation of %s is unknown (%s)", entry, what, hipGetErrorString(e2)); }
+  const size_t room = (size_t)((const char *)base + size - (const char *)p);
+  if (bytes > room) return fail(-2, "%s: %s needs %zu bytes, its allocation ends after %zu", entry, what, bytes, room);
+  return 0;
+}
+
+// Ordering as cddp_hip_mpc_advance with a device x_next: on the stream of cddp_hip_set_stream the kernels are ordered between the caller's
+// work before and after the call (fork / join) and the call does not block; otherwise the group streams are synchronised before it returns.
+static int io_finish(cddp_hip_handle *h) {
+  HIPCHK(hipGetLastError());
+  if (!h->have_user_stream) for (Inner *q : h->g) HIPCHK(hipStreamSynchronize(q->stream));
+  return join_to_user(h);
+}
+
+// which plane of the slotted fields holds every trajectory's current iterate (the slot rule the slotted getters follow), for tests and diagnosis
+int cddp_hip_get_live_slots(cddp_hip_handle *h, int32_t *slots, int32_t *n_slots) {
+  if (!h) return fail(-1, "null handle");
+  if (n_slots) *n_slots = h->g[0]->d.n_slots;
+  if (!slots) return 0;
+  HIPCHK(hipSetDevice(h->device));
+  { int rc = fork_from_user(h); if (rc) return rc; }
+  for (size_t gi = 0; gi < h->g.size(); ++gi) {
+    Inner *q = h->g[gi];
+    HIPCHK(hipMemcpyAsync(slots + h->b0[gi], q->d.cur, sizeof(int32_t) * (size_t)q->d.B, hipMemcpyDeviceToHost, q->stream));
+    HIPCHK(hipStreamSynchronize(q->stream));
+  }
+  return join_to_user(h);
+}
+
+int cddp_hip_field_shape(cddp_hip_handle *h, int field, int32_t *rows, int32_t *cols) {
+  if (!h) return fail(-1, "null handle");
+  IoField f;
+  { int rc = io_field(h->g[0], field, &f); if (rc) return rc; }
+  if (rows) *rows = f.T;
+  if (cols) *cols = f.E;
+  return 0;
+}
+
+int cddp_hip_get_field_device(cddp_hip_handle *h, int field, double *out_dev) {
+  if (!h) return fail(-1, "null handle");
+  std::vector<IoField> f(h->g.size());
+  for (size_t gi = 0; gi < h->g.size(); ++gi) { int rc = io_field(h->g[gi], field, &f[gi]); if (rc) return rc; }   // refusals first: nothing launched
+  if (!out_dev) return fail(-1, "cddp_hip_get_field_device: null output pointer");
+  HIPCHK(hipSetDevice(h->device));
+  const size_t per = (size_t)f[0].T * (size_t)f[0].E;
+  { int rc = io_check_pointer(h, out_dev, (size_t)h->B * per * sizeof(double), "cddp_hip_get_field_device", "the output"); if (rc) return rc; }
+  { int rc = fork_from_user(h); if (rc) return rc; }
+  for (size_t gi = 0; gi < h->g.size(); ++gi) {
+    const Inner *q = h->g[gi];
+    io_untile(f[gi].layout, f[gi].base, q->d.cur, f[gi].plane, q->d.B, q->d.NB, f[gi].T, f[gi].E, out_dev + (size_t)h->b0[gi] * per, q->stream);
+  }
+  return io_finish(h);
+}
+
+int cddp_hip_get_results_device(cddp_hip_handle *h, double *cols_dev, int32_t *icols_dev) {
+  if (!h) return fail(-1, "null handle");
+  if (!cols_dev || !icols_dev) return fail(-1, "cddp_hip_get_results_device: null output pointer");
+  HIPCHK(hipSetDevice(h->device));
+  { int rc = io_check_pointer(h, cols_dev, (size_t)h->B * 10 * sizeof(double), "cddp_hip_get_results_device", "the double columns"); if (rc) return rc; }
+  { int rc = io_check_pointer(h, icols_dev, (size_t)h->B * 4 * sizeof(int32_t), "cddp_hip_get_results_device", "the int32 columns"); if (rc) return rc; }
+  { int rc = fork_from_user(h); if (rc) return rc; }
+  for (size_t gi = 0; gi < h->g.size(); ++gi) {
+    const Inner *q = h->g[gi];
+    const DevBuf &d = q->d;
+    const IoResultSrc src = {{d.cost, d.merit, d.inf_pr, d.inf_du, d.inf_comp, d.mu, d.reg, d.alpha_pr, d.alpha_du, d.step_norm}, {d.iter, d.status, d.n_bwd, d.n_fwd}};   // (in_get_results)
+    io_results(src, d.B, cols_dev + (size_t)h->b0[gi] * 10, icols_dev + (size_t)h->b0[gi] * 4, q->stream);
+  }
+  return io_finish(h);
+}
+
+int cddp_hip_set_initial_device(cddp_hip_handle *h, const double *x0_dev, const double *U0_dev, const double *X0_dev) {
+  if (!h) return fail(-1, "null handle");
+  if (!x0_dev) return fail(-1, "cddp_hip_set_initial_device: null x0 pointer");
+  HIPCHK(hipSetDevice(h->device));
+  const size_t nX = (size_t)(h->N + 1) * h->nx, nU = (size_t)h->N * h->nu;
+  { int rc = io_check_pointer(h, x0_dev, (size_t)h->B * h->nx * sizeof(double), "cddp_hip_set_initial_device", "x0"); if (rc) return rc; }
+  if (U0_dev) { int rc = io_check_pointer(h, U0_dev, (size_t)h->B * nU * sizeof(double), "cddp_hip_set_initial_device", "U0"); if (rc) return rc; }
+  if (X0_dev) { int rc = io_check_pointer(h, X0_dev, (size_t)h->B * nX * sizeof(double), "cddp_hip_set_initial_device", "X0"); if (rc) return rc; }
+  { int rc = fork_from_user(h); if (rc) return rc; }
+  for (size_t gi = 0; gi < h->g.size(); ++gi) {
+    Inner *q = h->g[gi];
+    const size_t b0 = (size_t)h->b0[gi];
+    io_tile(X0_dev ? X0_dev + b0 * nX : nullptr, x0_dev + b0 * h->nx, q->d.B, q->d.NB, h->N + 1, h->nx, q->d_Xinit, q->stream);
+    io_tile(U0_dev ? U0_dev + b0 * nU : nullptr, nullptr, q->d.B, q->d.NB, h->N, h->nu, q->d_Uinit, q->stream);
+    q->have_initial = true; q->initialized = false; q->initial_dirty = true;   // as in_set_initial leaves them
+  }
+  return io_finish(h);
 }
 
 int cddp_hip_mpc_run(cddp_hip_handle *h, int steps, int mode, int flags, double *U_applied, double *X_visited, int32_t *iterations, int32_t *status,

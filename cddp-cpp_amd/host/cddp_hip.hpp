@@ -848,6 +848,38 @@ class HipBatchSolver : public ISolverAlgorithm {
     check(cddp_hip_track_plan(h_, plant.get(), x0.empty() ? nullptr : x0.data(), W.empty() ? nullptr : W.data(), t.X.data(), t.U.data()));
     return t;
   }
+  // NEW: device-resident inputs and outputs of the batch of the last initialize() / solveBatch() (cddp_hip_set_initial_device,
+  // cddp_hip_get_field_device, cddp_hip_get_results_device).  Every pointer is DEVICE memory of the solver's device, batch-major as the host
+  // entries; field = CDDP_HIP_FIELD_*.  The library refuses host addresses and allocations that are too short; refusals arrive as exceptions.
+  struct FieldShape { int rows = 0, cols = 0; };   // T and E of the field's [batch][T][E] array
+  FieldShape fieldShape(int field) {
+    if (!h_) throw std::runtime_error("cddp_hip: fieldShape needs a resident batch (the plug-in route has no resident handle)");
+    int32_t r = 0, c = 0;
+    check(cddp_hip_field_shape(h_, field, &r, &c));
+    FieldShape s; s.rows = r; s.cols = c;
+    return s;
+  }
+  void getFieldDevice(int field, double *out_dev) {   // batch * rows * cols doubles
+    if (!h_) throw std::runtime_error("cddp_hip: getFieldDevice needs a resident batch (the plug-in route has no resident handle)");
+    check(cddp_hip_get_field_device(h_, field, out_dev));
+  }
+  void resultsDevice(double *cols_dev /* batch * 10 */, int32_t *icols_dev /* batch * 4 */) {   // the columns of cddp_hip_result, in struct order
+    if (!h_) throw std::runtime_error("cddp_hip: resultsDevice needs a resident batch (the plug-in route has no resident handle)");
+    check(cddp_hip_get_results_device(h_, cols_dev, icols_dev));
+  }
+  // x0_dev: batch * nx; U0_dev: batch * N * nu or nullptr (zeros); X0_dev: batch * (N + 1) * nx or nullptr (x0 along the horizon).  The next
+  // resolveBatch() starts from this seed.
+  void setInitialDevice(const double *x0_dev, const double *U0_dev = nullptr, const double *X0_dev = nullptr) {
+    if (!h_) throw std::runtime_error("cddp_hip: setInitialDevice needs a resident batch (the plug-in route has no resident handle)");
+    check(cddp_hip_set_initial_device(h_, x0_dev, U0_dev, X0_dev));
+  }
+  // NEW: solve the resident batch again from the seed it holds now (setInitialDevice, mpcAdvance) -- solveBatch() without creating and uploading
+  std::vector<CDDPSolution> resolveBatch(CDDP &ctx) {
+    if (!h_) throw std::runtime_error("cddp_hip: resolveBatch needs a resident batch (the plug-in route has no resident handle)");
+    return collect(ctx, batch_);
+  }
+  int batch() const { return batch_; }
+  cddp_hip_handle *handle() const { return h_; }   // the resident batch's C handle (nullptr on the plug-in route), for the C entries without a wrapper method
   cddp_hip_stats stats{};
   // Route of LogDDP / MSIPDDP problems (round 5): Auto = an eligible problem (built-in plant with nx <= 8, built-in
   // objective / constraints; MSIPDDP also: no terminal set, and nu = 1 or nx = nu once a path constraint is present) runs on the resident

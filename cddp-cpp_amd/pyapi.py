@@ -165,6 +165,12 @@ TIMING_ROLLOUT, TIMING_ALL, TIMING_SWEEP = 0, 1, 2
 # cddp_hip_mpc_advance / cddp_hip_mpc_run (include/cddp_hip.h, "device-resident MPC step")
 MPC_KEEP_PLAN, MPC_SHIFT_EXISTING, MPC_SHIFT_PROVIDED = 0, 1, 2
 MPC_SHIFT_DUALS, MPC_X_DEVICE = 1, 2
+# cddp_hip_get_field_device / cddp_hip_field_shape (include/cddp_hip.h, "device-resident inputs and outputs"): enum cddp_hip_field
+FIELD_NAMES = ("X", "U", "K", "KFF", "VX", "VXX", "A", "B", "S", "Y", "G", "LAMBDA")
+FIELD_IDS = {name: i for i, name in enumerate(FIELD_NAMES)}
+# the columns of cddp_hip_get_results_device, in the order of cddp_hip_result
+RESULT_DEVICE_COLS = ("final_objective", "merit_function", "inf_pr", "inf_du", "inf_comp", "barrier_mu", "regularization", "alpha_pr", "alpha_du", "step_norm")
+RESULT_DEVICE_ICOLS = ("iterations", "status", "n_backward", "n_forward")
 
 
 # cddp_hip_plant_* / cddp_hip_mpc_run_plant / cddp_hip_track_plan (include/cddp_hip.h, "closed loop against a separate plant")
@@ -785,7 +791,7 @@ def load_hip(trig=None):
         lib.cddp_hip_create.argtypes = [C.POINTER(ProblemStruct), C.c_int, C.c_int, C.POINTER(C.c_void_p)]
         lib.cddp_hip_mpc_advance.argtypes = MPC_ADVANCE_ARGTYPES; lib.cddp_hip_mpc_advance.restype = C.c_int
         lib.cddp_hip_mpc_run.argtypes = MPC_RUN_ARGTYPES; lib.cddp_hip_mpc_run.restype = C.c_int
-        for name, at in PLANT_ARGTYPES.items():
+        for name, at in list(PLANT_ARGTYPES.items()) + list(DEVICE_IO_ARGTYPES.items()):
             fn = getattr(lib, name); fn.argtypes = at; fn.restype = C.c_int
         _hip_libs["lib"] = lib
     lib = _hip_libs["lib"]
@@ -806,6 +812,14 @@ PLANT_ARGTYPES = {
     "cddp_hip_mpc_run_plant": [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(Stats)],
     "cddp_hip_track_plan": [C.c_void_p, C.c_void_p, _dp, _dp, _dp, _dp],
 }
+# (device addresses: plain pointer values)
+DEVICE_IO_ARGTYPES = {
+    "cddp_hip_field_shape": [C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32)],
+    "cddp_hip_get_field_device": [C.c_void_p, C.c_int, C.c_void_p],
+    "cddp_hip_get_results_device": [C.c_void_p, C.c_void_p, C.c_void_p],
+    "cddp_hip_set_initial_device": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    "cddp_hip_get_live_slots": [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)],
+}
 
 EXPORTED_SYMBOLS = [
     "cddp_hip_default_options", "cddp_hip_abi_version", "cddp_hip_trig_shared", "cddp_hip_last_error", "cddp_hip_device_count",
@@ -820,6 +834,7 @@ EXPORTED_SYMBOLS = [
     "cddp_hip_stacks_get_scalars", "cddp_hip_set_terminal_equality", "cddp_hip_stacks_get_terminal", "cddp_hip_plugin_solve", "cddp_hip_plugin_solve_terminal", "cddp_hip_plugin_set_host_threads", "cddp_hip_plugin_last_stats", "cddp_hip_model_eval", "cddp_hip_set_options", "cddp_hip_set_initial_state", "cddp_hip_forget_solver_state", "cddp_hip_set_duals", "cddp_hip_set_terminal",
     "cddp_hip_costate_mode", "cddp_hip_costate_redos", "cddp_hip_mpc_advance", "cddp_hip_mpc_run",
     "cddp_hip_plant_create", "cddp_hip_plant_destroy", "cddp_hip_plant_step", "cddp_hip_mpc_run_plant", "cddp_hip_track_plan",
+    "cddp_hip_field_shape", "cddp_hip_get_field_device", "cddp_hip_get_results_device", "cddp_hip_set_initial_device", "cddp_hip_get_live_slots",
 ]
 
 
@@ -1061,6 +1076,110 @@ class HipBatchSolver:
 
     def write_gather_records_device(self, device_ptr):
         self._check(self.lib.cddp_hip_write_gather_records_device(self.h, C.c_void_p(device_ptr)))
+
+    # ---- device-resident inputs and outputs: torch.float64 tensors on the handle's device, batch-major as the numpy entries
+    def _torch_device(self):
+        import torch
+        return torch.device("cuda", self._device)
+
+    def _device_tensor(self, name, t, shape):
+        """The checks of a tensor handed to the C entry: refused here with ValueError, before the call."""
+        import torch
+        if not isinstance(t, torch.Tensor):
+            raise ValueError("%s: a torch tensor is expected, got %s" % (name, type(t).__name__))
+        if not t.is_cuda:
+            raise ValueError("%s lives on %s, the handle on device %d" % (name, t.device, self._device))
+        if t.device.index != self._device:
+            raise ValueError("%s lives on device %s, the handle on device %d" % (name, t.device.index, self._device))
+        if t.dtype != torch.float64:
+            raise ValueError("%s: dtype torch.float64 is expected, got %s" % (name, t.dtype))
+        if tuple(t.shape) != tuple(shape):
+            raise ValueError("%s: shape %s is expected, got %s" % (name, tuple(shape), tuple(t.shape)))
+        if not t.is_contiguous():
+            raise ValueError("%s must be contiguous (batch-major)" % name)
+        return t
+
+    def _order_device_io(self):
+        """Without a stream from set_stream the handle's streams know nothing of torch's: what torch has queued for the tensors is finished first."""
+        if not self._user_stream:
+            import torch
+            torch.cuda.current_stream(self._torch_device()).synchronize()
+
+    def set_initial_device(self, x0, U0=None, X0=None):
+        """set_initial from tensors on the handle's device (cddp_hip_set_initial_device): x0 (B, nx), U0 (B, N, nu) or None (zeros), X0
+        (B, N + 1, nx) or None (x0 along the horizon); row 0 of the seed is x0.  float64, contiguous.  Nothing crosses the bus; the handle is
+        left as set_initial leaves it.  Ordered on the stream given to set_stream, or after a synchronisation of torch's current stream."""
+        x0 = self._device_tensor("x0", x0, (self.B, self.p.nx))
+        if U0 is not None:
+            U0 = self._device_tensor("U0", U0, (self.B, self.p.N, self.p.nu))
+        if X0 is not None:
+            X0 = self._device_tensor("X0", X0, (self.B, self.p.N + 1, self.p.nx))
+        self._order_device_io()
+        self._check(self.lib.cddp_hip_set_initial_device(self.h, x0.data_ptr(), U0.data_ptr() if U0 is not None else None,
+                                                         X0.data_ptr() if X0 is not None else None))
+
+    def live_slots(self):
+        """The plane of the slotted fields that holds every trajectory's current iterate, (B,) int32 (cddp_hip_get_live_slots)."""
+        s = np.zeros(self.B, dtype=np.int32)
+        self._check(self.lib.cddp_hip_get_live_slots(self.h, s.ctypes.data_as(C.POINTER(C.c_int32)), None))
+        return s
+
+    def field_shape(self, name):
+        """(T, E) of the (B, T, E) array of a field of FIELD_NAMES (cddp_hip_field_shape)."""
+        if name not in FIELD_IDS:
+            raise ValueError("unknown field %r (one of %s)" % (name, ", ".join(FIELD_NAMES)))
+        rows = C.c_int32(0); cols = C.c_int32(0)
+        self._check(self.lib.cddp_hip_field_shape(self.h, FIELD_IDS[name], C.byref(rows), C.byref(cols)))
+        return int(rows.value), int(cols.value)
+
+    def field_device(self, name, out=None):
+        """One field of FIELD_NAMES as a (B, T, E) float64 tensor on the handle's device, bit for bit what its numpy getter returns
+        (cddp_hip_get_field_device).  out: a tensor to fill instead of a new one.  With a stream from set_stream the tensor is complete for
+        work queued on that stream; otherwise on return."""
+        import torch
+        T, E = self.field_shape(name)
+        if out is None:
+            out = torch.empty((self.B, T, E), dtype=torch.float64, device=self._torch_device())
+        else:
+            out = self._device_tensor("out", out, (self.B, T, E))
+        self._order_device_io()
+        self._check(self.lib.cddp_hip_get_field_device(self.h, FIELD_IDS[name], out.data_ptr()))
+        return out
+
+    def trajectory_device(self):
+        return self.field_device("X"), self.field_device("U")
+
+    def gains_device(self):
+        nx, nu = self.p.nx, self.p.nu
+        return self.field_device("K").view(self.B, self.p.N, nu, nx), self.field_device("KFF")
+
+    def value_device(self):
+        nx = self.p.nx
+        return self.field_device("VX"), self.field_device("VXX").view(self.B, self.p.N + 1, nx, nx)
+
+    def linearization_device(self):
+        nx, nu = self.p.nx, self.p.nu
+        return self.field_device("A").view(self.B, self.p.N, nx, nx), self.field_device("B").view(self.B, self.p.N, nx, nu)
+
+    def duals_device(self):
+        """(S, Y, G), each (B, N, m); refused as duals' C entry refuses a problem without slack / dual rows."""
+        return self.field_device("S"), self.field_device("Y"), self.field_device("G")
+
+    def costates_device(self):
+        return self.field_device("LAMBDA")
+
+    def results_device(self):
+        """results() on the device (cddp_hip_get_results_device): a dict of per-trajectory column views, named as RESULT_DTYPE, over one
+        (B, 10) float64 and one (B, 4) int32 tensor (also returned, as "cols" and "icols")."""
+        import torch
+        dev = self._torch_device()
+        cols = torch.empty((self.B, 10), dtype=torch.float64, device=dev); icols = torch.empty((self.B, 4), dtype=torch.int32, device=dev)
+        self._order_device_io()
+        self._check(self.lib.cddp_hip_get_results_device(self.h, cols.data_ptr(), icols.data_ptr()))
+        out = {name: cols[:, i] for i, name in enumerate(RESULT_DEVICE_COLS)}
+        out.update({name: icols[:, i] for i, name in enumerate(RESULT_DEVICE_ICOLS)})
+        out["cols"] = cols; out["icols"] = icols
+        return out
 
 
 class DevicePlant:

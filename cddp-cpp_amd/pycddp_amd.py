@@ -1143,6 +1143,50 @@ class CDDP:                         # cddp_core.hpp:214-423 / bind_solver.cpp:57
                 "status_message": [[api.STATUS_STRINGS[int(s)] for s in row] for row in r["status"]],
                 "solve_time_ms": float(r["stats"].solve_ms)}
 
+    def solve_batch_device(self, x0s, U0=None, X0=None, solver_type=SolverType.IPDDP, want=("X", "U")):
+        """NEW (no reference counterpart): solve_batch from device tensors to device tensors (cddp_hip_set_initial_device,
+        cddp_hip_get_field_device): neither the seed nor the solution crosses the bus or is transposed on the host.  x0s: (B, nx); U0:
+        (B, N, nu) or None (the trajectory of set_initial_trajectory for every member, else zeros); X0: (B, N + 1, nx) or None (likewise,
+        else x0 along the horizon) -- torch.float64, contiguous, on cuda:0, where the handle lives.  want: the fields to return, of
+        pyapi.FIELD_NAMES ("X", "U", "K", "KFF", "VX", "VXX", "A", "B", "S", "Y", "G", "LAMBDA").  Returns a dict: one (B, T, E) tensor per
+        wanted field, "results" (named per-trajectory column tensors: final_objective, ..., iterations, status, n_backward, n_forward)
+        and "solve_time_ms".  Bitwise what solve_batch computes.  Problems that solve_batch sends to the plug-in route are refused: they
+        have no resident handle."""
+        import torch
+        api = _api()
+        name = solver_type.value if isinstance(solver_type, SolverType) else str(solver_type)
+        want = tuple(want)
+        unknown = [w for w in want if w not in api.FIELD_IDS]
+        if unknown:
+            raise ValueError("want: unknown fields %s (known: %s)" % (unknown, ", ".join(api.FIELD_NAMES)))
+        if self._sys is None:
+            raise RuntimeError("Dynamical system must be set before solving.")
+        kind = self._resident_kind(name)
+        if kind is None:
+            raise NotImplementedError("solve_batch_device needs a problem of the resident route (built-in plant, objective and constraints): "
+                                      "solver '%s' with this problem runs on the plug-in route, which has no resident handle" % name)
+        if not isinstance(x0s, torch.Tensor) or x0s.dim() != 2:
+            raise ValueError("x0s: a (B, nx) torch tensor is expected")
+        B = int(x0s.shape[0])
+        if B <= 0:
+            raise ValueError("x0s: an empty batch")
+        if U0 is None and self._U is not None and x0s.is_cuda:
+            U0 = torch.as_tensor(np.ascontiguousarray(self._U, dtype=np.float64), device=x0s.device).expand(B, -1, -1).contiguous()
+        if X0 is None and self._X is not None and x0s.is_cuda:
+            X0 = torch.as_tensor(np.ascontiguousarray(self._X, dtype=np.float64), device=x0s.device).expand(B, -1, -1).contiguous()
+        p = self._problem(kind)
+        hs = api.HipBatchSolver(p, B)
+        try:
+            hs.set_initial_device(x0s, U0, X0)        # (shape, dtype, contiguity and device are checked there: ValueError)
+            st = hs.solve()
+            out = {w: hs.field_device(w) for w in want}
+            res = hs.results_device()
+        finally:
+            hs.close()
+        out["results"] = {k: v for k, v in res.items() if k not in ("cols", "icols")}
+        out["solve_time_ms"] = float(st.solve_ms)
+        return out
+
 
 __all__ = [n for n in dir() if not n.startswith("_") and n not in ("enum", "importlib", "os", "sys", "np")]
 __version__ = "0.1.0"

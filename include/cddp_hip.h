@@ -596,6 +596,37 @@ int cddp_hip_history_capacity(cddp_hip_handle *h);
  * single RCCL all-gather of SURVEY.md section 8(e). */
 int cddp_hip_write_gather_records_device(cddp_hip_handle *h, void *device_ptr);
 
+/* ---- device-resident inputs and outputs ----------------------------------
+ * A solve can start from DEVICE arrays and return DEVICE arrays: a seed proposed by a policy network, a plan consumed by a training loop
+ * or shifted by the caller's own kernel never crosses the bus and is never transposed on the host.  The arrays are batch-major, exactly
+ * what the host entries take and return ([b][t][e], contiguous doubles); kernels convert to and from the handle's internal layouts
+ * (csrc/inst_io.hip).  Pure data movement: every call is, bit for bit, its host counterpart.
+ *  - cddp_hip_field_shape: rows T and columns E of the [batch][T][E] array of a field (K: nu*nx, VXX / A: nx*nx, B: nx*nu, LAMBDA: the rows
+ *    cddp_hip_get_costates reports); no device work.  Either output may be NULL.
+ *  - cddp_hip_get_field_device: the field as its host getter returns it (cddp_hip_get_trajectory, _get_gains, _get_value,
+ *    _get_linearization, _get_duals, _get_costates), with the same refusals (no slack / dual rows, no costate trajectory).
+ *  - cddp_hip_get_results_device: cddp_hip_get_results as columns in struct order -- cols[b][10] = final_objective, merit_function, inf_pr,
+ *    inf_du, inf_comp, barrier_mu, regularization, alpha_pr, alpha_du, step_norm; icols[b][4] = iterations, status, n_backward, n_forward.
+ *  - cddp_hip_set_initial_device: cddp_hip_set_initial from device arrays (U0_dev, X0_dev may be NULL with the same meaning; row 0 of the
+ *    seed is x0 either way); the handle is left exactly as cddp_hip_set_initial leaves it.
+ * Ordering, as cddp_hip_mpc_advance with CDDP_HIP_MPC_X_DEVICE: on a handle with a stream from cddp_hip_set_stream the kernels are ordered
+ * on that stream (inputs written by work queued on it before the call are read, outputs are complete for work queued on it after) and the
+ * call does not block; otherwise the call returns after the kernels have run: outputs complete, inputs free.
+ * Refused before anything is launched, each with its own message, nothing changed: a NULL handle, an unknown field id, a NULL required
+ * pointer, a pointer that is not device memory of the handle's device (a host address, pinned or not, never reaches a kernel), a pointer
+ * whose allocation ends before the bytes the call touches.  A handle of several tile groups offsets the pointers per group.
+ * (New entry points; ABI version unchanged.) */
+enum cddp_hip_field { CDDP_HIP_FIELD_X = 0, CDDP_HIP_FIELD_U, CDDP_HIP_FIELD_K, CDDP_HIP_FIELD_KFF,
+                      CDDP_HIP_FIELD_VX, CDDP_HIP_FIELD_VXX, CDDP_HIP_FIELD_A, CDDP_HIP_FIELD_B,
+                      CDDP_HIP_FIELD_S, CDDP_HIP_FIELD_Y, CDDP_HIP_FIELD_G, CDDP_HIP_FIELD_LAMBDA };
+int cddp_hip_field_shape(cddp_hip_handle *h, int field, int32_t *rows, int32_t *cols);   /* T and E of [B][T][E]; no device work */
+int cddp_hip_get_field_device(cddp_hip_handle *h, int field, double *out_dev);           /* B*T*E doubles, batch-major */
+int cddp_hip_get_results_device(cddp_hip_handle *h, double *cols_dev /* B*10 */, int32_t *icols_dev /* B*4 */);
+int cddp_hip_set_initial_device(cddp_hip_handle *h, const double *x0_dev, const double *U0_dev, const double *X0_dev);
+/* The plane of the slotted fields (X, U, S, Y, G, Lambda) that holds every trajectory's current iterate, slots[batch] (host, may be NULL),
+ * and the number of planes: the slot rule the getters of those fields follow.  For tests and diagnosis. */
+int cddp_hip_get_live_slots(cddp_hip_handle *h, int32_t *slots, int32_t *n_slots);
+
 /* ---- multi-GPU: the single collective of the path --------------------------------------
  * One process (or host thread) per GPU, each with its own handle over a contiguous block of the global batch; nothing
  * is exchanged during a solve.  After it, ONE RCCL all-gather collects every trajectory's 16-byte record.
