@@ -212,6 +212,7 @@ class MSIPDDP:
         V_x = 2.0 * self.Qf @ (self.X[-1] - self.xref)
         V_xx = 2.0 * self.Qf; V_xx = 0.5 * (V_xx + V_xx.T)
         dV = np.zeros(2); idu = ipr = icomp = idef = snorm = 0.0
+        Vx = np.zeros((N + 1, nx)); Vxx = np.zeros((N + 1, nx, nx)); Vx[N] = V_x; Vxx[N] = V_xx     # kept for the step-level comparisons
         for t in range(N - 1, -1, -1):
             x, u, lam = self.X[t], self.U[t], self.Lam[t]
             d = self.F[t] - self.X[t + 1]
@@ -289,8 +290,9 @@ class MSIPDDP:
                 V_xx_n = Q_xx + K_u.T @ Q_ux + Q_ux.T @ K_u + K_u.T @ Q_uu @ K_u
                 ipr = max(ipr, float(np.max(np.abs(pres)))); icomp = max(icomp, float(np.max(np.abs(cres))))
             V_x, V_xx = V_x_n, 0.5 * (V_xx_n + V_xx_n.T)
+            Vx[t] = V_x; Vxx[t] = V_xx
             idu = max(idu, float(np.max(np.abs(Q_u)))); snorm = max(snorm, float(np.max(np.abs(k_u)))); idef = max(idef, float(np.max(np.abs(d))))
-        self.dV = dV; self.inf_du = idu; self.step_norm = snorm
+        self.dV = dV; self.inf_du = idu; self.step_norm = snorm; self.Vx = Vx; self.Vxx = Vxx
         if m: self.inf_pr = max(ipr, idef); self.inf_comp = icomp
         else: self.inf_pr = idef; self.inf_comp = 0.0
         return True
