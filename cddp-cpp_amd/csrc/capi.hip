@@ -221,6 +221,8 @@ struct Inner {
   // shadow costate (K4b deferred into the next sweep launch; SolveRun::enqueue_iteration, kernels_lean.hpp "K4b, deferred")
   bool shadow_bufs = false;      // the second value stack and the accept records are allocated (layout eligible at create)
   int cs_epoch = 0;              // stamps handed out: two per enqueued outer iteration over the handle's life (SolveRun::enqueue_iteration)
+  unsigned long long *h_ls = nullptr;   // pinned host copy of the rollout counter and the stage-2 tile counters (dev_types.hpp, kLsRan ...)
+  long long ls_counts[3] = {0, 0, 0};   // the last solve's stage-2 tiles that ran / returned at once / gave the poll up (cddp_hip_ls_stage_counts)
   int n_redo = 0;                // speculative solves discarded and run again with K4b on the chain (cddp_hip_costate_redos)
   bool last_shadow = false;      // the last solve ran (and kept) the shadow schedule (cddp_hip_costate_mode)
   bool ever_solved = false;
@@ -700,7 +702,7 @@ static int in_create(const cddp_hip_problem *problem, int batch, int device, con
   }
   DA(d.n_active, 1);
   DA(d.win_hist, CDDP_HIP_MAX_ALPHAS + 1);
-  DA(h->d_launched, 1);
+  DA(h->d_launched, ls_words(Bp / 64));   // + the line-search stage words (dev_types.hpp, kLsGran)
   DA(h->dP, 1);
   DA(h->d_Xinit, d.planeX); DA(h->d_Uinit, d.planeU);
   if (problem->x_ref_traj) {
@@ -741,6 +743,7 @@ static int in_destroy(Inner *h) {
   if (h->ev_poll) hipEventDestroy(h->ev_poll);
   if (h->ev_poll2) hipEventDestroy(h->ev_poll2);
   if (h->h_poll) hipHostFree(h->h_poll);
+  if (h->h_ls) hipHostFree(h->h_ls);
   if (h->h_bad) hipHostFree(h->h_bad);
   if (h->d_head) hipFree(h->d_head);
   if (h->h_head) hipHostFree(h->h_head);
@@ -978,7 +981,7 @@ static int in_forward(Inner *h, const double *alphas, int n_alphas, cddp_hip_tri
   HIPCHK(hipMemcpyAsync(h->dP, &tmp, sizeof(ProblemDev), hipMemcpyHostToDevice, h->stream));
   DevBuf dcall = h->d;   // (the caller's ladder may be any set of step sizes)
   dcall.ladder_sorted = ladder_strictly_decreasing(tmp.alphas, h->d.n_alphas);
-  h->ks->forward(dcall, h->route, h->P.solver, 0, n_alphas, PH_FWD1, 1, 0, h->stream);
+  h->ks->forward(dcall, h->route, h->P.solver, 0, n_alphas, PH_FWD1, 1, 0, h->stream, 0, 0);
   h->ks->costate(dcall, h->route, h->P.solver, 0, n_alphas, PH_FWD1, 1, 0, h->stream);
   HIPCHK(hipGetLastError());
   const DevBuf &d = h->d;
@@ -1022,6 +1025,11 @@ struct SolveRun {
   int k1 = 1, k_cap = 1, k_cap2 = 1;
   // shadow costate: K4b of an iteration rides in the next sweep launch (Inner::shadow_bufs); force_sync: the re-run of a discarded solve
   bool shadow = false, force_sync = false, pre_has_state = false, redo_needed = false;
+  // Both stages of a two-stage iteration in ONE rollout launch (kernels_lean.hpp::k_forward_ipddp_pc, split argument): first-success rule,
+  // the two-role rollout, and only with the shadow costate -- with k_costate on the chain a trial can be re-flagged 2 AFTER the rollout, and
+  // a lane may then need step sizes the launch skipped for it.  CDDP_HIP_LS_INKERNEL=0: two launches everywhere (the comparison side).
+  bool inkernel = false;
+  int poll_us = kLsPollUs;
   int stamp0 = 0;                   // the handle's stamp count when the solve began (outer iteration i carries stamp0 + 2 i and + 1)
   long waves_all = 0, per_alpha_waves = 1, two_stage_max_waves = 768;
   std::vector<int> hist_now, hist_prev;
@@ -1107,6 +1115,10 @@ struct SolveRun {
       // rollout + costate + update (~235 us) whenever ONE trajectory walks past k1: kept only for a first stage of at most 768
       // waves (CDDP_HIP_LS_TWO_MAX_WAVES; profiles/r03_ladder_sweep.md: 512 / 640 / 768 / 1024 -> 47.3 / 46.8 / 46.1 / 46.4 ms
       // per C2 solve on one box, differences at the box-to-box noise level).
+      // (Round 13: where both stages run in one rollout launch -- `inkernel` -- a miss costs one tile's chain inside the launch, not
+      //  a second group-wide rollout + update + flush.  Re-swept under that cost, profiles/r13_inkernel_stages.md section 7: 768 /
+      //  1024 / 2048 -> 37.0 / 37.2 / 37.2 ms per C2 solve, inside the spread: the threshold stays.  CDDP_HIP_LS_MARGIN=0 measured
+      //  -0.6 ms there and is recorded as a candidate, not adopted.)
       if (waves_all <= 2048 && (long)k1 * per_alpha_waves > two_stage_max_waves) one_stage = true;
       // A ladder that fits the chip once (at most one wavefront per SIMD) and light per-step work (nx <= 8): a first stage of more than
       // half of the ladder saves next to nothing over the whole ladder, while ONE trajectory past k1 costs a second full chain -- and
@@ -1148,11 +1160,16 @@ struct SolveRun {
     poll_evs[0] = h->ev_poll; poll_evs[1] = h->ev_poll2;
     win_enq = win_dig = 0; ran_ahead = false;
     if (!h->h_poll) HIPCHK(hipHostMalloc((void **)&h->h_poll, sizeof(int) * 2 * kPollWords));
-    HIPCHK(hipMemsetAsync(h->d_launched, 0, sizeof(unsigned long long), s));
+    HIPCHK(hipMemsetAsync(h->d_launched, 0, sizeof(unsigned long long) * kLsGran, s));   // the rollout counter and the stage-2 tile counters
     HIPCHK(hipEventRecord(h->ev_begin, s));
     pre_has_state = h->has_state;
     shadow = !force_sync && shadow_eligible(h, conc) && max_it > 0;
     redo_needed = false;
+    inkernel = shadow && P.ls_rule == CDDP_HIP_LS_FIRST_SUCCESS && h->knob->ls_inkernel &&
+               (h->route.rollout == Route::kPair || h->route.rollout == Route::kTwoConsumers);
+    poll_us = h->knob->ls_poll_us >= 0 ? h->knob->ls_poll_us : kLsPollUs;
+    h->ls_counts[0] = h->ls_counts[1] = h->ls_counts[2] = 0;
+    if (inkernel && !h->h_ls) HIPCHK(hipHostMalloc((void **)&h->h_ls, sizeof(unsigned long long) * kLsGran));
     h->last_shadow = shadow; h->ever_solved = true;
     if (shadow) HIPCHK(hipMemsetAsync(h->d.cs_bad, 0, sizeof(int), s));
     stamp0 = h->cs_epoch;
@@ -1201,6 +1218,8 @@ struct SolveRun {
       // accept.  The first kind cannot wait for the next sweep: the stage-2 rollout's lanes of a trajectory that is no longer in its phase
       // run along on trial slots taken relative to the NEW current slot (kernels_lean.hpp, k_forward_ipddp_pc), one of which may be the
       // slot the accepted step left -- whose x rows the costate needs.  Those rows are evaluated between update 1 and rollout 2.
+      // (Only the two-LAUNCH form of a two-stage iteration has a stage-1 update: with both stages in one rollout launch -- `inkernel`,
+      //  the default of a shadow solve -- cur[b] changes once, behind the launch, and every accept carries cs_epoch + 1.)
       h->cs_epoch += 2;
       dsh.cs_mode = 1; dsh.cs_stamp = h->cs_epoch + 1; dsh.cs_want = dsh.cs_stamp - 2;
       dsh.cs_fail_stamp = h->knob->fail_shadow > 0 ? stamp0 + 2 * h->knob->fail_shadow + 1 : 0;
@@ -1213,7 +1232,8 @@ struct SolveRun {
     hipStream_t sf = h->cu.fwd ? h->cu.fwd : s;
     auto to_fwd = [&](int k) { if (sf != s) { order_check(hipEventRecord(h->cu.ev[k], s)); order_check(hipStreamWaitEvent(sf, h->cu.ev[k], 0)); } };
     auto from_fwd = [&](int k) { if (sf != s) { order_check(hipEventRecord(h->cu.ev[k], sf)); order_check(hipStreamWaitEvent(s, h->cu.ev[k], 0)); } };
-    two_stage_marks = !one_stage;
+    const bool split = !one_stage && inkernel;   // a two-stage iteration as ONE rollout launch: the one-stage chain with the split handed to the kernel
+    two_stage_marks = !one_stage && !split;
     mark(0);
     ks->derivs(d, r, 0, s);
     tl_sweep_hop = h->cu.sweep ? &h->cu.hop : nullptr;
@@ -1223,8 +1243,10 @@ struct SolveRun {
     mark(1);
     to_fwd(0);
     if (fwd_wait) hipStreamWaitEvent(sf, fwd_wait, 0);
-    if (one_stage) {
-      ks->forward(d, r, P.solver, 0, na, PH_FWD1, 0, first_rule ? 1 : 0, sf);
+    if (one_stage || split) {
+      // (split: the workgroups of the step sizes >= k1 learn inside the launch which lanes of their tile still need them; cur[b] does not
+      //  change between the stages, so every accept carries the deferred stamp and no flush sits between rollouts)
+      ks->forward(d, r, P.solver, 0, na, PH_FWD1, 0, first_rule ? 1 : 0, sf, split ? k1 : 0, poll_us);
       if (fwd_done) hipEventRecord(fwd_done, sf);
       from_fwd(1);
       mark(2);
@@ -1233,7 +1255,7 @@ struct SolveRun {
       mark(3);
       launches += shadow ? 3 : 4;
     } else {
-      ks->forward(d, r, P.solver, 0, k1, PH_FWD1, 0, 1, sf);
+      ks->forward(d, r, P.solver, 0, k1, PH_FWD1, 0, 1, sf, 0, 0);
       from_fwd(1);
       mark(2);
       if (!shadow) ks->costate(d, r, P.solver, 0, k1, PH_FWD1, 0, 1, s);
@@ -1247,7 +1269,7 @@ struct SolveRun {
       ks->update(d, r, 1, k1, last, 0, s);
       mark(3);
       to_fwd(2);
-      ks->forward(d, r, P.solver, k1, na - k1, PH_FWD2, 0, 1, sf);
+      ks->forward(d, r, P.solver, k1, na - k1, PH_FWD2, 0, 1, sf, 0, 0);
       if (fwd_done) hipEventRecord(fwd_done, sf);
       from_fwd(3);
       mark(4);
@@ -1362,8 +1384,10 @@ struct SolveRun {
     const DevBuf &d = h->d;
     hipStream_t s = h->stream;
     HIPCHK(hipEventRecord(h->ev_end, s));
+    if (inkernel) HIPCHK(hipMemcpyAsync(h->h_ls, h->d_launched, sizeof(unsigned long long) * kLsGran, hipMemcpyDeviceToHost, s));   // read with the solve's one synchronisation
     HIPCHK(hipStreamSynchronize(s));
     HIPCHK(hipGetLastError());
+    if (inkernel) { h->ls_counts[0] = (long long)h->h_ls[kLsRan]; h->ls_counts[1] = (long long)h->h_ls[kLsRet]; h->ls_counts[2] = (long long)h->h_ls[kLsGiveUp]; }
     if (shadow && *h->h_bad != 0) { redo_needed = true; return 0; }   // discarded: cddp_hip_solve runs this group again with K4b on the chain
     if (tl_order_error != hipSuccess) {   // a cross-stream ordering call of this solve failed (launch.hpp::order_check): the results may come from racing kernels
       const hipError_t oe = tl_order_error; tl_order_error = hipSuccess;
@@ -1850,6 +1874,12 @@ int cddp_hip_costate_redos(cddp_hip_handle *h) {
   int n = 0;
   for (Inner *q : h->g) n += q->n_redo;
   return n;
+}
+int cddp_hip_ls_stage_counts(cddp_hip_handle *h, long long *counts) {
+  if (!h || !counts) return -1;
+  counts[0] = counts[1] = counts[2] = 0;
+  for (Inner *q : h->g) for (int i = 0; i < 3; ++i) counts[i] += q->ls_counts[i];
+  return 0;
 }
 int cddp_hip_concurrency(cddp_hip_handle *h) { return h ? std::max(1, std::min(h->conc, (int)h->g.size())) : -1; }
 

@@ -50,6 +50,22 @@ constexpr int kLS = 64;   // lane stride of the wave-tiled stacks (doubles)
 
 constexpr int kSinkDoubles = 1024 * 64;   // 512 KB
 
+// Second line-search stage inside the first stage's rollout launch (kernels_lean.hpp::k_forward_ipddp_pc, split argument k1).  The
+// words live BEHIND the rollout counter DevBuf::launched points at, so the kernel-argument record does not grow:
+//   [0]                          rollouts executed (as before)
+//   [kLsRan], [kLsRet], [kLsGiveUp]   stage-2 tiles of the solve that ran a trial / returned at once / gave the poll up
+//   [kLsGran + ((tile * CDDP_HIP_MAX_ALPHAS + a) * 2 + h)]   granule h (0: lanes 0-31, 1: lanes 32-63) of stage-1 step size a of a
+//                                64-trajectory tile: kLsTag in the upper word, that half of the tile's success mask in the lower.
+// A granule is ONE 8-byte word written with one atomic store: tag and value arrive together, the data is the flag.  The sweep that
+// precedes the rollout on the stream zeroes the granules (kernels_coop.hpp), so a tag is always this iteration's.
+constexpr int kLsRan = 1, kLsRet = 2, kLsGiveUp = 3, kLsGran = 8;
+constexpr unsigned kLsTag = 0x4c533231u;
+constexpr size_t ls_words(int NB) { return (size_t)kLsGran + (size_t)NB * CDDP_HIP_MAX_ALPHAS * 2; }
+// Give-up bound of the stage-2 poll, microseconds: 47 x the longest stage-1 rollout launch in the kernel trace of the headline (211 us;
+// 28 x the longest whole-ladder launch, 350 us -- profiles/r13_inkernel_stages.md section 2).  A poll outlasts its stage 1 only when the
+// tile's stage-1 workgroup was not dispatched beside it; the bound sits far above the ordinary wait, also that of ladders that share SIMDs.
+constexpr int kLsPollUs = 10000;
+
 struct DevBuf {
   int B, Bp, N, n_slots, n_alphas, hist_batch, hist_cap, NB;   // NB = Bp / 64 wave tiles
   int fail_costate_mask;                   // TEST HOOK (0 in production; environment variable CDDP_HIP_TEST_FAIL_COSTATE at create): the costate trial of

@@ -260,6 +260,11 @@ __global__ __launch_bounds__(64 * (1 + NH)) void k_backward_ipddp_coop(DevBuf d,
     }
     // (this launch replaces k_condense<.., true>, the first kernel of an outer iteration: see k_derivs)
     if (blockIdx.x == 0 && threadIdx.x == 0 && !force) *d.n_active = 0;
+    {   // ... and the first on the stream in front of the rollout: the success-mask granules of a two-stage launch start from zero (dev_types.hpp, kLsGran)
+      const int own = (int)gridDim.x - (d.cs_extra > 0 ? d.cs_extra : 0), ng = d.NB * CDDP_HIP_MAX_ALPHAS * 2;
+      for (int i = (int)blockIdx.x * (int)blockDim.x + (int)threadIdx.x; i < ng; i += own * (int)blockDim.x)
+        __hip_atomic_store(d.launched + kLsGran + i, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
     const bool act = (b < d.B) && (force || d.phase[b] == PH_ACTIVE);
     if (__builtin_amdgcn_ballot_w64(act) == 0ull) return;   // the same trajectories in every wave of the workgroup: all leave
     if (threadIdx.x == 0) {

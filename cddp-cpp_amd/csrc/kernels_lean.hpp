@@ -760,7 +760,7 @@ __device__ __attribute__((noinline)) RollOut<Model::NX> roll_step_checked(int in
 
 template <class Model, class Cons, bool TERM = false, int NC = 1>
 __global__ __launch_bounds__(64 * (1 + NC)) void k_forward_ipddp_pc(DevBuf d, const ProblemDev *__restrict__ Pk, const double *__restrict__ xrt,
-                                                                    int a0, int phase_req, int force) {
+                                                                    int a0, int phase_req, int force, int k1, int poll_us) {
   constexpr int NX = Model::NX, NU = Model::NU, M = Cons::M;
   typedef Objective<NX, NU> Obj;
   static_assert(M > 0, "two-role rollout is for path-constrained problems");
@@ -776,6 +776,7 @@ __global__ __launch_bounds__(64 * (1 + NC)) void k_forward_ipddp_pc(DevBuf d, co
   [[maybe_unused]] __shared__ int s_pfail[kL2], s_palive[kL2];   // NC = 2: consumer 1's first failing step / alive flag per lane
   [[maybe_unused]] __shared__ double s_pmax[4 * kL2];            // NC = 2: consumer 1's ev_max, ev_icomp, ys_lo, ys_hi per lane
   [[maybe_unused]] __shared__ double s_prun[kL2];                // NC = 2: the producer lane's running cost
+  __shared__ unsigned s_need[2];  // k1 > 0, stage 2: the lanes of the tile that need this step size (two halves of the 64-bit mask)
   __shared__ int s_pstat[64];     // first step at which the producer lane went non-finite (N + 2 = never)
   __shared__ double s_pcost[64];  // the producer lane's terminal cost l_f(x_N)
   __shared__ double s_xN[TERM ? NX * 64 : 1];   // the producer lane's x_N (terminal residual of the trial)
@@ -791,11 +792,59 @@ __global__ __launch_bounds__(64 * (1 + NC)) void k_forward_ipddp_pc(DevBuf d, co
   const ProblemDev *__restrict__ P = Pk;
   const cddp_hip_options &o = P->opt;
   const int N = d.N;
-  const bool active = (b < d.B) && (force || d.phase[b] == phase_req);
+  bool active = (b < d.B) && (force || d.phase[b] == phase_req);
   if (__builtin_amdgcn_ballot_w64(active) == 0ull) return;   // same mask in every wave: all leave
   if (producer) { s_pstat[lane] = N + 2; if (lane == 0) { s_prod = 0; s_consv[0] = 0; s_consv[1] = 0; if constexpr (NC > 1) { s_abort = 0x7fffffff; s_done1 = 0; } } }
   Obj::stage(P, s_obj, (int)threadIdx.x, 64 * (1 + NC));
+  // Both line-search stages in ONE launch (k1 > 0; capi.hip::SolveRun::enqueue_iteration): the workgroups of the step sizes a < k1 are
+  // stage 1 and run as in any launch; at their end the consumer publishes which of the tile's 64 trials it flagged 1 (publish_mask
+  // below).  The workgroups a >= k1 are stage 2: the trial of step size a is needed by the lanes of the tile that are in phase and
+  // for which NONE of the k1 first step sizes worked -- a function of the tile's own stage-1 trials.  One wave waits for the 2 k1
+  // granules of the tile (dev_types.hpp, kLsGran: tag and half mask in one 8-byte word, relaxed agent-scope accesses, no fence: the
+  // word is the data), the others wait at the barrier below.  The other lanes become inactive lanes.  HIP promises no dispatch
+  // order, so the wait is bounded by the wall clock (100 MHz): past poll_us the workgroup runs the trial for every lane in phase,
+  // which is what a one-stage launch does -- the first-success rule picks the same trial -- and counts a give-up.
+  const bool stage2 = k1 > 0 && a >= k1;
+  if (stage2 && producer) {
+    const unsigned long long *gran = d.launched + kLsGran + (size_t)blockIdx.x * (CDDP_HIP_MAX_ALPHAS * 2);
+    const unsigned long long in_phase = __builtin_amdgcn_ballot_w64(active);
+    const bool mine = lane < 2 * k1;   // k1 < CDDP_HIP_MAX_ALPHAS: at most 62 granules, one per lane
+    const unsigned long long t0 = wall_clock64(), bound = (unsigned long long)poll_us * 100ull;
+    unsigned long long v = 0ull;
+    bool gave_up = false;
+    for (;;) {
+      if (wall_clock64() - t0 >= bound) { gave_up = true; break; }
+      if (mine) v = __hip_atomic_load(gran + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (__builtin_amdgcn_ballot_w64(mine && (unsigned)(v >> 32) != kLsTag) == 0ull) break;
+      __builtin_amdgcn_s_sleep(16);
+    }
+    unsigned lo = 0u, hi = 0u;
+    if (!gave_up)
+      for (int i = 0; i < k1; ++i) {
+        lo |= (unsigned)__builtin_amdgcn_readlane((int)(unsigned)v, 2 * i);
+        hi |= (unsigned)__builtin_amdgcn_readlane((int)(unsigned)v, 2 * i + 1);
+      }
+    const unsigned long long need = in_phase & ~(((unsigned long long)hi << 32) | lo);
+    if (lane == 0) {
+      s_need[0] = (unsigned)need; s_need[1] = (unsigned)(need >> 32);
+      atomicAdd(d.launched + (need != 0ull ? kLsRan : kLsRet), 1ull);
+      if (gave_up) atomicAdd(d.launched + kLsGiveUp, 1ull);
+    }
+  }
   __syncthreads();
+  if (stage2) {
+    const unsigned n0 = __builtin_amdgcn_readfirstlane(s_need[0]), n1 = __builtin_amdgcn_readfirstlane(s_need[1]);
+    if ((n0 | n1) == 0u) return;   // every lane in phase has a step size among the first k1: all waves leave
+    active = active && ((((lane < 32 ? n0 : n1) >> (lane & 31)) & 1u) != 0u);
+  }
+  auto publish_mask = [&](const bool ok) {   // stage-1 consumer, all 64 lanes: the tile's success mask of this step size, as two granules
+    if (k1 > 0 && a < k1) {
+      const unsigned long long m = __builtin_amdgcn_ballot_w64(ok);
+      if (lane < 2)
+        __hip_atomic_store(d.launched + kLsGran + ((size_t)blockIdx.x * CDDP_HIP_MAX_ALPHAS + a) * 2 + lane,
+                           ((unsigned long long)kLsTag << 32) | (unsigned long long)(unsigned)(m >> (32 * lane)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+  };
   // Inactive lanes (padding, or a trajectory in another phase) run along on their OWN rows: their trial slots are
   // scratch (trial_slot never returns the current slot), so unconditional stores need no exec-mask branches.
   const int bb = (b < d.B) ? b : 0;
@@ -1272,6 +1321,7 @@ __global__ __launch_bounds__(64 * (1 + NC)) void k_forward_ipddp_pc(DevBuf d, co
     if (__hip_atomic_load(&s_abort, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) != 0x7fffffff) {   // (either wave may have posted it meanwhile)
       __hip_atomic_store(&s_consv[0], kAbort, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
       if (active) d.t_steps[ti] = fail_t;
+      publish_mask(false);
       return;
     }
   } else if constexpr (kPing) {
@@ -1287,6 +1337,7 @@ __global__ __launch_bounds__(64 * (1 + NC)) void k_forward_ipddp_pc(DevBuf d, co
         __hip_atomic_store(s_cons, kAbort, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         if (active) d.t_steps[ti] = fail_t;
         K4_TIME_END(1, t);
+        publish_mask(false);
         return;
       }
     }
@@ -1300,6 +1351,7 @@ __global__ __launch_bounds__(64 * (1 + NC)) void k_forward_ipddp_pc(DevBuf d, co
       if (__builtin_amdgcn_ballot_w64(alive) == 0ull) {
         __hip_atomic_store(s_cons, kAbort, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         if (active) d.t_steps[ti] = fail_t;
+        publish_mask(false);
         return;
       }
     }
@@ -1308,6 +1360,8 @@ __global__ __launch_bounds__(64 * (1 + NC)) void k_forward_ipddp_pc(DevBuf d, co
   K4_TIME_END(1, N);
   if (active) d.t_steps[ti] = fail_t;
   if (alive && s_pstat[lane] <= N) alive = false;
+  bool flagged = false;   // this lane's trial is flagged 1 (the lanes part ways below and meet again at publish_mask)
+  [&]() {
   if (!alive) return;
   if constexpr (NC > 1) run_cost = s_prun[lane];
   const double cost_new = run_cost + s_pcost[lane];   // + l_f(x_N)
@@ -1390,6 +1444,9 @@ __global__ __launch_bounds__(64 * (1 + NC)) void k_forward_ipddp_pc(DevBuf d, co
   d.t_inf_pr[ti] = ipr; d.t_inf_comp[ti] = icomp;
   d.t_ysmin[ti] = ys_lo; d.t_ysmax[ti] = ys_hi;
   d.t_success[ti] = accept ? 1 : 0;
+  flagged = accept;
+  }();
+  publish_mask(flagged);
 }
 
 #undef GI

@@ -34,6 +34,8 @@ struct Knobs {
   long ls_two_max_waves = env_long("CDDP_HIP_LS_TWO_MAX_WAVES", 768);   // largest first stage (wavefronts) a two-stage ladder keeps
   int ls_small_frac = env_num("CDDP_HIP_LS_SMALL_FRAC", 3, 1, INT_MAX);   // one stage when more than 1 / n of a small ladder is needed
   int ls_margin = env_num("CDDP_HIP_LS_MARGIN", 1, 0, 8);        // step sizes added to the histogram's first-stage count
+  bool ls_inkernel = env_first("CDDP_HIP_LS_INKERNEL") != '0';   // LS_INKERNEL=0: a two-stage ladder is always two rollout launches (capi.hip::SolveRun::inkernel_stages)
+  int ls_poll_us = env_num("CDDP_HIP_TEST_LS_POLL_US", -1, 0, INT_MAX);   // test hook: the stage-2 poll's give-up bound in microseconds (0: give up at once; unset: kLsPollUs)
   int run_ahead = env_num("CDDP_HIP_RUNAHEAD", 1, 0, 16);        // iterations enqueued behind a poll before the host waits for it
   int poll_every = env_num("CDDP_HIP_POLL_EVERY", 4, 1, INT_MAX);   // iterations between two "anything still running?" polls
   bool event_fence = env_first("CDDP_HIP_EVENT_FENCE") == '1';   // class-timing events with the default (system-scope fence) flags

@@ -57,7 +57,7 @@ struct KernelSet {
   Route (*route)(const DevBuf &, int solver, const Knobs &);
   void (*derivs)(const DevBuf &, const Route &, int force, hipStream_t);
   void (*backward)(const DevBuf &, const Route &, int solver, int force, int count_iter, hipStream_t);
-  void (*forward)(const DevBuf &, const Route &, int solver, int a0, int na, int phase_req, int force, int first_only, hipStream_t);
+  void (*forward)(const DevBuf &, const Route &, int solver, int a0, int na, int phase_req, int force, int first_only, hipStream_t, int k1, int poll_us);   // k1 > 0: the launch holds both line-search stages, split at step size k1 (two-role IPDDP rollout only)
   void (*costate)(const DevBuf &, const Route &, int solver, int a0, int na, int phase_req, int force, int first_only, hipStream_t);
   void (*update)(const DevBuf &, const Route &, int stage, int n1, int is_last, int do_count, hipStream_t);
   void (*init)(const DevBuf &, int mode, hipStream_t);
@@ -307,7 +307,7 @@ struct Launcher {
       hipLaunchKernelGGL((k_backward_ipddp<Model, Cons, TERM>), gridB(d), dim3(64), 0, s, d, d.P, d.xref_traj, force, count_iter);
     }
   }
-  static void forward(const DevBuf &d, const Route &r, int solver, int a0, int na, int phase_req, int force, int first_only, hipStream_t s) {
+  static void forward(const DevBuf &d, const Route &r, int solver, int a0, int na, int phase_req, int force, int first_only, hipStream_t s, int k1 = 0, int poll_us = 0) {
     if (na <= 0) return;
     const dim3 grid((d.B + 63) / 64, na);
     if (solver == CDDP_HIP_SOLVER_LOGDDP) {
@@ -337,13 +337,13 @@ struct Launcher {
         }
         // producer / consumer wave pair per (tile, alpha); CDDP_HIP_K4_CONSUMERS=2: two consumers where instantiated (opt-in, see route())
         if constexpr (PcTwoConsumers<Model, Cons>::value) {
-          if (r.rollout == Route::kTwoConsumers) { hipLaunchKernelGGL((k_forward_ipddp_pc<Model, Cons, false, 2>), grid, dim3(192), 0, s, d, d.P, d.xref_traj, a0, phase_req, force); return; }
+          if (r.rollout == Route::kTwoConsumers) { hipLaunchKernelGGL((k_forward_ipddp_pc<Model, Cons, false, 2>), grid, dim3(192), 0, s, d, d.P, d.xref_traj, a0, phase_req, force, k1, poll_us); return; }
         }
-        hipLaunchKernelGGL((k_forward_ipddp_pc<Model, Cons>), grid, dim3(128), 0, s, d, d.P, d.xref_traj, a0, phase_req, force);
+        hipLaunchKernelGGL((k_forward_ipddp_pc<Model, Cons>), grid, dim3(128), 0, s, d, d.P, d.xref_traj, a0, phase_req, force, k1, poll_us);
       } else {
         if constexpr (kTeCoop && Cons::M > 0) {   // same rollout after the cooperative terminal-equality sweep
           if (r.sweep == Route::kCoop) {
-            hipLaunchKernelGGL((k_forward_ipddp_pc<Model, Cons, true>), grid, dim3(128), 0, s, d, d.P, d.xref_traj, a0, phase_req, force);
+            hipLaunchKernelGGL((k_forward_ipddp_pc<Model, Cons, true>), grid, dim3(128), 0, s, d, d.P, d.xref_traj, a0, phase_req, force, 0, 0);
             return;
           }
         }

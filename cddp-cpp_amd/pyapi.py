@@ -832,7 +832,7 @@ EXPORTED_SYMBOLS = [
     "cddp_hip_backward_stacks", "cddp_hip_stacks_create_abi", "cddp_hip_stacks_destroy", "cddp_hip_set_stacks", "cddp_hip_set_defect_stack", "cddp_hip_set_control_box", "cddp_hip_set_hessian_stacks", "cddp_hip_set_constraint_stacks",
     "cddp_hip_stacks_backward", "cddp_hip_stacks_last_kernel_ms", "cddp_hip_stacks_last_sweep_form", "cddp_hip_stacks_factor_cache", "cddp_hip_stacks_get_gains", "cddp_hip_stacks_get_constraint_gains",
     "cddp_hip_stacks_get_scalars", "cddp_hip_set_terminal_equality", "cddp_hip_stacks_get_terminal", "cddp_hip_plugin_solve", "cddp_hip_plugin_solve_terminal", "cddp_hip_plugin_set_host_threads", "cddp_hip_plugin_last_stats", "cddp_hip_model_eval", "cddp_hip_set_options", "cddp_hip_set_initial_state", "cddp_hip_forget_solver_state", "cddp_hip_set_duals", "cddp_hip_set_terminal",
-    "cddp_hip_costate_mode", "cddp_hip_costate_redos", "cddp_hip_mpc_advance", "cddp_hip_mpc_run",
+    "cddp_hip_costate_mode", "cddp_hip_costate_redos", "cddp_hip_ls_stage_counts", "cddp_hip_mpc_advance", "cddp_hip_mpc_run",
     "cddp_hip_plant_create", "cddp_hip_plant_destroy", "cddp_hip_plant_step", "cddp_hip_mpc_run_plant", "cddp_hip_track_plan",
     "cddp_hip_field_shape", "cddp_hip_get_field_device", "cddp_hip_get_results_device", "cddp_hip_set_initial_device", "cddp_hip_get_live_slots",
 ]
@@ -882,6 +882,17 @@ class HipBatchSolver:
     def costate_redos(self):
         """Shadow solves of this handle that were discarded (non-finite deferred costate) and run again on the chain."""
         return int(self.lib.cddp_hip_costate_redos(self.h))
+
+    def ls_stage_counts(self):
+        """(ran, returned, gave_up): second-stage (tile, step size) workgroups of the last solve's two-stage iterations that ran inside
+        the first stage's rollout launch -- ran a trial, returned at once, gave the wait for the first stage's masks up.  All 0 when the
+        solve used two launches per such iteration (CDDP_HIP_LS_INKERNEL=0, costate on the chain, other solvers)."""
+        c = (C.c_longlong * 3)()
+        self.lib.cddp_hip_ls_stage_counts.argtypes = [C.c_void_p, C.POINTER(C.c_longlong)]
+        rc = self.lib.cddp_hip_ls_stage_counts(self.h, c)
+        if rc != 0:
+            raise HipError("cddp_hip_ls_stage_counts failed: %d" % rc)
+        return int(c[0]), int(c[1]), int(c[2])
 
     def set_stream(self, stream_ptr):
         self._check(self.lib.cddp_hip_set_stream(self.h, C.c_void_p(stream_ptr)))

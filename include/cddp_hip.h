@@ -459,6 +459,12 @@ int cddp_hip_solve(cddp_hip_handle *h, cddp_hip_stats *stats);
 int cddp_hip_costate_mode(cddp_hip_handle *h);
 /* Deferred solves of this handle that met a non-finite costate row, were discarded and run again on the chain (0 on healthy problems). */
 int cddp_hip_costate_redos(cddp_hip_handle *h);
+/* Two-stage line-search iterations of the last cddp_hip_solve that ran both stages in ONE rollout launch (deferred costate, first-success
+ * rule, two-role rollout; CDDP_HIP_LS_INKERNEL=0 turns the form off): counts[0] = second-stage (tile, step size) workgroups that ran a
+ * trial, counts[1] = those that returned at once because the first stage had served every lane of their tile, counts[2] = those that
+ * gave up waiting for the first stage's masks and ran the trial for every lane in phase (correct, and 0 unless the device dispatched a
+ * second stage without its first).  All 0 when no launch took the form.  Summed over the handle's tile groups. */
+int cddp_hip_ls_stage_counts(cddp_hip_handle *h, long long *counts);
 
 /* ---- device-resident MPC step --------------------------------------------
  * Between two solves of a receding-horizon loop the plan does not leave the device: cddp_hip_mpc_advance makes the seed of the next
