@@ -15,6 +15,7 @@
 #include "launch.hpp"
 #include "plant.hpp"
 #include "io_kernels.hpp"
+#include "sens_kernels.hpp"
 
 // 1 when a[0] > a[1] > ... > a[n - 1] (NaN-free): the ladders cddp_hip_build_alphas makes; DevBuf::ladder_sorted
 static int ladder_strictly_decreasing(const double *a, int n) {
@@ -2216,6 +2217,103 @@ int cddp_hip_set_initial_device(cddp_hip_handle *h, const double *x0_dev, const 
     q->have_initial = true; q->initialized = false; q->initial_dirty = true;   // as in_set_initial leaves them
   }
   return io_finish(h);
+}
+
+// ---- linear response of the plan to its initial state (inst_sens.hip): forward and adjoint recursions over the A / Bm / K stacks ----
+// the refusals the two entries share, in the order of the header; nothing is launched and nothing changed before they have all passed
+static int sens_refuse(const char *entry, const cddp_hip_handle *h, int flags, int nvec) {
+  if (!h) return fail(-1, "%s: null handle", entry);
+  if (flags & ~CDDP_HIP_SENS_DEVICE) return fail(-2, "%s: unknown flag bits 0x%x (CDDP_HIP_SENS_DEVICE is the only flag)", entry, (unsigned)(flags & ~CDDP_HIP_SENS_DEVICE));
+  if (nvec < 1) return fail(-2, "%s: nvec = %d, at least one vector is needed", entry, nvec);
+  return 0;
+}
+static int sens_refuse_handle(const char *entry, const cddp_hip_handle *h) {
+  if (h->g[0]->P.solver == CDDP_HIP_SOLVER_MSIPDDP)
+    return fail(-1, "%s: not for an MSIPDDP handle: its plan carries defects and its gains belong to the gap-closing recursion, so this recursion is not its response", entry);
+  for (const Inner *q : h->g) {
+    if (!q->has_plan) return fail(-1, "%s needs a solved handle: there are no A, B and K stacks before cddp_hip_solve (or cddp_hip_initialize and cddp_hip_backward)", entry);
+    if (!q->d.A || !q->d.Bm || !q->d.K) return fail(-1, "%s: this handle keeps no A / B / K stacks", entry);
+  }
+  return 0;
+}
+static SensStacks sens_stacks(const Inner *q) {
+  const DevBuf &d = q->d;
+  return SensStacks{d.A, d.Bm, d.K, q->route.t4 ? cddp_io::kT4 : cddp_io::kTiled, d.B, d.NB, d.N, q->P.nx, q->P.nu};   // (io_field: the layout of A / Bm)
+}
+// a temporary device array of a host-pointer call, freed when the call returns
+struct SensTmp {
+  double *p = nullptr;
+  ~SensTmp() { if (p) (void)hipFree(p); }
+  int alloc(size_t n) { HIPCHK(hipMalloc((void **)&p, n * sizeof(double))); return 0; }
+};
+
+int cddp_hip_plan_jvp(cddp_hip_handle *h, int flags, int nvec, const double *dx0, double *dX, double *dU) {
+  static const char *const me = "cddp_hip_plan_jvp";
+  { int rc = sens_refuse(me, h, flags, nvec); if (rc) return rc; }
+  if (!dx0) return fail(-1, "%s: null dx0 pointer", me);
+  if (!dX && !dU) return fail(-1, "%s: dX and dU are both null: nothing to compute", me);
+  { int rc = sens_refuse_handle(me, h); if (rc) return rc; }
+  HIPCHK(hipSetDevice(h->device));
+  const size_t n0 = (size_t)nvec * h->nx, nX = (size_t)nvec * (h->N + 1) * h->nx, nU = (size_t)nvec * h->N * h->nu, B = (size_t)h->B;
+  const bool dev = (flags & CDDP_HIP_SENS_DEVICE) != 0;
+  SensTmp t0, tX, tU;
+  const double *d0 = dx0; double *dXd = dX, *dUd = dU;
+  if (dev) {
+    { int rc = io_check_pointer(h, dx0, B * n0 * sizeof(double), me, "dx0"); if (rc) return rc; }
+    if (dX) { int rc = io_check_pointer(h, dX, B * nX * sizeof(double), me, "dX"); if (rc) return rc; }
+    if (dU) { int rc = io_check_pointer(h, dU, B * nU * sizeof(double), me, "dU"); if (rc) return rc; }
+  } else {
+    { int rc = t0.alloc(B * n0); if (rc) return rc; }
+    HIPCHK(hipMemcpy(t0.p, dx0, B * n0 * sizeof(double), hipMemcpyHostToDevice));
+    d0 = t0.p;
+    if (dX) { int rc = tX.alloc(B * nX); if (rc) return rc; dXd = tX.p; }
+    if (dU) { int rc = tU.alloc(B * nU); if (rc) return rc; dUd = tU.p; }
+  }
+  { int rc = fork_from_user(h); if (rc) return rc; }
+  for (size_t gi = 0; gi < h->g.size(); ++gi) {
+    const Inner *q = h->g[gi];
+    const size_t b0 = (size_t)h->b0[gi];
+    HIPCHK(sens_jvp(sens_stacks(q), nvec, d0 + b0 * n0, dXd ? dXd + b0 * nX : nullptr, dUd ? dUd + b0 * nU : nullptr, q->stream));
+  }
+  if (dev) return io_finish(h);
+  HIPCHK(hipGetLastError());
+  for (Inner *q : h->g) HIPCHK(hipStreamSynchronize(q->stream));
+  if (dX) HIPCHK(hipMemcpy(dX, tX.p, B * nX * sizeof(double), hipMemcpyDeviceToHost));
+  if (dU) HIPCHK(hipMemcpy(dU, tU.p, B * nU * sizeof(double), hipMemcpyDeviceToHost));
+  return join_to_user(h);
+}
+
+int cddp_hip_plan_vjp(cddp_hip_handle *h, int flags, int nvec, const double *gX, const double *gU, double *gx0) {
+  static const char *const me = "cddp_hip_plan_vjp";
+  { int rc = sens_refuse(me, h, flags, nvec); if (rc) return rc; }
+  if (!gx0) return fail(-1, "%s: null gx0 pointer", me);
+  { int rc = sens_refuse_handle(me, h); if (rc) return rc; }
+  HIPCHK(hipSetDevice(h->device));
+  const size_t n0 = (size_t)nvec * h->nx, nX = (size_t)nvec * (h->N + 1) * h->nx, nU = (size_t)nvec * h->N * h->nu, B = (size_t)h->B;
+  const bool dev = (flags & CDDP_HIP_SENS_DEVICE) != 0;
+  SensTmp t0, tX, tU;
+  const double *gXd = gX, *gUd = gU; double *g0 = gx0;
+  if (dev) {
+    if (gX) { int rc = io_check_pointer(h, gX, B * nX * sizeof(double), me, "gX"); if (rc) return rc; }
+    if (gU) { int rc = io_check_pointer(h, gU, B * nU * sizeof(double), me, "gU"); if (rc) return rc; }
+    { int rc = io_check_pointer(h, gx0, B * n0 * sizeof(double), me, "gx0"); if (rc) return rc; }
+  } else {
+    { int rc = t0.alloc(B * n0); if (rc) return rc; }
+    g0 = t0.p;
+    if (gX) { int rc = tX.alloc(B * nX); if (rc) return rc; HIPCHK(hipMemcpy(tX.p, gX, B * nX * sizeof(double), hipMemcpyHostToDevice)); gXd = tX.p; }
+    if (gU) { int rc = tU.alloc(B * nU); if (rc) return rc; HIPCHK(hipMemcpy(tU.p, gU, B * nU * sizeof(double), hipMemcpyHostToDevice)); gUd = tU.p; }
+  }
+  { int rc = fork_from_user(h); if (rc) return rc; }
+  for (size_t gi = 0; gi < h->g.size(); ++gi) {
+    const Inner *q = h->g[gi];
+    const size_t b0 = (size_t)h->b0[gi];
+    HIPCHK(sens_vjp(sens_stacks(q), nvec, gXd ? gXd + b0 * nX : nullptr, gUd ? gUd + b0 * nU : nullptr, g0 + b0 * n0, q->stream));
+  }
+  if (dev) return io_finish(h);
+  HIPCHK(hipGetLastError());
+  for (Inner *q : h->g) HIPCHK(hipStreamSynchronize(q->stream));
+  HIPCHK(hipMemcpy(gx0, t0.p, B * n0 * sizeof(double), hipMemcpyDeviceToHost));
+  return join_to_user(h);
 }
 
 int cddp_hip_mpc_run(cddp_hip_handle *h, int steps, int mode, int flags, double *U_applied, double *X_visited, int32_t *iterations, int32_t *status,

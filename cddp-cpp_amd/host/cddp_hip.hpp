@@ -873,6 +873,18 @@ class HipBatchSolver : public ISolverAlgorithm {
     if (!h_) throw std::runtime_error("cddp_hip: setInitialDevice needs a resident batch (the plug-in route has no resident handle)");
     check(cddp_hip_set_initial_device(h_, x0_dev, U0_dev, X0_dev));
   }
+  // NEW: the linear response of the resident batch's plans to their initial states (cddp_hip_plan_jvp / cddp_hip_plan_vjp): forward,
+  // dx_{t+1} = A_t dx_t + B_t du_t with du_t = K_t dx_t from dx0, and its adjoint from the gradients of a loss with respect to (X, U), over
+  // the stacks of the last backward sweep.  Arrays are [batch][nvec][t][e]; flags = 0: host pointers, CDDP_HIP_SENS_DEVICE: device pointers
+  // of the solver's device.  dX or dU may be nullptr (not both); gX or gU nullptr = zeros.
+  void planJvp(int flags, int nvec, const double *dx0 /* batch*nvec*nx */, double *dX /* batch*nvec*(N+1)*nx */, double *dU /* batch*nvec*N*nu */) {
+    if (!h_) throw std::runtime_error("cddp_hip: planJvp needs a resident batch (the plug-in route has no resident handle)");
+    check(cddp_hip_plan_jvp(h_, flags, nvec, dx0, dX, dU));
+  }
+  void planVjp(int flags, int nvec, const double *gX /* batch*nvec*(N+1)*nx */, const double *gU /* batch*nvec*N*nu */, double *gx0 /* batch*nvec*nx */) {
+    if (!h_) throw std::runtime_error("cddp_hip: planVjp needs a resident batch (the plug-in route has no resident handle)");
+    check(cddp_hip_plan_vjp(h_, flags, nvec, gX, gU, gx0));
+  }
   // NEW: solve the resident batch again from the seed it holds now (setInitialDevice, mpcAdvance) -- solveBatch() without creating and uploading
   std::vector<CDDPSolution> resolveBatch(CDDP &ctx) {
     if (!h_) throw std::runtime_error("cddp_hip: resolveBatch needs a resident batch (the plug-in route has no resident handle)");

@@ -165,6 +165,8 @@ TIMING_ROLLOUT, TIMING_ALL, TIMING_SWEEP = 0, 1, 2
 # cddp_hip_mpc_advance / cddp_hip_mpc_run (include/cddp_hip.h, "device-resident MPC step")
 MPC_KEEP_PLAN, MPC_SHIFT_EXISTING, MPC_SHIFT_PROVIDED = 0, 1, 2
 MPC_SHIFT_DUALS, MPC_X_DEVICE = 1, 2
+# cddp_hip_plan_jvp / cddp_hip_plan_vjp (include/cddp_hip.h, "linear response of a solved plan to its initial state")
+SENS_DEVICE = 1
 # cddp_hip_get_field_device / cddp_hip_field_shape (include/cddp_hip.h, "device-resident inputs and outputs"): enum cddp_hip_field
 FIELD_NAMES = ("X", "U", "K", "KFF", "VX", "VXX", "A", "B", "S", "Y", "G", "LAMBDA")
 FIELD_IDS = {name: i for i, name in enumerate(FIELD_NAMES)}
@@ -819,6 +821,9 @@ DEVICE_IO_ARGTYPES = {
     "cddp_hip_get_results_device": [C.c_void_p, C.c_void_p, C.c_void_p],
     "cddp_hip_set_initial_device": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
     "cddp_hip_get_live_slots": [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)],
+    # (host or device addresses, by the flag: plain pointer values)
+    "cddp_hip_plan_jvp": [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
+    "cddp_hip_plan_vjp": [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
 }
 
 EXPORTED_SYMBOLS = [
@@ -835,6 +840,7 @@ EXPORTED_SYMBOLS = [
     "cddp_hip_costate_mode", "cddp_hip_costate_redos", "cddp_hip_ls_stage_counts", "cddp_hip_mpc_advance", "cddp_hip_mpc_run",
     "cddp_hip_plant_create", "cddp_hip_plant_destroy", "cddp_hip_plant_step", "cddp_hip_mpc_run_plant", "cddp_hip_track_plan",
     "cddp_hip_field_shape", "cddp_hip_get_field_device", "cddp_hip_get_results_device", "cddp_hip_set_initial_device", "cddp_hip_get_live_slots",
+    "cddp_hip_plan_jvp", "cddp_hip_plan_vjp",
 ]
 
 
@@ -853,6 +859,7 @@ class HipBatchSolver:
         self._check(rc)
         self.m = self.lib.cddp_hip_dual_dim(self.h)
         self._user_stream = False; self._device = int(device)
+        self.plan_epoch = 0      # counts the calls that rewrite the A / B / K stacks (sweeps): what plan_jvp / plan_vjp read belongs to the last of them
 
     def _check(self, rc):
         if rc != 0:
@@ -909,6 +916,7 @@ class HipBatchSolver:
         self._check(self.lib.cddp_hip_set_initial(self.h, _ptr(x0), _ptr(U0), _ptr(X0)))
 
     def initialize(self):
+        self.plan_epoch += 1
         self._check(self.lib.cddp_hip_initialize(self.h))
 
     # ---- warm start / MPC restarts
@@ -941,6 +949,7 @@ class HipBatchSolver:
         self._check(self.lib.cddp_hip_set_terminal(self.h, _ptr(a[0]), _ptr(a[1]), _ptr(a[2])))
 
     def backward(self):
+        self.plan_epoch += 1
         ok = np.zeros(self.B, dtype=np.int32)
         self._check(self.lib.cddp_hip_backward(self.h, ok.ctypes.data_as(C.POINTER(C.c_int32))))
         return ok
@@ -951,6 +960,7 @@ class HipBatchSolver:
         return t
 
     def solve(self):
+        self.plan_epoch += 1
         st = Stats()
         self._check(self.lib.cddp_hip_solve(self.h, C.byref(st)))
         return st
@@ -998,7 +1008,7 @@ class HipBatchSolver:
         """`steps` closed-loop MPC steps with the model as the plant (cddp_hip_mpc_run): solve, record, advance -- one call, one copy per
         output.  Returns a dict: U_applied (B, steps, nu), X_visited (B, steps + 1, nx), iterations and status (B, steps, int32), stats
         (the per-solve Stats added up)."""
-        steps = int(steps)
+        steps = int(steps); self.plan_epoch += 1
         U = np.zeros((self.B, max(steps, 0), self.p.nu)); X = np.zeros((self.B, max(steps, 0) + 1, self.p.nx))
         it = np.zeros((self.B, max(steps, 0)), dtype=np.int32); st = np.zeros((self.B, max(steps, 0)), dtype=np.int32)
         stats = Stats()
@@ -1011,7 +1021,7 @@ class HipBatchSolver:
         """`steps` closed-loop MPC steps against a DevicePlant (cddp_hip_mpc_run_plant): solve, plant step on the device from row 0 of the
         plan and its u_0 (saturated, disturbed by W[:, k]), advance from the plant's state.  W: None or (B, steps, nx), uploaded once.
         Returns the dict of mpc_run; U_applied holds the saturated controls, X_visited the plant's states."""
-        steps = int(steps)
+        steps = int(steps); self.plan_epoch += 1
         U = np.zeros((self.B, max(steps, 0), self.p.nu)); X = np.zeros((self.B, max(steps, 0) + 1, self.p.nx))
         it = np.zeros((self.B, max(steps, 0)), dtype=np.int32); st = np.zeros((self.B, max(steps, 0)), dtype=np.int32)
         Wa = _arr(W).reshape(self.B, max(steps, 0), self.p.nx) if W is not None else None
@@ -1191,6 +1201,92 @@ class HipBatchSolver:
         out.update({name: icols[:, i] for i, name in enumerate(RESULT_DEVICE_ICOLS)})
         out["cols"] = cols; out["icols"] = icols
         return out
+
+
+    # ---- linear response of the plan to its initial state (cddp_hip_plan_jvp / cddp_hip_plan_vjp): numpy arrays take the host path,
+    # torch.float64 tensors on the handle's device the device path; the result is of the kind of the input
+    def _sens_arg(self, name, a, tail, nvec=None, squeeze=None):
+        """One array argument, (B,) + tail or (B, R) + tail -> (the contiguous (B, R) + tail array, R, whether the vector axis was absent)."""
+        is_t = hasattr(a, "data_ptr")
+        shape = tuple(a.shape)
+        if shape == (self.B,) + tuple(tail):
+            R, sq = 1, True
+        elif len(shape) == len(tail) + 2 and shape[0] == self.B and shape[2:] == tuple(tail) and shape[1] >= 1:
+            R, sq = int(shape[1]), False
+        else:
+            raise ValueError("%s: shape %s or %s is expected, got %s" % (name, (self.B,) + tuple(tail), (self.B, "R") + tuple(tail), shape))
+        if nvec is not None and (R != nvec or sq != squeeze):
+            raise ValueError("%s: %d vector(s) per trajectory, the other argument has %d (or only one of them has the vector axis)" % (name, R, nvec))
+        full = (self.B, R) + tuple(tail)
+        if is_t:
+            a = self._device_tensor(name, a.reshape(full) if a.is_contiguous() else a, full)
+        else:
+            a = _arr(a).reshape(full)
+        return a, R, sq
+
+    def plan_jvp(self, dx0, want=("dX", "dU")):
+        """The first-order response of the closed-loop plan to a change dx0 of its initial state (cddp_hip_plan_jvp): dx_{t+1} = A_t dx_t +
+        B_t du_t, du_t = K_t dx_t over the stacks of the last backward sweep.  dx0: (B, nx) or (B, R, nx), a numpy array or a torch.float64
+        tensor on the handle's device.  Returns (dX, dU) of shape (B, [R,] N + 1, nx) and (B, [R,] N, nu), of dx0's kind; an output that
+        `want` does not name is None.  The handle's state is not modified."""
+        want = tuple(want)
+        if not want or any(w not in ("dX", "dU") for w in want):
+            raise ValueError("want: a non-empty subset of ('dX', 'dU') is expected, got %r" % (want,))
+        N, nx, nu = self.p.N, self.p.nx, self.p.nu
+        d, R, sq = self._sens_arg("dx0", dx0, (nx,))
+        sx = (self.B, N + 1, nx) if sq else (self.B, R, N + 1, nx)
+        su = (self.B, N, nu) if sq else (self.B, R, N, nu)
+        if hasattr(d, "data_ptr"):
+            import torch
+            dev = self._torch_device()
+            dX = torch.empty(sx, dtype=torch.float64, device=dev) if "dX" in want else None
+            dU = torch.empty(su, dtype=torch.float64, device=dev) if "dU" in want else None
+            self._order_device_io()
+            self._check(self.lib.cddp_hip_plan_jvp(self.h, SENS_DEVICE, R, d.data_ptr(), dX.data_ptr() if dX is not None else None,
+                                                   dU.data_ptr() if dU is not None else None))
+        else:
+            dX = np.zeros(sx) if "dX" in want else None
+            dU = np.zeros(su) if "dU" in want else None
+            self._check(self.lib.cddp_hip_plan_jvp(self.h, 0, R, d.ctypes.data, dX.ctypes.data if dX is not None else None,
+                                                   dU.ctypes.data if dU is not None else None))
+        return dX, dU
+
+    def plan_vjp(self, gX=None, gU=None):
+        """The gradient with respect to x_0 of a loss on the plan, from its gradients gX (B, [R,] N + 1, nx) and gU (B, [R,] N, nu) with
+        respect to (X, U); None = zeros (cddp_hip_plan_vjp: the adjoint of plan_jvp's recursion).  numpy arrays or torch.float64 tensors on
+        the handle's device, both of one kind.  Returns (B, [R,] nx) of that kind."""
+        N, nx, nu = self.p.N, self.p.nx, self.p.nu
+        if gX is None and gU is None:
+            raise ValueError("plan_vjp: gX and gU are both None (the gradient would be zero)")
+        gx = gu = None; R = sq = None
+        if gX is not None:
+            gx, R, sq = self._sens_arg("gX", gX, (N + 1, nx))
+        if gU is not None:
+            gu, R, sq = self._sens_arg("gU", gU, (N, nu), R, sq)
+        kinds = {hasattr(a, "data_ptr") for a in (gx, gu) if a is not None}
+        if len(kinds) != 1:
+            raise ValueError("plan_vjp: gX and gU must both be numpy arrays or both be device tensors")
+        s0 = (self.B, nx) if sq else (self.B, R, nx)
+        if kinds.pop():
+            import torch
+            g0 = torch.empty(s0, dtype=torch.float64, device=self._torch_device())
+            self._order_device_io()
+            self._check(self.lib.cddp_hip_plan_vjp(self.h, SENS_DEVICE, R, gx.data_ptr() if gx is not None else None,
+                                                   gu.data_ptr() if gu is not None else None, g0.data_ptr()))
+        else:
+            g0 = np.zeros(s0)
+            self._check(self.lib.cddp_hip_plan_vjp(self.h, 0, R, gx.ctypes.data if gx is not None else None,
+                                                   gu.ctypes.data if gu is not None else None, g0.ctypes.data))
+        return g0
+
+    def plan_jacobian_device(self):
+        """(dX/dx0 (B, N + 1, nx, nx), dU/dx0 (B, N, nu, nx)) as device tensors, from ONE plan_jvp with the nx unit vectors: entry
+        [b, t, i, j] is the response of X[b, t, i] (U[b, t, i]) to x0[b, j]."""
+        import torch
+        nx = self.p.nx
+        eye = torch.eye(nx, dtype=torch.float64, device=self._torch_device()).expand(self.B, nx, nx).contiguous()
+        dX, dU = self.plan_jvp(eye)
+        return dX.permute(0, 2, 3, 1).contiguous(), dU.permute(0, 2, 3, 1).contiguous()
 
 
 class DevicePlant:

@@ -1187,6 +1187,84 @@ class CDDP:                         # cddp_core.hpp:214-423 / bind_solver.cpp:57
         out["solve_time_ms"] = float(st.solve_ms)
         return out
 
+    def solve_batch_diff(self, x0s, U0=None, X0=None, solver_type=SolverType.IPDDP, refresh=False):
+        """NEW (no reference counterpart): solve_batch_device as a differentiable function of x0s (cddp_hip_plan_vjp).  Returns a dict: "X"
+        (B, N + 1, nx) and "U" (B, N, nu), tensors whose backward pass carries a loss gradient on (X, U) into x0s.grad through the adjoint of
+        the closed-loop linear response dx_{t+1} = A_t dx_t + B_t du_t, du_t = K_t dx_t (with CLDDP the active-set derivative, with IPDDP
+        the condensed interior-point gain); "results" and "solve_time_ms" as solve_batch_device; "solver": the resident
+        pyapi.HipBatchSolver, which stays open because the backward pass reads its stacks -- close() it when done.  The seeds U0 / X0 get no
+        gradient: at a solution the plan does not depend on its seed to first order.  The stacks belong to the last backward sweep, one
+        accepted step before the returned plan; refresh=True runs one more sweep at the returned plan first (its error, if any, is
+        raised).  A backward pass after another sweep of the same solver (solve, backward, initialize, an MPC run) raises RuntimeError
+        instead of returning the gradient of another plan.  MSIPDDP is refused."""
+        import torch
+        api = _api()
+        name = solver_type.value if isinstance(solver_type, SolverType) else str(solver_type)
+        if self._sys is None:
+            raise RuntimeError("Dynamical system must be set before solving.")
+        kind = self._resident_kind(name)
+        if kind is None:
+            raise NotImplementedError("solve_batch_diff needs a problem of the resident route (built-in plant, objective and constraints): "
+                                      "solver '%s' with this problem runs on the plug-in route, which has no resident handle" % name)
+        if not isinstance(x0s, torch.Tensor) or x0s.dim() != 2:
+            raise ValueError("x0s: a (B, nx) torch tensor is expected")
+        B = int(x0s.shape[0])
+        if B <= 0:
+            raise ValueError("x0s: an empty batch")
+        if U0 is None and self._U is not None and x0s.is_cuda:
+            U0 = torch.as_tensor(np.ascontiguousarray(self._U, dtype=np.float64), device=x0s.device).expand(B, -1, -1).contiguous()
+        if X0 is None and self._X is not None and x0s.is_cuda:
+            X0 = torch.as_tensor(np.ascontiguousarray(self._X, dtype=np.float64), device=x0s.device).expand(B, -1, -1).contiguous()
+        hs = api.HipBatchSolver(self._problem(kind), B)
+        try:
+            stats = {}
+            X, U = _plan_function()(x0s, U0, X0, hs, bool(refresh), stats)
+            res = hs.results_device()
+        except Exception:
+            hs.close()
+            raise
+        return {"X": X, "U": U, "results": {k: v for k, v in res.items() if k not in ("cols", "icols")},
+                "solve_time_ms": float(stats["solve_ms"]), "solver": hs}
+
+
+_PLAN_FUNCTION = []
+
+
+def _plan_function():
+    """The torch.autograd.Function of CDDP.solve_batch_diff (made at first use: importing this module does not import torch)."""
+    if _PLAN_FUNCTION:
+        return _PLAN_FUNCTION[0].apply
+    import torch
+
+    class _PlanOfInitialState(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, x0s, U0, X0, hs, refresh, stats):
+            x0 = x0s.detach()
+            hs.set_initial_device(x0 if x0.is_contiguous() else x0.contiguous(), U0.detach() if U0 is not None else None,
+                                  X0.detach() if X0 is not None else None)     # (shape, dtype, device: ValueError there)
+            stats["solve_ms"] = hs.solve().solve_ms
+            if refresh:
+                hs.backward()          # the stacks at the returned plan; a failed call raises HipError
+            ctx.hs = hs; ctx.epoch = hs.plan_epoch
+            X, U = hs.field_device("X"), hs.field_device("U")
+            return X, U
+
+        @staticmethod
+        def backward(ctx, gX, gU):
+            hs = ctx.hs
+            if not hs.h:
+                raise RuntimeError("solve_batch_diff: the solver was closed before the backward pass; its stacks are gone")
+            if hs.plan_epoch != ctx.epoch:
+                raise RuntimeError("solve_batch_diff: stale plan -- the solver has run another sweep (solve, backward, initialize or an MPC run) since "
+                                   "this plan was returned, so its A, B and K stacks belong to another plan; run the backward pass before reusing the solver")
+            if not ctx.needs_input_grad[0] or (gX is None and gU is None):
+                return None, None, None, None, None, None
+            g0 = hs.plan_vjp(gX.contiguous() if gX is not None else None, gU.contiguous() if gU is not None else None)
+            return g0, None, None, None, None, None
+
+    _PLAN_FUNCTION.append(_PlanOfInitialState)
+    return _PlanOfInitialState.apply
+
 
 __all__ = [n for n in dir() if not n.startswith("_") and n not in ("enum", "importlib", "os", "sys", "np")]
 __version__ = "0.1.0"

@@ -633,6 +633,41 @@ int cddp_hip_set_initial_device(cddp_hip_handle *h, const double *x0_dev, const 
  * and the number of planes: the slot rule the getters of those fields follow.  For tests and diagnosis. */
 int cddp_hip_get_live_slots(cddp_hip_handle *h, int32_t *slots, int32_t *n_slots);
 
+/* ---- linear response of a solved plan to its initial state -----------------
+ * The first-order response of the closed-loop plan to a change of x_0 is the recursion dx_{t+1} = A_t dx_t + B_t du_t, du_t = K_t dx_t; the
+ * gradient of a loss on (X, U) with respect to x_0 is its adjoint.  Both run on the device over the stacks where the sweep left them
+ * (csrc/inst_sens.hip): no stack is copied or un-tiled.  With CLDDP K_t carries the clamped rows of the BoxQP (the active-set derivative),
+ * with IPDDP it is the condensed interior-point gain.  Run forward, the recursion is the neighbouring-extremal correction of a plan for a
+ * measured state.
+ * WHICH SWEEP: K_t, A_t, B_t are the stacks cddp_hip_get_gains and cddp_hip_get_linearization read at the time of the call.  They belong to
+ * the LAST BACKWARD SWEEP, which ran at the iterate BEFORE the last accepted step, not at the returned plan; at a converged solve the
+ * difference is of the size of the last step.  A caller who wants them at the returned plan calls cddp_hip_backward first.
+ * Arrays: batch-major, then the vector index, then time, then the element: [b][r][t][e], contiguous doubles, nvec vectors per trajectory.
+ * flags = 0: host pointers; the call uploads, computes, downloads and returns when the outputs are written.  CDDP_HIP_SENS_DEVICE: every
+ * array argument is a device pointer of the handle's device, checked and ordered as cddp_hip_get_field_device checks and orders its own
+ * (see "device-resident inputs and outputs"); a handle of several tile groups offsets the pointers per group.  The handle's state is not
+ * modified.
+ * Arithmetic (the library is built with -ffp-contract=off: every product is rounded before it is added), per trajectory and per vector:
+ *  - cddp_hip_plan_jvp: dx_0 = dx0.  For t = 0 .. N-1, first du_t: s = 0; for j ascending s += K_t[i][j] * dx_t[j]; du_t[i] = s.  Then
+ *    dx_{t+1}: s = 0; for j ascending s += A_t[i][j] * dx_t[j]; for k ascending, on the same accumulator, s += B_t[i][k] * du_t[k];
+ *    dx_{t+1}[i] = s.  dX rows are dx_0 .. dx_N, dU rows du_0 .. du_{N-1}; either output may be NULL, not both.
+ *  - cddp_hip_plan_vjp: lam = gX_N (zeros when gX is NULL).  For t = N-1 .. 0, first mu: s = 0; for i ascending s += B_t[i][k] * lam[i];
+ *    mu[k] = gU_t[k] + s (mu[k] = s when gU is NULL).  Then lam': s = 0; for i ascending s += A_t[i][j] * lam[i]; for k ascending
+ *    s += K_t[k][j] * mu[k]; lam'[j] = gX_t[j] + s (lam'[j] = s when gX is NULL); lam = lam'.  gx0 = lam after t = 0.
+ *  Non-finite stack rows propagate; nothing is special-cased.  (The sign of an exact zero is not specified.)
+ * Refused before anything is launched, each with its own message, nothing changed: a NULL handle, unknown flag bits, nvec < 1, a NULL dx0
+ * or gx0, dX and dU both NULL, a handle that was never solved or swept, an MSIPDDP handle (its plan carries defects and its gains belong to
+ * the gap-closing recursion, so this recursion is not its response), and with CDDP_HIP_SENS_DEVICE a pointer cddp_hip_get_field_device
+ * would refuse.  (New entry points; ABI version unchanged.) */
+enum { CDDP_HIP_SENS_DEVICE = 1 };   /* all array arguments are device pointers of the handle's device */
+int cddp_hip_plan_jvp(cddp_hip_handle *h, int flags, int nvec,
+                      const double *dx0 /* B*nvec*nx */,
+                      double *dX /* B*nvec*(N+1)*nx or NULL */, double *dU /* B*nvec*N*nu or NULL */);
+int cddp_hip_plan_vjp(cddp_hip_handle *h, int flags, int nvec,
+                      const double *gX /* B*nvec*(N+1)*nx or NULL = zeros */,
+                      const double *gU /* B*nvec*N*nu or NULL = zeros */,
+                      double *gx0 /* B*nvec*nx */);
+
 /* ---- multi-GPU: the single collective of the path --------------------------------------
  * One process (or host thread) per GPU, each with its own handle over a contiguous block of the global batch; nothing
  * is exchanged during a solve.  After it, ONE RCCL all-gather collects every trajectory's 16-byte record.
