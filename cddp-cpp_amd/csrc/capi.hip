@@ -5,6 +5,7 @@
 #include <chrono>
 #include <cmath>
 #include <cstdarg>
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -16,6 +17,7 @@
 #include "plant.hpp"
 #include "io_kernels.hpp"
 #include "sens_kernels.hpp"
+#include "score_kernels.hpp"
 
 // 1 when a[0] > a[1] > ... > a[n - 1] (NaN-free): the ladders cddp_hip_build_alphas makes; DevBuf::ladder_sorted
 static int ladder_strictly_decreasing(const double *a, int n) {
@@ -1742,6 +1744,8 @@ struct cddp_hip_handle {
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
   void *d_send = nullptr;              // send buffer of cddp_hip_allgather_results (shard_capacity records)
   int send_cap = 0;
+  double *d_score = nullptr; size_t score_cap = 0;   // cddp_hip_score_rollouts / cddp_hip_seed_best: staging of host arrays, grown on demand
+  int32_t *d_winner = nullptr;                       // cddp_hip_seed_best: winner[B], the gather index of the seed
 };
 
 namespace {
@@ -1860,6 +1864,8 @@ int cddp_hip_destroy(cddp_hip_handle *h) {
   if (h->ev_fork) { hipEventDestroy(h->ev_fork); hipEventDestroy(h->ev_join); }
   for (int k = 0; k < 2; ++k) if (h->ev_pp[k]) hipEventDestroy(h->ev_pp[k]);
   if (h->d_send) hipFree(h->d_send);
+  if (h->d_score) hipFree(h->d_score);
+  if (h->d_winner) hipFree(h->d_winner);
   delete h;
   return 0;
 }
@@ -2436,6 +2442,13 @@ int plant_fits(const char *who, cddp_hip_handle *h, cddp_hip_plant *p) {
   return 0;
 }
 
+// a feedback rollout reads the live slot and the gain stack: refused before the handle has either
+int plan_tracked(const char *who, const cddp_hip_handle *h) {
+  for (const Inner *q : h->g)
+    if (!q->has_plan) return fail(-1, "%s needs a solved handle: there is no plan and no gain stack to track before cddp_hip_solve (or cddp_hip_initialize and cddp_hip_backward)", who);
+  return 0;
+}
+
 // disturbances: one synchronous upload into the plant's buffer (grown on demand) before anything of the call is enqueued
 int plant_upload_W(cddp_hip_plant *p, const double *W, size_t n) {
   if (p->W_cap < n) {
@@ -2566,8 +2579,7 @@ int cddp_hip_mpc_run_plant(cddp_hip_handle *h, cddp_hip_plant *plant, int steps,
 
 int cddp_hip_track_plan(cddp_hip_handle *h, cddp_hip_plant *plant, const double *x0, const double *W, double *X_out, double *U_out) {
   { int rc = plant_fits("cddp_hip_track_plan", h, plant); if (rc) return rc; }
-  for (Inner *q : h->g)
-    if (!q->has_plan) return fail(-1, "cddp_hip_track_plan needs a solved handle: there is no plan and no gain stack to track before cddp_hip_solve (or cddp_hip_initialize and cddp_hip_backward)");
+  { int rc = plan_tracked("cddp_hip_track_plan", h); if (rc) return rc; }
   HIPCHK(hipSetDevice(h->device));
   const int N = h->N, nx = h->nx, nu = h->nu, Bp = plant->pd.Bp, NBlog = Bp / 64;
   const size_t nXl = (size_t)(N + 1) * nx * Bp, nUl = (size_t)N * nu * Bp;
@@ -2593,6 +2605,132 @@ int cddp_hip_track_plan(cddp_hip_handle *h, cddp_hip_plant *plant, const double 
   std::vector<double> buf;
   if (X_out) { buf.resize(nXl); HIPCHK(hipMemcpy(buf.data(), plant->d_trX, nXl * sizeof(double), hipMemcpyDeviceToHost)); from_soa(buf.data(), X_out, h->B, Bp, N + 1, nx); }
   if (U_out) { buf.resize(nUl); HIPCHK(hipMemcpy(buf.data(), plant->d_trU, nUl * sizeof(double), hipMemcpyDeviceToHost)); from_soa(buf.data(), U_out, h->B, Bp, N, nu); }
+  return join_to_user(h);
+}
+
+// ---- scoring candidate control sequences (inst_score.hip) and seeding from the best of them ----
+// the handle's staging buffer of the host-pointer forms: at least n doubles
+static int score_scratch(cddp_hip_handle *h, size_t n) {
+  if (h->score_cap >= n) return 0;
+  if (h->d_score) hipFree(h->d_score);
+  h->d_score = nullptr; h->score_cap = 0;
+  HIPCHK(hipMalloc((void **)&h->d_score, n * sizeof(double)));
+  h->score_cap = n;
+  return 0;
+}
+
+int cddp_hip_score_rollouts(cddp_hip_handle *h, cddp_hip_plant *plant, int flags, int ncand, const double *x0, const double *U,
+                            double *cost, double *viol, double *X_out, double *U_out) {
+  static const char *const me = "cddp_hip_score_rollouts";
+  const int known = CDDP_HIP_SCORE_DEVICE | CDDP_HIP_SCORE_FEEDBACK | CDDP_HIP_SCORE_X0_PER_CANDIDATE;
+  if (!h) return fail(-1, "%s: null handle", me);
+  if (flags & ~known) return fail(-2, "%s: unknown flag bits 0x%x", me, (unsigned)(flags & ~known));
+  if (ncand < 1) return fail(-2, "%s: ncand = %d, at least one candidate is needed", me, ncand);
+  if (!cost) return fail(-1, "%s: null cost pointer", me);
+  const bool dev = (flags & CDDP_HIP_SCORE_DEVICE) != 0, fb = (flags & CDDP_HIP_SCORE_FEEDBACK) != 0, xpc = (flags & CDDP_HIP_SCORE_X0_PER_CANDIDATE) != 0;
+  if (!U && !fb) return fail(-1, "%s: U is NULL without CDDP_HIP_SCORE_FEEDBACK: there is nothing to roll out", me);
+  if (xpc && !x0) return fail(-1, "%s: CDDP_HIP_SCORE_X0_PER_CANDIDATE with a NULL x0", me);
+  if (fb) { int rc = plan_tracked(me, h); if (rc) return rc; }
+  if (!x0) for (const Inner *q : h->g) if (!q->has_plan) return fail(-1, "%s: x0 is NULL and the handle has no plan whose row 0 could stand in", me);
+  if (plant) { int rc = plant_fits(me, h, plant); if (rc) return rc; }
+  const size_t B = (size_t)h->B, S = (size_t)ncand, nx = (size_t)h->nx, nu = (size_t)h->nu, N = (size_t)h->N;
+  if (((size_t)((h->B + 63) / 64 * 64) * S + 63) / 64 > 0x7fffffffull) return fail(-2, "%s: batch * ncand = %zu exceeds what one launch holds", me, B * S);
+  HIPCHK(hipSetDevice(h->device));
+  const size_t n0 = xpc ? S * nx : nx, nU = S * N * nu, nX = S * (N + 1) * nx;   // per trajectory
+  const double *x0d = x0, *Ud = U;
+  double *costd = cost, *viold = viol, *Xd = X_out, *Uod = U_out;
+  if (dev) {
+    if (x0) { int rc = io_check_pointer(h, x0, B * n0 * sizeof(double), me, "x0"); if (rc) return rc; }
+    if (U) { int rc = io_check_pointer(h, U, B * nU * sizeof(double), me, "U"); if (rc) return rc; }
+    { int rc = io_check_pointer(h, cost, B * S * sizeof(double), me, "cost"); if (rc) return rc; }
+    if (viol) { int rc = io_check_pointer(h, viol, B * S * sizeof(double), me, "viol"); if (rc) return rc; }
+    if (X_out) { int rc = io_check_pointer(h, X_out, B * nX * sizeof(double), me, "X_out"); if (rc) return rc; }
+    if (U_out) { int rc = io_check_pointer(h, U_out, B * nU * sizeof(double), me, "U_out"); if (rc) return rc; }
+  } else {
+    const size_t total = B * ((x0 ? n0 : 0) + (U ? nU : 0) + S + (viol ? S : 0) + (X_out ? nX : 0) + (U_out ? nU : 0));
+    { int rc = score_scratch(h, total); if (rc) return rc; }
+    double *top = h->d_score;
+    if (x0) { HIPCHK(hipMemcpy(top, x0, B * n0 * sizeof(double), hipMemcpyHostToDevice)); x0d = top; top += B * n0; }
+    if (U) { HIPCHK(hipMemcpy(top, U, B * nU * sizeof(double), hipMemcpyHostToDevice)); Ud = top; top += B * nU; }
+    costd = top; top += B * S;
+    if (viol) { viold = top; top += B * S; }
+    if (X_out) { Xd = top; top += B * nX; }
+    if (U_out) { Uod = top; top += B * nU; }
+  }
+  { int rc = fork_from_user(h); if (rc) return rc; }
+  for (size_t gi = 0; gi < h->g.size(); ++gi) {
+    const Inner *q = h->g[gi];
+    const size_t b0 = (size_t)h->b0[gi];
+    PlantDev pd;
+    if (plant) pd = plant->pd;
+    else {   // the handle's own model as a plant: one step of dt, no box, the derived block of the ProblemDev on the device
+      std::memset(&pd, 0, sizeof(pd));
+      pd.model = q->P.model; pd.integrator = q->P.integrator; pd.substeps = 1; pd.nx = q->P.nx; pd.nu = q->P.nu; pd.Bp = q->d.Bp; pd.h = q->P.dt;
+      pd.params = (const double *)((const char *)q->dP + offsetof(ProblemDev, mp));
+    }
+    ScoreArgs a;
+    a.S = ncand; a.b0 = (int)b0; a.feedback = fb ? 1 : 0; a.x0_per_cand = xpc ? 1 : 0;
+    a.x0 = x0d ? x0d + b0 * n0 : nullptr; a.U = Ud ? Ud + b0 * nU : nullptr;
+    a.cost = costd + b0 * S; a.viol = viold ? viold + b0 * S : nullptr;
+    a.X_out = Xd ? Xd + b0 * nX : nullptr; a.U_out = Uod ? Uod + b0 * nU : nullptr;
+    const hipError_t e = score_launch(pd, q->d, a, q->stream);
+    if (e == hipErrorInvalidValue) return fail(-3, "%s: the library has no scoring kernel for model id %d with nx = %d, nu = %d", me, pd.model, pd.nx, pd.nu);
+    HIPCHK(e);
+  }
+  if (dev) return io_finish(h);
+  HIPCHK(hipGetLastError());
+  for (Inner *q : h->g) HIPCHK(hipStreamSynchronize(q->stream));
+  HIPCHK(hipMemcpy(cost, costd, B * S * sizeof(double), hipMemcpyDeviceToHost));
+  if (viol) HIPCHK(hipMemcpy(viol, viold, B * S * sizeof(double), hipMemcpyDeviceToHost));
+  if (X_out) HIPCHK(hipMemcpy(X_out, Xd, B * nX * sizeof(double), hipMemcpyDeviceToHost));
+  if (U_out) HIPCHK(hipMemcpy(U_out, Uod, B * nU * sizeof(double), hipMemcpyDeviceToHost));
+  return join_to_user(h);
+}
+
+int cddp_hip_seed_best(cddp_hip_handle *h, int flags, int ncand, const double *x0, const double *U, const double *cost, const double *viol,
+                       double viol_tol, int32_t *winner) {
+  static const char *const me = "cddp_hip_seed_best";
+  if (!h) return fail(-1, "%s: null handle", me);
+  if (flags & ~CDDP_HIP_SCORE_DEVICE) return fail(-2, "%s: unknown flag bits 0x%x (CDDP_HIP_SCORE_DEVICE is the only flag)", me, (unsigned)(flags & ~CDDP_HIP_SCORE_DEVICE));
+  if (ncand < 1) return fail(-2, "%s: ncand = %d, at least one candidate is needed", me, ncand);
+  if (!U) return fail(-1, "%s: null U pointer", me);
+  if (!cost) return fail(-1, "%s: null cost pointer", me);
+  if (!x0) for (const Inner *q : h->g) if (!q->have_initial) return fail(-1, "%s: x0 is NULL and the handle has no initial state to keep (cddp_hip_set_initial)", me);
+  HIPCHK(hipSetDevice(h->device));
+  const bool dev = (flags & CDDP_HIP_SCORE_DEVICE) != 0;
+  const size_t B = (size_t)h->B, S = (size_t)ncand, nx = (size_t)h->nx, nU = (size_t)h->N * h->nu;
+  const double *x0d = x0, *Ud = U, *costd = cost, *viold = viol;
+  if (dev) {
+    if (x0) { int rc = io_check_pointer(h, x0, B * nx * sizeof(double), me, "x0"); if (rc) return rc; }
+    { int rc = io_check_pointer(h, U, B * S * nU * sizeof(double), me, "U"); if (rc) return rc; }
+    { int rc = io_check_pointer(h, cost, B * S * sizeof(double), me, "cost"); if (rc) return rc; }
+    if (viol) { int rc = io_check_pointer(h, viol, B * S * sizeof(double), me, "viol"); if (rc) return rc; }
+    if (winner) { int rc = io_check_pointer(h, winner, B * sizeof(int32_t), me, "winner"); if (rc) return rc; }
+  } else {
+    { int rc = score_scratch(h, B * ((x0 ? nx : 0) + S * nU + S + (viol ? S : 0))); if (rc) return rc; }
+    double *top = h->d_score;
+    if (x0) { HIPCHK(hipMemcpy(top, x0, B * nx * sizeof(double), hipMemcpyHostToDevice)); x0d = top; top += B * nx; }
+    HIPCHK(hipMemcpy(top, U, B * S * nU * sizeof(double), hipMemcpyHostToDevice)); Ud = top; top += B * S * nU;
+    HIPCHK(hipMemcpy(top, cost, B * S * sizeof(double), hipMemcpyHostToDevice)); costd = top; top += B * S;
+    if (viol) { HIPCHK(hipMemcpy(top, viol, B * S * sizeof(double), hipMemcpyHostToDevice)); viold = top; top += B * S; }
+  }
+  if (!h->d_winner) HIPCHK(hipMalloc((void **)&h->d_winner, B * sizeof(int32_t)));
+  { int rc = fork_from_user(h); if (rc) return rc; }
+  for (size_t gi = 0; gi < h->g.size(); ++gi) {
+    Inner *q = h->g[gi];
+    const size_t b0 = (size_t)h->b0[gi];
+    int32_t *w = h->d_winner + b0;
+    score_select_launch(q->d.B, ncand, costd + b0 * S, viold ? viold + b0 * S : nullptr, viol_tol, w, q->stream);
+    // the seed exactly as cddp_hip_set_initial_device(x0, U[:, winner], NULL) tiles it; only the gather index is new
+    if (x0d) io_tile(nullptr, x0d + b0 * nx, q->d.B, q->d.NB, h->N + 1, h->nx, q->d_Xinit, q->stream);
+    io_tile(Ud + b0 * S * nU, nullptr, q->d.B, q->d.NB, h->N, h->nu, q->d_Uinit, q->stream, w, ncand);
+    if (winner && dev) HIPCHK(hipMemcpyAsync(winner + b0, w, (size_t)q->d.B * sizeof(int32_t), hipMemcpyDeviceToDevice, q->stream));
+    q->have_initial = true; q->initialized = false; q->initial_dirty = true;   // as cddp_hip_set_initial_device leaves them
+  }
+  if (dev) return io_finish(h);
+  HIPCHK(hipGetLastError());
+  for (Inner *q : h->g) HIPCHK(hipStreamSynchronize(q->stream));
+  if (winner) HIPCHK(hipMemcpy(winner, h->d_winner, B * sizeof(int32_t), hipMemcpyDeviceToHost));
   return join_to_user(h);
 }
 

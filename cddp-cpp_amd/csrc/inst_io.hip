@@ -27,6 +27,13 @@ constexpr int kIoPitch = kIoCols + 1;    // LDS row pitch in doubles, odd (see a
 constexpr int kIoThreads = 256;          // a multiple of 64: a thread's lane on the stack side is threadIdx.x & 63 throughout
 constexpr int kIoMaxGridY = 65535;
 
+// the batch-major record trajectory b of a tile kernel reads: its own, or the selected one of its S candidates
+__device__ __forceinline__ size_t io_record(const int32_t *sel, int S, int b) {
+  if (!sel) return (size_t)b;
+  const int w = sel[b];
+  return (size_t)b * (size_t)S + (size_t)(w < 0 ? 0 : w);
+}
+
 template <int LAYOUT>
 __global__ __launch_bounds__(kIoThreads) void k_io_untile(const double *__restrict__ src, const int *__restrict__ cur, size_t plane, int B, int NB, int T, int E,
                                                           int tile0, double *__restrict__ out) {
@@ -53,15 +60,16 @@ __global__ __launch_bounds__(kIoThreads) void k_io_untile(const double *__restri
   }
 }
 
+// sel (cddp_hip_seed_best): trajectory b reads record b * S + max(sel[b], 0) of src instead of record b -- the only difference of the gather
 __global__ __launch_bounds__(kIoThreads) void k_io_tile(const double *__restrict__ src, const double *__restrict__ row, int B, int NB, int T, int E, int tile0,
-                                                        double *__restrict__ dst) {
+                                                        double *__restrict__ dst, const int32_t *__restrict__ sel, int S) {
   __shared__ double img[64 * kIoPitch];
   const int tile = tile0 + (int)blockIdx.y, b0 = tile * 64;
   const int TE = T * E, c0 = (int)blockIdx.x * kIoCols, nc = min(kIoCols, TE - c0), n = nc * 64;
   if (src) {
     for (int i = threadIdx.x; i < n; i += kIoThreads) {
       const int l = i / nc, col = i - l * nc, b = b0 + l;
-      if (b < B) img[l * kIoPitch + col] = src[(size_t)b * (size_t)TE + (size_t)(c0 + col)];
+      if (b < B) img[l * kIoPitch + col] = src[io_record(sel, S, b) * (size_t)TE + (size_t)(c0 + col)];
     }
     __syncthreads();
   }
@@ -88,13 +96,13 @@ __global__ __launch_bounds__(64) void k_io_untile_naive(const double *__restrict
 }
 
 __global__ __launch_bounds__(64) void k_io_tile_naive(const double *__restrict__ src, const double *__restrict__ row, int B, int NB, int T, int E, int tile0,
-                                                      double *__restrict__ dst) {
+                                                      double *__restrict__ dst, const int32_t *__restrict__ sel, int S) {
   const int b = (tile0 + (int)blockIdx.y) * 64 + (int)threadIdx.x, t = (int)blockIdx.x;
   for (int e = 0; e < E; ++e) {
     double v = 0.0;
     if (b < B) {
       if (row && (t == 0 || !src)) v = row[(size_t)b * (size_t)E + (size_t)e];
-      else if (src) v = src[cddp_io::batch_major(b, T, t, E, e)];
+      else if (src) v = src[io_record(sel, S, b) * (size_t)T * (size_t)E + (size_t)t * (size_t)E + (size_t)e];
     }
     dst[cddp_io::tiled(t, NB, E, e, b)] = v;
   }
@@ -129,14 +137,14 @@ void io_untile(int layout, const double *src, const int *cur, size_t plane, int 
   else untile_launch<cddp_io::kTiled>(naive, src, cur, plane, B, NB, T, E, out, stream);
 }
 
-void io_tile(const double *src, const double *row, int B, int NB, int T, int E, double *dst, hipStream_t stream) {
+void io_tile(const double *src, const double *row, int B, int NB, int T, int E, double *dst, hipStream_t stream, const int32_t *sel, int S) {
   if (NB <= 0 || T <= 0 || E <= 0) return;
   const bool naive = io_map_naive();
   const int TE = T * E;
   for (int tile0 = 0; tile0 < NB; tile0 += kIoMaxGridY) {   // every tile of the padded batch: padding lanes are written too
     const int ny = std::min(kIoMaxGridY, NB - tile0);
-    if (naive) hipLaunchKernelGGL(k_io_tile_naive, dim3(T, ny), dim3(64), 0, stream, src, row, B, NB, T, E, tile0, dst);
-    else hipLaunchKernelGGL(k_io_tile, dim3((TE + kIoCols - 1) / kIoCols, ny), dim3(kIoThreads), 0, stream, src, row, B, NB, T, E, tile0, dst);
+    if (naive) hipLaunchKernelGGL(k_io_tile_naive, dim3(T, ny), dim3(64), 0, stream, src, row, B, NB, T, E, tile0, dst, sel, S);
+    else hipLaunchKernelGGL(k_io_tile, dim3((TE + kIoCols - 1) / kIoCols, ny), dim3(kIoThreads), 0, stream, src, row, B, NB, T, E, tile0, dst, sel, S);
   }
 }
 

@@ -11,6 +11,7 @@
 // plant keeps the few it names -- the unrolled copy of the others is dead code).
 #include "plant.hpp"
 #include "dev_models.hpp"
+#include "plant_models.hpp"
 
 namespace cddp_dev {
 namespace {
@@ -126,16 +127,6 @@ __global__ __launch_bounds__(64) void k_track_plan(PlantDev pd, DevBuf d, int b0
     for (int i = 0; i < NX; ++i) Xlog[(((size_t)(t + 1) * LNB + ltile) * NX + i) * 64 + lane] = x[i];
   }
 }
-
-typedef LTIModel<1, 1> Lti11;
-typedef LTIModel<2, 1> Lti21;
-
-// every model struct: Y(Model).  The two LTI shapes are the ones inst_lti.hip builds solver kernels for.
-#define PLANT_MODEL_LIST(Y) \
-  Y(PendulumModel) Y(CartPoleModel) Y(UnicycleModel) Y(QuadrotorModel) Y(ManipulatorModel) Y(Quad12Model) Y(Manip7Model) Y(BicycleModel) \
-  Y(CarModel) Y(HCWModel) Y(EulerAttitudeModel) Y(QuaternionAttitudeModel) Y(MrpAttitudeModel) Y(SpacecraftTwobodyModel) \
-  Y(SpacecraftLanding2DModel) Y(DubinsCarModel) Y(DreyfusRocketModel) Y(AcrobotModel) Y(Usv3DofModel) Y(ForkliftModel) \
-  Y(QuadrotorRateModel) Y(SpacecraftLinearFuelModel) Y(SpacecraftNonlinearModel) Y(Lti11) Y(Lti21)
 
 template <class M> bool is_model(int model, int nx, int nu) { return model == M::ID && nx == M::NX && nu == M::NU; }
 

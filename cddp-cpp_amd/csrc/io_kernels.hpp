@@ -19,7 +19,8 @@ void io_untile(int layout, const double *src, const int *cur, size_t plane, int 
 // batch-major -> wave-tiled seed buffer (d_Xinit, d_Uinit), all NB * 64 lanes of every row: padding lanes 0.0; a trajectory's row t is
 // row[b][e] when `row` is given and (t == 0 or src == NULL), else src[b][t][e], else 0.0.
 //   X: io_tile(X0, x0, ...)  -- row 0 is x0 (cddp_core.cpp:294), without X0 every row is;   U: io_tile(U0, NULL, ...) -- without U0 zeros
-void io_tile(const double *src, const double *row, int B, int NB, int T, int E, double *dst, hipStream_t stream);
+// sel / S (cddp_hip_seed_best): src is [B][S][T][E] and trajectory b takes record max(sel[b], 0) of its S (sel: B int32 on the device)
+void io_tile(const double *src, const double *row, int B, int NB, int T, int E, double *dst, hipStream_t stream, const int32_t *sel = nullptr, int S = 1);
 
 // the columns of cddp_hip_result in struct order: cols[b][10] doubles, icols[b][4] int32
 struct IoResultSrc { const double *d[10]; const int *i[4]; };

@@ -885,6 +885,20 @@ class HipBatchSolver : public ISolverAlgorithm {
     if (!h_) throw std::runtime_error("cddp_hip: planVjp needs a resident batch (the plug-in route has no resident handle)");
     check(cddp_hip_plan_vjp(h_, flags, nvec, gX, gU, gx0));
   }
+  // NEW: what ncand candidate control sequences per trajectory are worth, in one launch (cddp_hip_score_rollouts), and the seed taken from
+  // the best of them (cddp_hip_seed_best).  Arrays are [batch][ncand][t][e]; flags: CDDP_HIP_SCORE_DEVICE (device pointers of the solver's
+  // device), CDDP_HIP_SCORE_FEEDBACK (u = U + K_t (x - X_t) around the live plan, U may then be nullptr), CDDP_HIP_SCORE_X0_PER_CANDIDATE.
+  // plant: nullptr = the batch's own model.  viol, X_out, U_out may be nullptr.  seedBest: winner[batch] or nullptr; resolveBatch() solves.
+  void scoreRollouts(Plant *plant, int flags, int ncand, const double *x0 /* batch*nx | batch*ncand*nx | nullptr */, const double *U /* batch*ncand*N*nu */,
+                     double *cost /* batch*ncand */, double *viol = nullptr, double *X_out = nullptr, double *U_out = nullptr) {
+    if (!h_) throw std::runtime_error("cddp_hip: scoreRollouts needs a resident batch (the plug-in route has no resident handle)");
+    check(cddp_hip_score_rollouts(h_, plant ? plant->get() : nullptr, flags, ncand, x0, U, cost, viol, X_out, U_out));
+  }
+  void seedBest(int flags, int ncand, const double *x0 /* batch*nx | nullptr */, const double *U, const double *cost, const double *viol, double viol_tol,
+                int32_t *winner = nullptr) {
+    if (!h_) throw std::runtime_error("cddp_hip: seedBest needs a resident batch (the plug-in route has no resident handle)");
+    check(cddp_hip_seed_best(h_, flags, ncand, x0, U, cost, viol, viol_tol, winner));
+  }
   // NEW: solve the resident batch again from the seed it holds now (setInitialDevice, mpcAdvance) -- solveBatch() without creating and uploading
   std::vector<CDDPSolution> resolveBatch(CDDP &ctx) {
     if (!h_) throw std::runtime_error("cddp_hip: resolveBatch needs a resident batch (the plug-in route has no resident handle)");

@@ -167,6 +167,10 @@ MPC_KEEP_PLAN, MPC_SHIFT_EXISTING, MPC_SHIFT_PROVIDED = 0, 1, 2
 MPC_SHIFT_DUALS, MPC_X_DEVICE = 1, 2
 # cddp_hip_plan_jvp / cddp_hip_plan_vjp (include/cddp_hip.h, "linear response of a solved plan to its initial state")
 SENS_DEVICE = 1
+# cddp_hip_score_rollouts / cddp_hip_seed_best (include/cddp_hip.h, "scoring candidate control sequences and seeding from the best")
+SCORE_DEVICE = 1
+SCORE_FEEDBACK = 2
+SCORE_X0_PER_CANDIDATE = 4
 # cddp_hip_get_field_device / cddp_hip_field_shape (include/cddp_hip.h, "device-resident inputs and outputs"): enum cddp_hip_field
 FIELD_NAMES = ("X", "U", "K", "KFF", "VX", "VXX", "A", "B", "S", "Y", "G", "LAMBDA")
 FIELD_IDS = {name: i for i, name in enumerate(FIELD_NAMES)}
@@ -824,6 +828,8 @@ DEVICE_IO_ARGTYPES = {
     # (host or device addresses, by the flag: plain pointer values)
     "cddp_hip_plan_jvp": [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
     "cddp_hip_plan_vjp": [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
+    "cddp_hip_score_rollouts": [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    "cddp_hip_seed_best": [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p],
 }
 
 EXPORTED_SYMBOLS = [
@@ -841,6 +847,7 @@ EXPORTED_SYMBOLS = [
     "cddp_hip_plant_create", "cddp_hip_plant_destroy", "cddp_hip_plant_step", "cddp_hip_mpc_run_plant", "cddp_hip_track_plan",
     "cddp_hip_field_shape", "cddp_hip_get_field_device", "cddp_hip_get_results_device", "cddp_hip_set_initial_device", "cddp_hip_get_live_slots",
     "cddp_hip_plan_jvp", "cddp_hip_plan_vjp",
+    "cddp_hip_score_rollouts", "cddp_hip_seed_best",
 ]
 
 
@@ -1287,6 +1294,114 @@ class HipBatchSolver:
         eye = torch.eye(nx, dtype=torch.float64, device=self._torch_device()).expand(self.B, nx, nx).contiguous()
         dX, dU = self.plan_jvp(eye)
         return dX.permute(0, 2, 3, 1).contiguous(), dU.permute(0, 2, 3, 1).contiguous()
+
+    # ---- scoring candidate control sequences and seeding from the best (cddp_hip_score_rollouts / cddp_hip_seed_best): numpy arrays take
+    # the host path, torch.float64 tensors on the handle's device the device path; every argument of a call is of one kind
+    def _score_arg(self, who, name, a, shapes, device):
+        """One array argument whose shape must be one of `shapes`: a contiguous float64 numpy array, or the checked device tensor."""
+        if hasattr(a, "data_ptr") and not isinstance(a, np.ndarray):
+            if not device:
+                raise ValueError("%s: %s is a device tensor, the other arguments are numpy arrays" % (who, name))
+            if tuple(a.shape) not in shapes:
+                raise ValueError("%s: %s: shape %s is expected, got %s" % (who, name, " or ".join(str(x) for x in shapes), tuple(a.shape)))
+            return self._device_tensor(name, a, tuple(a.shape))
+        if device:
+            raise ValueError("%s: %s is not a device tensor, the other arguments are" % (who, name))
+        if isinstance(a, np.ndarray) and a.dtype != np.float64:
+            raise ValueError("%s: %s: dtype float64 is expected, got %s" % (who, name, a.dtype))
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        if tuple(a.shape) not in shapes:
+            raise ValueError("%s: %s: shape %s is expected, got %s" % (who, name, " or ".join(str(x) for x in shapes), tuple(a.shape)))
+        return a
+
+    @staticmethod
+    def _addr(a):
+        return None if a is None else (a.ctypes.data if isinstance(a, np.ndarray) else a.data_ptr())
+
+    def score_rollouts(self, U, x0=None, plant=None, feedback=False, want=("cost", "viol"), ncand=None):
+        """What S candidate control sequences per trajectory are worth, in one launch (cddp_hip_score_rollouts): U (B, S, N, nu), or None
+        with feedback=True (the plan's own U); x0 (B, nx), (B, S, nx) or None (row 0 of the live plan); plant: a DevicePlant or None (the
+        handle's own model).  feedback=True applies u_t = U_t + K_t (x_t - X_t) around the live plan.  numpy arrays, or torch.float64
+        tensors on the handle's device (device path, device tensors back).  want: any of "cost" (B, S), "viol" (B, S), "X" (B, S, N + 1,
+        nx), "U" (B, S, N, nu: the controls as applied); returns a dict.  With U None the number of candidates is x0's S, or ncand, or 1.
+        The handle's solver state is not modified."""
+        who = "score_rollouts"
+        want = tuple(want)
+        if any(w not in ("cost", "viol", "X", "U") for w in want):
+            raise ValueError("%s: want: a subset of ('cost', 'viol', 'X', 'U') is expected, got %r" % (who, want))
+        B, N, nx, nu = self.B, self.p.N, self.p.nx, self.p.nu
+        if U is None and not feedback:
+            raise ValueError("%s: U is None without feedback=True: there is nothing to roll out" % who)
+        given = [a for a in (U, x0) if a is not None]
+        device = any(hasattr(a, "data_ptr") and not isinstance(a, np.ndarray) for a in given)
+        S = None
+        if U is not None:
+            if len(tuple(U.shape) if hasattr(U, "shape") else np.shape(U)) != 4:
+                raise ValueError("%s: U: shape (%d, S, %d, %d) is expected, got %s" % (who, B, N, nu, tuple(np.shape(U))))
+            S = int(np.shape(U)[1])
+            if S < 1:
+                raise ValueError("%s: U: at least one candidate is expected" % who)
+            U = self._score_arg(who, "U", U, [(B, S, N, nu)], device)
+        flags = SCORE_FEEDBACK if feedback else 0
+        if x0 is not None:
+            shp = tuple(np.shape(x0))
+            if S is None:
+                S = int(shp[1]) if len(shp) == 3 else (int(ncand) if ncand is not None else 1)
+            x0 = self._score_arg(who, "x0", x0, [(B, nx), (B, S, nx)], device)
+            if len(shp) == 3:
+                flags |= SCORE_X0_PER_CANDIDATE
+        if S is None:
+            S = int(ncand) if ncand is not None else 1
+        if ncand is not None and int(ncand) != S:
+            raise ValueError("%s: ncand = %d, the arrays hold %d candidates" % (who, int(ncand), S))
+        if S < 1:
+            raise ValueError("%s: at least one candidate is expected" % who)
+        shapes = {"cost": (B, S), "viol": (B, S), "X": (B, S, N + 1, nx), "U": (B, S, N, nu)}
+        out = {}
+        if device:
+            import torch
+            dev = self._torch_device()
+            for w in ("cost",) + tuple(w for w in want if w != "cost"):
+                out[w] = torch.empty(shapes[w], dtype=torch.float64, device=dev)
+            self._order_device_io()
+            flags |= SCORE_DEVICE
+        else:
+            for w in ("cost",) + tuple(w for w in want if w != "cost"):
+                out[w] = np.zeros(shapes[w])
+        self._check(self.lib.cddp_hip_score_rollouts(self.h, plant.h if plant is not None else None, flags, S, self._addr(x0), self._addr(U),
+                                                     self._addr(out["cost"]), self._addr(out.get("viol")), self._addr(out.get("X")), self._addr(out.get("U"))))
+        return {w: out[w] for w in want}
+
+    def seed_best(self, U, cost, viol=None, x0=None, viol_tol=0.0):
+        """Seed the handle from the best of S candidates per trajectory (cddp_hip_seed_best): the admissible (finite, viol <= viol_tol)
+        candidate of lowest cost, else the finite one of lowest viol then cost, ties to the lowest index, else candidate 0 with winner -1.
+        U (B, S, N, nu), cost (B, S), viol (B, S) or None (all 0), x0 (B, nx) or None (keep the handle's x0); numpy arrays or
+        torch.float64 device tensors, all of one kind.  Returns winner (B,) int32 of that kind.  The handle is left exactly as
+        set_initial_device(x0, U[arange(B), winner]) leaves it."""
+        who = "seed_best"
+        B, N, nx, nu = self.B, self.p.N, self.p.nx, self.p.nu
+        if U is None or cost is None:
+            raise ValueError("%s: U and cost are required" % who)
+        device = hasattr(U, "data_ptr") and not isinstance(U, np.ndarray)
+        if len(tuple(np.shape(U))) != 4 or int(np.shape(U)[1]) < 1:
+            raise ValueError("%s: U: shape (%d, S, %d, %d) with S >= 1 is expected, got %s" % (who, B, N, nu, tuple(np.shape(U))))
+        S = int(np.shape(U)[1])
+        U = self._score_arg(who, "U", U, [(B, S, N, nu)], device)
+        cost = self._score_arg(who, "cost", cost, [(B, S)], device)
+        if viol is not None:
+            viol = self._score_arg(who, "viol", viol, [(B, S)], device)
+        if x0 is not None:
+            x0 = self._score_arg(who, "x0", x0, [(B, nx)], device)
+        viol_tol = float(viol_tol)
+        if device:
+            import torch
+            winner = torch.empty((B,), dtype=torch.int32, device=self._torch_device())
+            self._order_device_io()
+        else:
+            winner = np.zeros(B, dtype=np.int32)
+        self._check(self.lib.cddp_hip_seed_best(self.h, SCORE_DEVICE if device else 0, S, self._addr(x0), self._addr(U), self._addr(cost),
+                                                self._addr(viol), viol_tol, self._addr(winner)))
+        return winner
 
 
 class DevicePlant:

@@ -1187,6 +1187,49 @@ class CDDP:                         # cddp_core.hpp:214-423 / bind_solver.cpp:57
         out["solve_time_ms"] = float(st.solve_ms)
         return out
 
+    def solve_batch_sampled(self, x0s, U_candidates, solver_type=SolverType.IPDDP, viol_tol=0.0, want=("X", "U")):
+        """NEW (no reference counterpart): solve_batch_device started from the best of S candidate control sequences per trajectory
+        (cddp_hip_score_rollouts, cddp_hip_seed_best): every candidate is rolled out on the device in one launch, the admissible one
+        (largest constraint violation <= viol_tol) of lowest objective seeds its trajectory, and the batch is solved from there.  x0s:
+        (B, nx), U_candidates: (B, S, N, nu) -- torch.float64, contiguous, on cuda:0.  The candidates are the caller's: nothing is drawn
+        or blended here.  Returns what solve_batch_device returns, plus "winner" ((B,) int32, -1 where no candidate was finite and
+        candidate 0 was taken) and "seed_cost" ((B,), the winner's objective before the solve)."""
+        import torch
+        api = _api()
+        name = solver_type.value if isinstance(solver_type, SolverType) else str(solver_type)
+        want = tuple(want)
+        unknown = [w for w in want if w not in api.FIELD_IDS]
+        if unknown:
+            raise ValueError("want: unknown fields %s (known: %s)" % (unknown, ", ".join(api.FIELD_NAMES)))
+        if self._sys is None:
+            raise RuntimeError("Dynamical system must be set before solving.")
+        kind = self._resident_kind(name)
+        if kind is None:
+            raise NotImplementedError("solve_batch_sampled needs a problem of the resident route (built-in plant, objective and constraints): "
+                                      "solver '%s' with this problem runs on the plug-in route, which has no resident handle" % name)
+        if not isinstance(x0s, torch.Tensor) or x0s.dim() != 2:
+            raise ValueError("x0s: a (B, nx) torch tensor is expected")
+        if not isinstance(U_candidates, torch.Tensor) or U_candidates.dim() != 4:
+            raise ValueError("U_candidates: a (B, S, N, nu) torch tensor is expected")
+        B = int(x0s.shape[0])
+        if B <= 0:
+            raise ValueError("x0s: an empty batch")
+        p = self._problem(kind)
+        hs = api.HipBatchSolver(p, B)
+        try:
+            sc = hs.score_rollouts(U_candidates, x0=x0s)      # (shape, dtype, contiguity and device are checked there: ValueError)
+            winner = hs.seed_best(U_candidates, sc["cost"], sc["viol"], x0=x0s, viol_tol=viol_tol)
+            st = hs.solve()
+            out = {w: hs.field_device(w) for w in want}
+            res = hs.results_device()
+        finally:
+            hs.close()
+        out["results"] = {k: v for k, v in res.items() if k not in ("cols", "icols")}
+        out["solve_time_ms"] = float(st.solve_ms)
+        out["winner"] = winner
+        out["seed_cost"] = sc["cost"].gather(1, winner.clamp(min=0).long().unsqueeze(1)).squeeze(1)
+        return out
+
     def solve_batch_diff(self, x0s, U0=None, X0=None, solver_type=SolverType.IPDDP, refresh=False):
         """NEW (no reference counterpart): solve_batch_device as a differentiable function of x0s (cddp_hip_plan_vjp).  Returns a dict: "X"
         (B, N + 1, nx) and "U" (B, N, nu), tensors whose backward pass carries a loss gradient on (X, U) into x0s.grad through the adjoint of

@@ -668,6 +668,61 @@ int cddp_hip_plan_vjp(cddp_hip_handle *h, int flags, int nvec,
                       const double *gU /* B*nvec*N*nu or NULL = zeros */,
                       double *gx0 /* B*nvec*nx */);
 
+/* ---- scoring candidate control sequences and seeding from the best -----------
+ * The plan a nonconvex solve ends in depends on the control sequence it starts from.  cddp_hip_score_rollouts rolls S candidate control
+ * sequences per trajectory out in ONE launch (csrc/inst_score.hip, one lane per trajectory and candidate) and returns what each is worth:
+ * its objective and its largest constraint violation, optionally the states and the applied controls.  cddp_hip_seed_best picks a winner
+ * per trajectory and seeds the handle from it on the device.  The same rollout scores the plan's feedback policy from a cloud of
+ * initial states (CDDP_HIP_SCORE_FEEDBACK) and a candidate on a mismatched plant (plant != NULL).  Candidates are the caller's: the
+ * library draws no noise and blends nothing.
+ * Arrays: batch-major, then the candidate, then time, then the element, contiguous doubles.  flags without CDDP_HIP_SCORE_DEVICE: host
+ * pointers, staged through device scratch the handle owns (grown on demand, freed with the handle); the call returns when the outputs
+ * are written.  CDDP_HIP_SCORE_DEVICE: every pointer is device memory of the handle's device, checked and ordered as
+ * cddp_hip_get_field_device checks and orders its own; a handle of several tile groups offsets the pointers per group.
+ * Arithmetic (the library is built with -ffp-contract=off; the tests are bitwise), per trajectory b and candidate c:
+ *   x = x0 (x0[b], x0[b][c] with CDDP_HIP_SCORE_X0_PER_CANDIDATE, row 0 of the live plan when x0 is NULL); cost = 0.0; viol = 0.0;
+ *   for t = 0 .. N-1, in this order:
+ *    - u = U[b][c][t].  With CDDP_HIP_SCORE_FEEDBACK u[i] = U[b][c][t][i] + s, s = 0; for j ascending s += K_t[i][j] * (x[j] - X_t[j]):
+ *      the line of cddp_hip_track_plan, X_t and K_t read from the live slot and the gain stack; U == NULL then means the plan's own U_t.
+ *    - with a plant: u[i] = fmin(fmax(u[i], u_lower[i]), u_upper[i]) (only with a box); u is the saturated control from here on.
+ *    - cost += (e^T (Q dt)) e + (u^T (R dt)) u, e = x - x_ref (x - x_ref_traj[t] when the problem has a per-step reference): for every
+ *      column j a zero accumulator r += e[i] * Qdt[i][j], i ascending, then sx += r * e[j]; likewise su; the step adds sx + su.
+ *    - every path row g_i = g(x, u) - upper in the problem's stacked order (the constraint objects sorted by name), as the solver
+ *      evaluates it; viol = max(viol, g_i) for i ascending, written (viol < g_i) ? g_i : viol.
+ *    - x <- step(integrator, dt, params, x, u) of the handle's own model; with a plant `substeps` steps of dt / substeps with the plant's
+ *      parameter block of trajectory b (see "closed loop against a separate plant").
+ *   then cost += (e_N^T Qf) e_N and the terminal INEQUALITY rows A_N x_N - b_N are folded into viol the same way (IPDDP handles; the
+ *   other solvers ignore the terminal set).  Terminal EQUALITIES are not part of viol.
+ *  Cost and rows are evaluated on x_t BEFORE the step: the order of cddp_hip_initialize, whose final_objective a candidate's cost equals
+ *  bit for bit.  viol > 0 means some row is violated by that much; a feasible rollout has viol = 0.  A non-finite state makes cost
+ *  non-finite (0 * NaN is NaN); a NaN row alone is not seen by max().  X_out rows are x_0 .. x_N, U_out rows the controls as applied.
+ *  The handle's solver state is not modified.
+ * cddp_hip_seed_best, per trajectory (csrc/score_select.hpp): a candidate is FINITE when cost and viol are both finite, ADMISSIBLE when
+ * it is finite and viol <= viol_tol.  The winner is the admissible candidate of lowest cost; when none is admissible, the finite
+ * candidate of lowest viol, then of lowest cost; ties go to the lowest c.  When no candidate is finite winner[b] = -1, the trajectory
+ * is seeded from c = 0 and the call still succeeds.  The handle is then left bit for bit as
+ * cddp_hip_set_initial_device(h, x0, U[:, winner], NULL) leaves it (x0 == NULL: the seed's x0 and state rows stay as they are, which
+ * needs an earlier cddp_hip_set_initial); nothing else of the handle changes.
+ * Refused before anything is launched, each with its own message, nothing changed: a NULL handle, unknown flag bits, ncand < 1, a NULL
+ * cost, a NULL U without CDDP_HIP_SCORE_FEEDBACK (seed_best: a NULL U), CDDP_HIP_SCORE_X0_PER_CANDIDATE or a handle without a plan
+ * with a NULL x0, CDDP_HIP_SCORE_FEEDBACK on a handle cddp_hip_track_plan would refuse, a plant cddp_hip_track_plan would refuse, and
+ * with CDDP_HIP_SCORE_DEVICE a pointer cddp_hip_get_field_device would refuse.  (New entry points; ABI version unchanged.) */
+enum { CDDP_HIP_SCORE_DEVICE = 1,            /* every pointer is device memory of the handle's device */
+       CDDP_HIP_SCORE_FEEDBACK = 2,          /* u_t = U_c,t + K_t (x_t - X_t) around the handle's live plan; U == NULL then means the plan's own U */
+       CDDP_HIP_SCORE_X0_PER_CANDIDATE = 4 };/* x0 is [B][S][nx] instead of [B][nx] */
+int cddp_hip_score_rollouts(cddp_hip_handle *h, cddp_hip_plant *plant /* NULL: the handle's own model, integrator, dt, parameters */,
+                            int flags, int ncand /* S >= 1 */,
+                            const double *x0   /* [B][nx] | [B][S][nx] | NULL = row 0 of the live plan */,
+                            const double *U    /* [B][S][N][nu] */,
+                            double *cost       /* [B][S] */,
+                            double *viol       /* [B][S] or NULL */,
+                            double *X_out      /* [B][S][N+1][nx] or NULL */,
+                            double *U_out      /* [B][S][N][nu] applied controls, or NULL */);
+int cddp_hip_seed_best(cddp_hip_handle *h, int flags /* CDDP_HIP_SCORE_DEVICE or 0 */, int ncand,
+                       const double *x0 /* [B][nx] or NULL = keep the handle's x0 */, const double *U /* [B][S][N][nu] */,
+                       const double *cost /* [B][S] */, const double *viol /* [B][S] or NULL = all 0 */, double viol_tol,
+                       int32_t *winner /* [B] or NULL */);
+
 /* ---- multi-GPU: the single collective of the path --------------------------------------
  * One process (or host thread) per GPU, each with its own handle over a contiguous block of the global batch; nothing
  * is exchanged during a solve.  After it, ONE RCCL all-gather collects every trajectory's 16-byte record.
