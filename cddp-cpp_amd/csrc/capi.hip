@@ -18,6 +18,7 @@
 #include "io_kernels.hpp"
 #include "sens_kernels.hpp"
 #include "score_kernels.hpp"
+#include "mppi_kernels.hpp"
 
 // 1 when a[0] > a[1] > ... > a[n - 1] (NaN-free): the ladders cddp_hip_build_alphas makes; DevBuf::ladder_sorted
 static int ladder_strictly_decreasing(const double *a, int n) {
@@ -2731,6 +2732,209 @@ int cddp_hip_seed_best(cddp_hip_handle *h, int flags, int ncand, const double *x
   HIPCHK(hipGetLastError());
   for (Inner *q : h->g) HIPCHK(hipStreamSynchronize(q->stream));
   if (winner) HIPCHK(hipMemcpy(winner, h->d_winner, B * sizeof(int32_t), hipMemcpyDeviceToHost));
+  return join_to_user(h);
+}
+
+// ---- sampling-based plan refinement (inst_mppi.hip): candidates drawn in the kernels, weights and blend of csrc/mppi.hpp ----
+// The refusals the three entries share, in the order of the header: those that read nothing of the handle first.  Fills the draw.
+static int mppi_refuse(const char *me, const cddp_hip_handle *h, int flags, int known, const cddp_hip_mppi_desc *desc, MppiDraw *a) {
+  if (!h) return fail(-1, "%s: null handle", me);
+  if (flags & ~known) return fail(-2, "%s: unknown flag bits 0x%x", me, (unsigned)(flags & ~known));
+  if (!desc) return fail(-1, "%s: null descriptor", me);
+  if (desc->iters < 1) return fail(-2, "%s: iters = %d, at least one round is needed", me, desc->iters);
+  if (desc->ncand < 1) return fail(-2, "%s: ncand = %d, at least one candidate is needed", me, desc->ncand);
+  if (!(desc->lambda > 0.0) || !std::isfinite(desc->lambda)) return fail(-2, "%s: lambda = %g is not positive and finite", me, desc->lambda);
+  if (desc->viol_tol != desc->viol_tol) return fail(-2, "%s: viol_tol is NaN", me);
+  if (!desc->sigma) return fail(-1, "%s: null sigma pointer", me);
+  if ((desc->u_lower == nullptr) != (desc->u_upper == nullptr)) return fail(-2, "%s: half a box: u_lower and u_upper are both set or both NULL", me);
+  const int nu = h->nu;
+  if (nu > kMppiMaxNu) return fail(-3, "%s: nu = %d, the sampling kernels hold at most %d controls", me, nu, kMppiMaxNu);
+  std::memset(a, 0, sizeof(*a));
+  for (int i = 0; i < nu; ++i) {
+    if (!(desc->sigma[i] > 0.0) || !std::isfinite(desc->sigma[i])) return fail(-2, "%s: sigma[%d] = %g is not positive and finite", me, i, desc->sigma[i]);
+    a->sigma[i] = desc->sigma[i];
+    if (desc->u_lower) {
+      if (!(desc->u_lower[i] <= desc->u_upper[i])) return fail(-2, "%s: u_lower[%d] = %g exceeds u_upper[%d] = %g", me, i, desc->u_lower[i], i, desc->u_upper[i]);
+      a->lower[i] = desc->u_lower[i]; a->upper[i] = desc->u_upper[i];
+    }
+  }
+  a->seed = desc->seed; a->stream = desc->stream; a->S = desc->ncand; a->keep_mean = desc->keep_mean ? 1 : 0; a->box = desc->u_lower ? 1 : 0;
+  return 0;
+}
+
+static int mppi_needs_plan_U(const char *me, const cddp_hip_handle *h) {
+  for (const Inner *q : h->g) if (!q->has_plan) return fail(-1, "%s: U_mean is NULL and the handle has no plan whose U could stand in", me);
+  return 0;
+}
+
+// the live plan's U of one group, batch-major, as cddp_hip_get_field_device(CDDP_HIP_FIELD_U) writes it
+static void mppi_plan_U(const cddp_hip_handle *h, const Inner *q, double *out) {
+  io_untile(cddp_io::kSlotted, q->d.U, q->d.cur, q->d.planeU, q->d.B, q->d.NB, h->N, h->nu, out, q->stream);
+}
+
+int cddp_hip_sample_controls(cddp_hip_handle *h, int flags, const cddp_hip_mppi_desc *desc, const double *U_mean, double *U_out) {
+  static const char *const me = "cddp_hip_sample_controls";
+  MppiDraw a;
+  { int rc = mppi_refuse(me, h, flags, CDDP_HIP_SCORE_DEVICE, desc, &a); if (rc) return rc; }
+  if (!U_out) return fail(-1, "%s: null U_out pointer", me);
+  if (!U_mean) { int rc = mppi_needs_plan_U(me, h); if (rc) return rc; }
+  const bool dev = (flags & CDDP_HIP_SCORE_DEVICE) != 0;
+  const size_t B = (size_t)h->B, S = (size_t)desc->ncand, nU = (size_t)h->N * h->nu;
+  if ((B * S * ((nU + 1) / 2) + 255) / 256 > 0x7fffffffull) return fail(-2, "%s: batch * ncand * N * nu / 2 = %zu lanes exceed what one launch holds", me, B * S * ((nU + 1) / 2));
+  HIPCHK(hipSetDevice(h->device));
+  const double *meand = U_mean;
+  double *outd = U_out;
+  if (dev) {
+    if (U_mean) { int rc = io_check_pointer(h, U_mean, B * nU * sizeof(double), me, "U_mean"); if (rc) return rc; }
+    { int rc = io_check_pointer(h, U_out, B * S * nU * sizeof(double), me, "U_out"); if (rc) return rc; }
+    if (!U_mean) { int rc = score_scratch(h, B * nU); if (rc) return rc; meand = h->d_score; }
+  } else {
+    { int rc = score_scratch(h, B * nU + B * S * nU); if (rc) return rc; }
+    if (U_mean) HIPCHK(hipMemcpy(h->d_score, U_mean, B * nU * sizeof(double), hipMemcpyHostToDevice));
+    meand = h->d_score; outd = h->d_score + B * nU;
+  }
+  { int rc = fork_from_user(h); if (rc) return rc; }
+  for (size_t gi = 0; gi < h->g.size(); ++gi) {
+    const Inner *q = h->g[gi];
+    const size_t b0 = (size_t)h->b0[gi];
+    if (!U_mean) mppi_plan_U(h, q, const_cast<double *>(meand) + b0 * nU);
+    a.b0 = (int)b0;
+    HIPCHK(mppi_sample_launch(a, q->d.B, h->N, h->nu, meand + b0 * nU, outd + b0 * S * nU, q->stream));
+  }
+  if (dev) return io_finish(h);
+  HIPCHK(hipGetLastError());
+  for (Inner *q : h->g) HIPCHK(hipStreamSynchronize(q->stream));
+  HIPCHK(hipMemcpy(U_out, outd, B * S * nU * sizeof(double), hipMemcpyDeviceToHost));
+  return join_to_user(h);
+}
+
+int cddp_hip_mppi_blend(cddp_hip_handle *h, int flags, const cddp_hip_mppi_desc *desc, const double *U_mean, const double *U_cand, const double *cost,
+                        const double *viol, double *U_out, double *stats) {
+  static const char *const me = "cddp_hip_mppi_blend";
+  MppiDraw a;
+  { int rc = mppi_refuse(me, h, flags, CDDP_HIP_SCORE_DEVICE, desc, &a); if (rc) return rc; }
+  if (!U_mean) return fail(-1, "%s: null U_mean pointer", me);
+  if (!U_cand) return fail(-1, "%s: null U_cand pointer", me);
+  if (!cost) return fail(-1, "%s: null cost pointer", me);
+  if (!U_out) return fail(-1, "%s: null U_out pointer", me);
+  const bool dev = (flags & CDDP_HIP_SCORE_DEVICE) != 0;
+  const size_t B = (size_t)h->B, S = (size_t)desc->ncand, nU = (size_t)h->N * h->nu;
+  HIPCHK(hipSetDevice(h->device));
+  const double *meand = U_mean, *candd = U_cand, *costd = cost, *viold = viol;
+  double *outd = U_out, *wd, *std_;
+  if (dev) {
+    { int rc = io_check_pointer(h, U_mean, B * nU * sizeof(double), me, "U_mean"); if (rc) return rc; }
+    { int rc = io_check_pointer(h, U_cand, B * S * nU * sizeof(double), me, "U_cand"); if (rc) return rc; }
+    { int rc = io_check_pointer(h, cost, B * S * sizeof(double), me, "cost"); if (rc) return rc; }
+    if (viol) { int rc = io_check_pointer(h, viol, B * S * sizeof(double), me, "viol"); if (rc) return rc; }
+    { int rc = io_check_pointer(h, U_out, B * nU * sizeof(double), me, "U_out"); if (rc) return rc; }
+    if (stats) { int rc = io_check_pointer(h, stats, B * 3 * sizeof(double), me, "stats"); if (rc) return rc; }
+    { int rc = score_scratch(h, B * S + B * 3); if (rc) return rc; }
+    wd = h->d_score; std_ = wd + B * S;
+  } else {
+    { int rc = score_scratch(h, B * S + B * 3 + 2 * B * nU + B * S * nU + 2 * B * S); if (rc) return rc; }
+    double *top = h->d_score;
+    wd = top; top += B * S;
+    std_ = top; top += B * 3;
+    HIPCHK(hipMemcpy(top, U_mean, B * nU * sizeof(double), hipMemcpyHostToDevice)); meand = top; top += B * nU;
+    HIPCHK(hipMemcpy(top, U_cand, B * S * nU * sizeof(double), hipMemcpyHostToDevice)); candd = top; top += B * S * nU;
+    HIPCHK(hipMemcpy(top, cost, B * S * sizeof(double), hipMemcpyHostToDevice)); costd = top; top += B * S;
+    if (viol) { HIPCHK(hipMemcpy(top, viol, B * S * sizeof(double), hipMemcpyHostToDevice)); viold = top; }
+    top += B * S;
+    outd = top;
+  }
+  { int rc = fork_from_user(h); if (rc) return rc; }
+  for (size_t gi = 0; gi < h->g.size(); ++gi) {
+    const Inner *q = h->g[gi];
+    const size_t b0 = (size_t)h->b0[gi];
+    a.b0 = (int)b0;
+    mppi_weights_launch(q->d.B, desc->ncand, costd + b0 * S, viold ? viold + b0 * S : nullptr, desc->viol_tol, desc->lambda, wd + b0 * S, std_ + b0 * 3, q->stream);
+    HIPCHK(mppi_blend_launch(a, q->d.B, h->N, h->nu, meand + b0 * nU, candd + b0 * S * nU, wd + b0 * S, std_ + b0 * 3, outd + b0 * nU, q->stream));
+    if (dev && stats) HIPCHK(hipMemcpyAsync(stats + b0 * 3, std_ + b0 * 3, (size_t)q->d.B * 3 * sizeof(double), hipMemcpyDeviceToDevice, q->stream));
+  }
+  if (dev) return io_finish(h);
+  HIPCHK(hipGetLastError());
+  for (Inner *q : h->g) HIPCHK(hipStreamSynchronize(q->stream));
+  HIPCHK(hipMemcpy(U_out, outd, B * nU * sizeof(double), hipMemcpyDeviceToHost));
+  if (stats) HIPCHK(hipMemcpy(stats, std_, B * 3 * sizeof(double), hipMemcpyDeviceToHost));
+  return join_to_user(h);
+}
+
+int cddp_hip_mppi_refine(cddp_hip_handle *h, cddp_hip_plant *plant, int flags, const cddp_hip_mppi_desc *desc, const double *x0, const double *U_mean,
+                         double *U_out, double *cost_out, double *viol_out, double *stats) {
+  static const char *const me = "cddp_hip_mppi_refine";
+  MppiDraw a;
+  { int rc = mppi_refuse(me, h, flags, CDDP_HIP_SCORE_DEVICE | CDDP_HIP_MPPI_SEED, desc, &a); if (rc) return rc; }
+  if (!U_out) return fail(-1, "%s: null U_out pointer", me);
+  const bool dev = (flags & CDDP_HIP_SCORE_DEVICE) != 0, seed = (flags & CDDP_HIP_MPPI_SEED) != 0;
+  if (!x0) for (const Inner *q : h->g) if (!q->has_plan) return fail(-1, "%s: x0 is NULL and the handle has no plan whose row 0 could stand in", me);
+  if (!x0 && seed) for (const Inner *q : h->g) if (!q->have_initial) return fail(-1, "%s: x0 is NULL and the handle has no initial state to keep (cddp_hip_set_initial)", me);
+  if (!U_mean) { int rc = mppi_needs_plan_U(me, h); if (rc) return rc; }
+  if (plant) { int rc = plant_fits(me, h, plant); if (rc) return rc; }
+  const size_t B = (size_t)h->B, S = (size_t)desc->ncand, nx = (size_t)h->nx, nU = (size_t)h->N * h->nu;
+  if (((size_t)((h->B + 63) / 64 * 64) * S + 63) / 64 > 0x7fffffffull) return fail(-2, "%s: batch * ncand = %zu exceeds what one launch holds", me, B * S);
+  HIPCHK(hipSetDevice(h->device));
+  if (dev) {
+    if (x0) { int rc = io_check_pointer(h, x0, B * nx * sizeof(double), me, "x0"); if (rc) return rc; }
+    if (U_mean) { int rc = io_check_pointer(h, U_mean, B * nU * sizeof(double), me, "U_mean"); if (rc) return rc; }
+    { int rc = io_check_pointer(h, U_out, B * nU * sizeof(double), me, "U_out"); if (rc) return rc; }
+    if (cost_out) { int rc = io_check_pointer(h, cost_out, B * S * sizeof(double), me, "cost_out"); if (rc) return rc; }
+    if (viol_out) { int rc = io_check_pointer(h, viol_out, B * S * sizeof(double), me, "viol_out"); if (rc) return rc; }
+    if (stats) { int rc = io_check_pointer(h, stats, B * 3 * sizeof(double), me, "stats"); if (rc) return rc; }
+  }
+  // scratch: the mean ping-ponged between two [B][N][nu] buffers, cost | viol | w [B][S], stats [B][3], the staged x0 of the host form
+  { int rc = score_scratch(h, 2 * B * nU + 3 * B * S + 3 * B + (dev ? 0 : B * nx)); if (rc) return rc; }
+  double *mean[2] = {h->d_score, h->d_score + B * nU};
+  double *costd = mean[1] + B * nU, *viold = costd + B * S, *wd = viold + B * S, *std_ = wd + B * S;
+  const double *x0d = x0;
+  if (!dev) {
+    if (x0) { double *xs = std_ + 3 * B; HIPCHK(hipMemcpy(xs, x0, B * nx * sizeof(double), hipMemcpyHostToDevice)); x0d = xs; }
+    if (U_mean) HIPCHK(hipMemcpy(mean[0], U_mean, B * nU * sizeof(double), hipMemcpyHostToDevice));
+  }
+  { int rc = fork_from_user(h); if (rc) return rc; }
+  const double *last = mean[desc->iters & 1];   // where the mean lies after the last round
+  for (size_t gi = 0; gi < h->g.size(); ++gi) {
+    Inner *q = h->g[gi];
+    const size_t b0 = (size_t)h->b0[gi], Bg = (size_t)q->d.B;
+    PlantDev pd;
+    if (plant) pd = plant->pd;
+    else {   // the handle's own model as a plant, as cddp_hip_score_rollouts dresses it
+      std::memset(&pd, 0, sizeof(pd));
+      pd.model = q->P.model; pd.integrator = q->P.integrator; pd.substeps = 1; pd.nx = q->P.nx; pd.nu = q->P.nu; pd.Bp = q->d.Bp; pd.h = q->P.dt;
+      pd.params = (const double *)((const char *)q->dP + offsetof(ProblemDev, mp));
+    }
+    if (!U_mean) mppi_plan_U(h, q, mean[0] + b0 * nU);
+    else if (dev) HIPCHK(hipMemcpyAsync(mean[0] + b0 * nU, U_mean + b0 * nU, Bg * nU * sizeof(double), hipMemcpyDeviceToDevice, q->stream));
+    a.b0 = (int)b0;
+    for (int k = 0; k < desc->iters; ++k) {
+      const double *in = mean[k & 1] + b0 * nU;
+      double *out = mean[(k + 1) & 1] + b0 * nU;
+      a.stream = desc->stream + (uint32_t)k;
+      const hipError_t e = mppi_score_launch(pd, q->d, a, x0d ? x0d + b0 * nx : nullptr, in, costd + b0 * S, viold + b0 * S, q->stream);
+      if (e == hipErrorInvalidValue) return fail(-3, "%s: the library has no scoring kernel for model id %d with nx = %d, nu = %d", me, pd.model, pd.nx, pd.nu);
+      HIPCHK(e);
+      mppi_weights_launch(q->d.B, desc->ncand, costd + b0 * S, viold + b0 * S, desc->viol_tol, desc->lambda, wd + b0 * S, std_ + b0 * 3, q->stream);
+      HIPCHK(mppi_blend_launch(a, q->d.B, h->N, h->nu, in, nullptr, wd + b0 * S, std_ + b0 * 3, out, q->stream));
+    }
+    if (seed) {   // exactly as cddp_hip_set_initial_device(x0, U_out, NULL) tiles it
+      if (x0d) io_tile(nullptr, x0d + b0 * nx, q->d.B, q->d.NB, h->N + 1, h->nx, q->d_Xinit, q->stream);
+      io_tile(last + b0 * nU, nullptr, q->d.B, q->d.NB, h->N, h->nu, q->d_Uinit, q->stream);
+      q->have_initial = true; q->initialized = false; q->initial_dirty = true;
+    }
+    if (dev) {
+      HIPCHK(hipMemcpyAsync(U_out + b0 * nU, last + b0 * nU, Bg * nU * sizeof(double), hipMemcpyDeviceToDevice, q->stream));
+      if (cost_out) HIPCHK(hipMemcpyAsync(cost_out + b0 * S, costd + b0 * S, Bg * S * sizeof(double), hipMemcpyDeviceToDevice, q->stream));
+      if (viol_out) HIPCHK(hipMemcpyAsync(viol_out + b0 * S, viold + b0 * S, Bg * S * sizeof(double), hipMemcpyDeviceToDevice, q->stream));
+      if (stats) HIPCHK(hipMemcpyAsync(stats + b0 * 3, std_ + b0 * 3, Bg * 3 * sizeof(double), hipMemcpyDeviceToDevice, q->stream));
+    }
+  }
+  if (dev) return io_finish(h);
+  HIPCHK(hipGetLastError());
+  for (Inner *q : h->g) HIPCHK(hipStreamSynchronize(q->stream));
+  HIPCHK(hipMemcpy(U_out, last, B * nU * sizeof(double), hipMemcpyDeviceToHost));
+  if (cost_out) HIPCHK(hipMemcpy(cost_out, costd, B * S * sizeof(double), hipMemcpyDeviceToHost));
+  if (viol_out) HIPCHK(hipMemcpy(viol_out, viold, B * S * sizeof(double), hipMemcpyDeviceToHost));
+  if (stats) HIPCHK(hipMemcpy(stats, std_, B * 3 * sizeof(double), hipMemcpyDeviceToHost));
   return join_to_user(h);
 }
 

@@ -899,6 +899,25 @@ class HipBatchSolver : public ISolverAlgorithm {
     if (!h_) throw std::runtime_error("cddp_hip: seedBest needs a resident batch (the plug-in route has no resident handle)");
     check(cddp_hip_seed_best(h_, flags, ncand, x0, U, cost, viol, viol_tol, winner));
   }
+  // NEW: the sampling front end (include/cddp_hip.h "sampling-based plan refinement").  desc: seed, stream, iters, ncand, keep_mean, lambda,
+  // viol_tol and the host arrays sigma[nu], u_lower[nu], u_upper[nu].  sampleControls writes the candidates [batch][ncand][N][nu] drawn around
+  // U_mean (nullptr: the live plan's U); mppiBlend weighs and blends candidates of the caller's; mppiRefine runs desc.iters rounds of draw ->
+  // roll out -> weights -> blend without storing a candidate (cost_out, viol_out [batch][ncand] and stats [batch][3] = n_adm, rho, ess are the
+  // last round's and may be nullptr) and, with CDDP_HIP_MPPI_SEED, seeds the batch from the refined mean; resolveBatch() solves.
+  void sampleControls(int flags, const cddp_hip_mppi_desc &desc, const double *U_mean /* batch*N*nu | nullptr */, double *U_out /* batch*ncand*N*nu */) {
+    if (!h_) throw std::runtime_error("cddp_hip: sampleControls needs a resident batch (the plug-in route has no resident handle)");
+    check(cddp_hip_sample_controls(h_, flags, &desc, U_mean, U_out));
+  }
+  void mppiBlend(int flags, const cddp_hip_mppi_desc &desc, const double *U_mean, const double *U_cand, const double *cost, const double *viol,
+                 double *U_out /* batch*N*nu */, double *stats = nullptr) {
+    if (!h_) throw std::runtime_error("cddp_hip: mppiBlend needs a resident batch (the plug-in route has no resident handle)");
+    check(cddp_hip_mppi_blend(h_, flags, &desc, U_mean, U_cand, cost, viol, U_out, stats));
+  }
+  void mppiRefine(Plant *plant, int flags, const cddp_hip_mppi_desc &desc, const double *x0 /* batch*nx | nullptr */, const double *U_mean /* | nullptr */,
+                  double *U_out /* batch*N*nu */, double *cost_out = nullptr, double *viol_out = nullptr, double *stats = nullptr) {
+    if (!h_) throw std::runtime_error("cddp_hip: mppiRefine needs a resident batch (the plug-in route has no resident handle)");
+    check(cddp_hip_mppi_refine(h_, plant ? plant->get() : nullptr, flags, &desc, x0, U_mean, U_out, cost_out, viol_out, stats));
+  }
   // NEW: solve the resident batch again from the seed it holds now (setInitialDevice, mpcAdvance) -- solveBatch() without creating and uploading
   std::vector<CDDPSolution> resolveBatch(CDDP &ctx) {
     if (!h_) throw std::runtime_error("cddp_hip: resolveBatch needs a resident batch (the plug-in route has no resident handle)");

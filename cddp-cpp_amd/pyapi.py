@@ -171,6 +171,8 @@ SENS_DEVICE = 1
 SCORE_DEVICE = 1
 SCORE_FEEDBACK = 2
 SCORE_X0_PER_CANDIDATE = 4
+# cddp_hip_sample_controls / cddp_hip_mppi_blend / cddp_hip_mppi_refine (include/cddp_hip.h, "sampling-based plan refinement")
+MPPI_SEED = 8
 # cddp_hip_get_field_device / cddp_hip_field_shape (include/cddp_hip.h, "device-resident inputs and outputs"): enum cddp_hip_field
 FIELD_NAMES = ("X", "U", "K", "KFF", "VX", "VXX", "A", "B", "S", "Y", "G", "LAMBDA")
 FIELD_IDS = {name: i for i, name in enumerate(FIELD_NAMES)}
@@ -188,6 +190,13 @@ class PlantDesc(C.Structure):   # cddp_hip_plant_desc
         ("abi_version", C.c_int32), ("model", C.c_int32), ("integrator", C.c_int32), ("substeps", C.c_int32),
         ("nx", C.c_int32), ("nu", C.c_int32), ("params_per_trajectory", C.c_int32), ("_pad", C.c_int32),
         ("dt", C.c_double), ("model_params", _dp), ("lti_A", _dp), ("lti_B", _dp), ("u_lower", _dp), ("u_upper", _dp),
+    ]
+
+
+class MppiDesc(C.Structure):   # cddp_hip_mppi_desc
+    _fields_ = [
+        ("seed", C.c_uint64), ("stream", C.c_uint32), ("iters", C.c_int32), ("ncand", C.c_int32), ("keep_mean", C.c_int32),
+        ("lam", C.c_double), ("viol_tol", C.c_double), ("sigma", _dp), ("u_lower", _dp), ("u_upper", _dp),
     ]
 
 
@@ -830,6 +839,9 @@ DEVICE_IO_ARGTYPES = {
     "cddp_hip_plan_vjp": [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
     "cddp_hip_score_rollouts": [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
     "cddp_hip_seed_best": [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p],
+    "cddp_hip_sample_controls": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
+    "cddp_hip_mppi_blend": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    "cddp_hip_mppi_refine": [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
 }
 
 EXPORTED_SYMBOLS = [
@@ -848,6 +860,7 @@ EXPORTED_SYMBOLS = [
     "cddp_hip_field_shape", "cddp_hip_get_field_device", "cddp_hip_get_results_device", "cddp_hip_set_initial_device", "cddp_hip_get_live_slots",
     "cddp_hip_plan_jvp", "cddp_hip_plan_vjp",
     "cddp_hip_score_rollouts", "cddp_hip_seed_best",
+    "cddp_hip_sample_controls", "cddp_hip_mppi_blend", "cddp_hip_mppi_refine",
 ]
 
 
@@ -1402,6 +1415,115 @@ class HipBatchSolver:
         self._check(self.lib.cddp_hip_seed_best(self.h, SCORE_DEVICE if device else 0, S, self._addr(x0), self._addr(U), self._addr(cost),
                                                 self._addr(viol), viol_tol, self._addr(winner)))
         return winner
+
+    # ---- sampling-based plan refinement (cddp_hip_sample_controls / cddp_hip_mppi_blend / cddp_hip_mppi_refine): the conventions of
+    # score_rollouts -- numpy arrays take the host path, torch.float64 tensors on the handle's device the device path, one kind per call
+    def _mppi_desc(self, who, sigma, ncand, lam=1.0, seed=0, stream=0, iters=1, keep_mean=False, viol_tol=0.0, u_lower=None, u_upper=None):
+        """-> (MppiDesc, the arrays it points into).  What can be refused without the library is refused here with ValueError."""
+        nu = self.p.nu
+        ncand = int(ncand); iters = int(iters); lam = float(lam); viol_tol = float(viol_tol); seed = int(seed); stream = int(stream)
+        if ncand < 1:
+            raise ValueError("%s: ncand: at least one candidate is expected, got %d" % (who, ncand))
+        if iters < 1:
+            raise ValueError("%s: iters: at least one round is expected, got %d" % (who, iters))
+        if not (lam > 0.0 and np.isfinite(lam)):
+            raise ValueError("%s: lam: a positive finite temperature is expected, got %r" % (who, lam))
+        if not 0 <= seed < 2 ** 64 or not 0 <= stream < 2 ** 32:
+            raise ValueError("%s: seed is a 64-bit and stream a 32-bit unsigned number, got %r and %r" % (who, seed, stream))
+        sg = np.ascontiguousarray(np.broadcast_to(np.asarray(sigma, dtype=np.float64), (nu,)) if np.ndim(sigma) == 0 else np.asarray(sigma, dtype=np.float64))
+        if sg.shape != (nu,) or not (np.isfinite(sg).all() and (sg > 0.0).all()):
+            raise ValueError("%s: sigma: %d positive finite entries (or one scalar) are expected, got %r" % (who, nu, sigma))
+        if (u_lower is None) != (u_upper is None):
+            raise ValueError("%s: u_lower and u_upper are both given or both None" % who)
+        d = MppiDesc()
+        d.seed = seed; d.stream = stream; d.iters = iters; d.ncand = ncand; d.keep_mean = 1 if keep_mean else 0; d.lam = lam; d.viol_tol = viol_tol
+        keep = [sg]
+        d.sigma = _ptr(sg)
+        if u_lower is not None:
+            lo = np.ascontiguousarray(np.asarray(u_lower, dtype=np.float64)); up = np.ascontiguousarray(np.asarray(u_upper, dtype=np.float64))
+            if lo.shape != (nu,) or up.shape != (nu,) or not (lo <= up).all():
+                raise ValueError("%s: u_lower, u_upper: %d entries each with u_lower <= u_upper are expected" % (who, nu))
+            keep += [lo, up]
+            d.u_lower = _ptr(lo); d.u_upper = _ptr(up)
+        return d, keep
+
+    def _is_device(self, *arrays):
+        return any(hasattr(a, "data_ptr") and not isinstance(a, np.ndarray) for a in arrays if a is not None)
+
+    def _mppi_out(self, shape, device):
+        if device:
+            import torch
+            return torch.empty(shape, dtype=torch.float64, device=self._torch_device())
+        return np.zeros(shape)
+
+    def sample_controls(self, sigma, ncand, U_mean=None, device=None, **draw):
+        """The S = ncand candidate controls the refinement draws around U_mean (B, N, nu), or around the live plan's U when it is None
+        (cddp_hip_sample_controls): (B, S, N, nu), u = U_mean + sigma * z clipped to [u_lower, u_upper], z a standard normal that is a
+        function of (seed, stream, trajectory, candidate, element) alone.  draw: seed, stream, keep_mean, u_lower, u_upper.  numpy in, numpy
+        out; a device tensor in (or device=True with U_mean None), a device tensor out."""
+        who = "sample_controls"
+        B, N, nu = self.B, self.p.N, self.p.nu
+        d, keep = self._mppi_desc(who, sigma, ncand, **draw)
+        dev = self._is_device(U_mean) if device is None else bool(device)
+        if U_mean is not None:
+            U_mean = self._score_arg(who, "U_mean", U_mean, [(B, N, nu)], dev)
+        out = self._mppi_out((B, d.ncand, N, nu), dev)
+        if dev:
+            self._order_device_io()
+        self._check(self.lib.cddp_hip_sample_controls(self.h, SCORE_DEVICE if dev else 0, C.addressof(d), self._addr(U_mean), self._addr(out)))
+        return out
+
+    def mppi_blend(self, U_mean, U_cand, cost, viol=None, lam=1.0, viol_tol=0.0, u_lower=None, u_upper=None):
+        """Softmin weights and blend over candidates the caller supplies (cddp_hip_mppi_blend): U_mean (B, N, nu), U_cand (B, S, N, nu),
+        cost and viol (B, S) (viol None: all 0).  Admissible = finite with viol <= viol_tol; w_c = exp(-(cost_c - rho) / lam) / eta over the
+        admissible candidates, rho their lowest cost; U' = U_mean + sum_c w_c (U_c - U_mean), clipped to the box.  Returns (U', stats), stats
+        (B, 3) = n_adm, rho, ess; a trajectory without an admissible candidate keeps its mean.  numpy arrays or device tensors, of one kind."""
+        who = "mppi_blend"
+        B, N, nu = self.B, self.p.N, self.p.nu
+        if U_mean is None or U_cand is None or cost is None:
+            raise ValueError("%s: U_mean, U_cand and cost are required" % who)
+        if len(tuple(np.shape(U_cand))) != 4 or int(np.shape(U_cand)[1]) < 1:
+            raise ValueError("%s: U_cand: shape (%d, S, %d, %d) with S >= 1 is expected, got %s" % (who, B, N, nu, tuple(np.shape(U_cand))))
+        S = int(np.shape(U_cand)[1])
+        d, keep = self._mppi_desc(who, 1.0, S, lam=lam, viol_tol=viol_tol, u_lower=u_lower, u_upper=u_upper)
+        dev = self._is_device(U_cand)
+        U_mean = self._score_arg(who, "U_mean", U_mean, [(B, N, nu)], dev)
+        U_cand = self._score_arg(who, "U_cand", U_cand, [(B, S, N, nu)], dev)
+        cost = self._score_arg(who, "cost", cost, [(B, S)], dev)
+        if viol is not None:
+            viol = self._score_arg(who, "viol", viol, [(B, S)], dev)
+        out = self._mppi_out((B, N, nu), dev); stats = self._mppi_out((B, 3), dev)
+        if dev:
+            self._order_device_io()
+        self._check(self.lib.cddp_hip_mppi_blend(self.h, SCORE_DEVICE if dev else 0, C.addressof(d), self._addr(U_mean), self._addr(U_cand),
+                                                 self._addr(cost), self._addr(viol), self._addr(out), self._addr(stats)))
+        return out, stats
+
+    def mppi_refine(self, sigma, ncand, x0=None, U_mean=None, plant=None, seed_handle=False, device=None, **draw):
+        """`iters` rounds of draw -> roll out -> softmin weights -> blend around U_mean (B, N, nu; None: the live plan's U), from x0 (B, nx;
+        None: row 0 of the live plan), on the handle's model or a DevicePlant (cddp_hip_mppi_refine).  The candidates are drawn inside the
+        kernels: no (B, S, N, nu) array exists.  draw: lam, seed, stream, iters, keep_mean, viol_tol, u_lower, u_upper; round k draws from
+        stream + k.  Returns a dict: "U" (B, N, nu) the refined mean, "cost" and "viol" (B, S) and "stats" (B, 3) = n_adm, rho, ess of the
+        last round.  seed_handle=True leaves the handle as set_initial_device(x0, U) leaves it.  numpy arrays or device tensors (device=True
+        when both arrays are None); the handle's solver state is otherwise untouched."""
+        who = "mppi_refine"
+        B, N, nx, nu = self.B, self.p.N, self.p.nx, self.p.nu
+        d, keep = self._mppi_desc(who, sigma, ncand, **draw)
+        dev = self._is_device(x0, U_mean) if device is None else bool(device)
+        if x0 is not None:
+            x0 = self._score_arg(who, "x0", x0, [(B, nx)], dev)
+        if U_mean is not None:
+            U_mean = self._score_arg(who, "U_mean", U_mean, [(B, N, nu)], dev)
+        S = d.ncand
+        out = {"U": self._mppi_out((B, N, nu), dev), "cost": self._mppi_out((B, S), dev), "viol": self._mppi_out((B, S), dev),
+               "stats": self._mppi_out((B, 3), dev)}
+        flags = (SCORE_DEVICE if dev else 0) | (MPPI_SEED if seed_handle else 0)
+        if dev:
+            self._order_device_io()
+        self._check(self.lib.cddp_hip_mppi_refine(self.h, plant.h if plant is not None else None, flags, C.addressof(d), self._addr(x0),
+                                                  self._addr(U_mean), self._addr(out["U"]), self._addr(out["cost"]), self._addr(out["viol"]),
+                                                  self._addr(out["stats"])))
+        return out
 
 
 class DevicePlant:

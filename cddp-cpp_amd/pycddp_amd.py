@@ -1230,6 +1230,51 @@ class CDDP:                         # cddp_core.hpp:214-423 / bind_solver.cpp:57
         out["seed_cost"] = sc["cost"].gather(1, winner.clamp(min=0).long().unsqueeze(1)).squeeze(1)
         return out
 
+    def solve_batch_mppi(self, x0s, U0, sigma, ncand, iters=1, lam=1.0, seed=0, stream=0, keep_mean=True, viol_tol=0.0, u_lower=None,
+                         u_upper=None, solver_type=SolverType.IPDDP, want=("X", "U")):
+        """NEW (no reference counterpart): solve_batch_device behind a sampling front end (cddp_hip_mppi_refine).  `iters` rounds of: draw
+        ncand controls per trajectory around the current mean (u = mean + sigma * z, clipped to [u_lower, u_upper]), roll them out, weight
+        the admissible ones (largest constraint violation <= viol_tol) by exp(-(cost - lowest cost) / lam), blend; the refined mean seeds
+        the handle and the batch is solved from there.  The candidates are drawn inside the kernels from a counter-based generator: the
+        result is a function of (seed, stream) alone and no (B, S, N, nu) array is stored.  x0s: (B, nx), U0: (B, N, nu) -- torch.float64,
+        contiguous, on cuda:0.  Returns what solve_batch_device returns, plus "stats" ((B, 3): admissible candidates, lowest admissible
+        cost and effective sample size of the last round) and "U_seed" ((B, N, nu), the refined mean the solve started from)."""
+        import torch
+        api = _api()
+        name = solver_type.value if isinstance(solver_type, SolverType) else str(solver_type)
+        want = tuple(want)
+        unknown = [w for w in want if w not in api.FIELD_IDS]
+        if unknown:
+            raise ValueError("want: unknown fields %s (known: %s)" % (unknown, ", ".join(api.FIELD_NAMES)))
+        if self._sys is None:
+            raise RuntimeError("Dynamical system must be set before solving.")
+        kind = self._resident_kind(name)
+        if kind is None:
+            raise NotImplementedError("solve_batch_mppi needs a problem of the resident route (built-in plant, objective and constraints): "
+                                      "solver '%s' with this problem runs on the plug-in route, which has no resident handle" % name)
+        if not isinstance(x0s, torch.Tensor) or x0s.dim() != 2:
+            raise ValueError("x0s: a (B, nx) torch tensor is expected")
+        if not isinstance(U0, torch.Tensor) or U0.dim() != 3:
+            raise ValueError("U0: a (B, N, nu) torch tensor is expected")
+        B = int(x0s.shape[0])
+        if B <= 0:
+            raise ValueError("x0s: an empty batch")
+        p = self._problem(kind)
+        hs = api.HipBatchSolver(p, B)
+        try:
+            ref = hs.mppi_refine(sigma, ncand, x0=x0s, U_mean=U0, seed_handle=True, iters=iters, lam=lam, seed=seed, stream=stream,
+                                 keep_mean=keep_mean, viol_tol=viol_tol, u_lower=u_lower, u_upper=u_upper)
+            st = hs.solve()
+            out = {w: hs.field_device(w) for w in want}
+            res = hs.results_device()
+        finally:
+            hs.close()
+        out["results"] = {k: v for k, v in res.items() if k not in ("cols", "icols")}
+        out["solve_time_ms"] = float(st.solve_ms)
+        out["stats"] = ref["stats"]
+        out["U_seed"] = ref["U"]
+        return out
+
     def solve_batch_diff(self, x0s, U0=None, X0=None, solver_type=SolverType.IPDDP, refresh=False):
         """NEW (no reference counterpart): solve_batch_device as a differentiable function of x0s (cddp_hip_plan_vjp).  Returns a dict: "X"
         (B, N + 1, nx) and "U" (B, N, nu), tensors whose backward pass carries a loss gradient on (X, U) into x0s.grad through the adjoint of

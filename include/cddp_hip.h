@@ -673,8 +673,8 @@ int cddp_hip_plan_vjp(cddp_hip_handle *h, int flags, int nvec,
  * sequences per trajectory out in ONE launch (csrc/inst_score.hip, one lane per trajectory and candidate) and returns what each is worth:
  * its objective and its largest constraint violation, optionally the states and the applied controls.  cddp_hip_seed_best picks a winner
  * per trajectory and seeds the handle from it on the device.  The same rollout scores the plan's feedback policy from a cloud of
- * initial states (CDDP_HIP_SCORE_FEEDBACK) and a candidate on a mismatched plant (plant != NULL).  Candidates are the caller's: the
- * library draws no noise and blends nothing.
+ * initial states (CDDP_HIP_SCORE_FEEDBACK) and a candidate on a mismatched plant (plant != NULL).  Candidates are the caller's here:
+ * these two entries draw no noise and blend nothing ("sampling-based plan refinement" below does).
  * Arrays: batch-major, then the candidate, then time, then the element, contiguous doubles.  flags without CDDP_HIP_SCORE_DEVICE: host
  * pointers, staged through device scratch the handle owns (grown on demand, freed with the handle); the call returns when the outputs
  * are written.  CDDP_HIP_SCORE_DEVICE: every pointer is device memory of the handle's device, checked and ordered as
@@ -722,6 +722,64 @@ int cddp_hip_seed_best(cddp_hip_handle *h, int flags /* CDDP_HIP_SCORE_DEVICE or
                        const double *x0 /* [B][nx] or NULL = keep the handle's x0 */, const double *U /* [B][S][N][nu] */,
                        const double *cost /* [B][S] */, const double *viol /* [B][S] or NULL = all 0 */, double viol_tol,
                        int32_t *winner /* [B] or NULL */);
+
+/* ---- sampling-based plan refinement (MPPI) with candidates drawn in the kernel -----------
+ * The sampling front end of a nonconvex solve: perturb the current plan, roll the candidates out, weight them by a softmin of their cost,
+ * blend, repeat, then seed the solver.  The candidates come from a counter-based generator, so the lane that scores a candidate and the
+ * lane that blends it draw the same numbers and no [B][S][N][nu] array lies between them (cddp_hip_mppi_refine allocates none); results
+ * are a function of (seed, stream) alone, and a tile group draws what the whole batch would draw because the counter carries the
+ * trajectory's index in the batch.  csrc/mppi.hpp is the normative statement (host and device compile it), restated here; the library is
+ * built with -ffp-contract=off and the tests are bitwise.
+ * Generator: Philox4x32-10, multipliers 0xD2511F53 and 0xCD9E8D57, key increments 0x9E3779B9 and 0xBB67AE85.
+ * Normal pair: element e = t * nu + i of candidate c of trajectory b lies in pair j = e >> 1.  Counter = (j, c, b, stream), key = (seed
+ *  low word, seed high word), output words r0..r3; m1 = ((u64)r1 << 32 | r0) >> 11, m2 = ((u64)r3 << 32 | r2) >> 11,
+ *  u1 = ((double)m1 + 1.0) * 0x1p-53, u2 = (double)m2 * 0x1p-53, rad = sqrt(-2.0 * log_fast(u1)),
+ *  (s, co) = sincos_fast(0x1.921fb54442d18p+2 * u2); z = rad * co for even e, rad * s for odd e (log_fast, sincos_fast: csrc/dev_trig.hpp,
+ *  always inside their fast range; sqrt correctly rounded).
+ * Candidate: u_c[t][i] = mean[t][i] + sigma[i] * z, then fmin(fmax(u, u_lower[i]), u_upper[i]) with a box; with keep_mean candidate 0
+ *  takes z = 0.
+ * Weights, per trajectory over c ascending: a candidate is admissible when cost and viol are finite and viol <= viol_tol (the predicate of
+ *  cddp_hip_seed_best).  rho = the lowest admissible cost, q = (cost_c - rho) / lambda, a_c = q <= 700.0 ? exp_fast(-q) : 0.0 (0 when
+ *  inadmissible), eta = sum a_c, w_c = a_c / eta, ess = 1 / sum w_c^2.  When no candidate is admissible every w_c = 0, the trajectory's
+ *  mean is left as it is and n_adm = rho = ess = 0.
+ * Blend, per element: s = 0; for c ascending s += w_c * (u_c[t][i] - mean[t][i]); mean' = mean + s, clipped to the box when there is one.
+ * cddp_hip_sample_controls writes the candidates of desc->stream around U_mean (NULL: the live plan's U, which needs a plan).
+ * cddp_hip_mppi_blend weighs and blends candidates the caller supplies as they lie (viol NULL = all 0); only lambda, viol_tol, ncand and the
+ *  box of the descriptor matter to it.  stats is [B][3] = n_adm, rho, ess.
+ * cddp_hip_mppi_refine runs desc->iters rounds of score -> weights -> blend, round k with stream desc->stream + k.  Scoring is
+ *  cddp_hip_score_rollouts' arithmetic and order without feedback, on the handle's model or on `plant`, whose own box is applied after the
+ *  descriptor's (the blend uses the control as drawn and clipped by the descriptor's box).  x0 NULL: row 0 of the live plan.  U_out is the
+ *  mean after the last round; cost_out, viol_out [B][S] and stats [B][3] (each may be NULL) are those of the last round.  With
+ *  CDDP_HIP_MPPI_SEED the handle is then left bit for bit as cddp_hip_set_initial_device(h, x0, U_out, NULL) leaves it (x0 NULL: the seed's
+ *  x0 and state rows stay as they are, which needs an earlier cddp_hip_set_initial); otherwise the handle's solver state is untouched.
+ * Flags, pointer checks, stream ordering, tile-group offsets and the handle-owned scratch are those of cddp_hip_score_rollouts: host
+ * pointers by default, CDDP_HIP_SCORE_DEVICE for device pointers (sigma and the box are always host arrays, read during the call).
+ * Refused before anything is launched, each with its own message: a NULL handle or descriptor, unknown flag bits, iters < 1, ncand < 1, a
+ * lambda that is not positive and finite, a NaN viol_tol, a NULL sigma or an entry that is not positive and finite, a half-given box or
+ * lower > upper, a NULL U_mean on a handle without a plan, a NULL output, what cddp_hip_score_rollouts refuses of x0 and the plant, what
+ * cddp_hip_seed_best refuses of a NULL x0 (CDDP_HIP_MPPI_SEED), and with CDDP_HIP_SCORE_DEVICE a pointer cddp_hip_get_field_device would
+ * refuse.  (New entry points; ABI version unchanged.) */
+typedef struct cddp_hip_mppi_desc {
+  uint64_t seed;
+  uint32_t stream;                     /* the noise stream; refinement round k draws from stream + k */
+  int32_t iters;                       /* rounds of cddp_hip_mppi_refine (>= 1; the other entries ignore it but check it) */
+  int32_t ncand;                       /* S >= 1 */
+  int32_t keep_mean;                   /* nonzero: candidate 0 is the mean itself */
+  double lambda;                       /* temperature of the softmin, positive */
+  double viol_tol;
+  const double *sigma;                 /* [nu], host */
+  const double *u_lower, *u_upper;     /* [nu], host; both set or both NULL */
+} cddp_hip_mppi_desc;                  /* 64 bytes */
+enum { CDDP_HIP_MPPI_SEED = 8 };       /* cddp_hip_mppi_refine: seed the handle from the refined mean (with CDDP_HIP_SCORE_DEVICE or without) */
+int cddp_hip_sample_controls(cddp_hip_handle *h, int flags, const cddp_hip_mppi_desc *desc,
+                             const double *U_mean /* [B][N][nu] or NULL = the live plan's U */, double *U_out /* [B][S][N][nu] */);
+int cddp_hip_mppi_blend(cddp_hip_handle *h, int flags, const cddp_hip_mppi_desc *desc, const double *U_mean /* [B][N][nu] */,
+                        const double *U_cand /* [B][S][N][nu] */, const double *cost /* [B][S] */, const double *viol /* [B][S] or NULL */,
+                        double *U_out /* [B][N][nu] */, double *stats /* [B][3] or NULL */);
+int cddp_hip_mppi_refine(cddp_hip_handle *h, cddp_hip_plant *plant /* or NULL */, int flags, const cddp_hip_mppi_desc *desc,
+                         const double *x0 /* [B][nx] or NULL */, const double *U_mean /* [B][N][nu] or NULL = the live plan's U */,
+                         double *U_out /* [B][N][nu] */, double *cost_out /* [B][S] or NULL */, double *viol_out /* [B][S] or NULL */,
+                         double *stats /* [B][3] or NULL */);
 
 /* ---- multi-GPU: the single collective of the path --------------------------------------
  * One process (or host thread) per GPU, each with its own handle over a contiguous block of the global batch; nothing
