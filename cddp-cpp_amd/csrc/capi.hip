@@ -975,6 +975,30 @@ static int in_backward(Inner *h, int32_t *ok) {
   return 0;
 }
 
+// Time-sliced wave priority of a two-role IPDDP rollout launch (launch.hpp::RollSlice, PcSlice; kernels_lean.hpp::k_forward_ipddp_pc_sl).  n_run: the
+// step sizes whose workgroups run from the launch's start (the whole ladder, or the first stage of a split launch: a sleeping stage-2
+// workgroup takes no issue slots).  late_from = the workgroups that give every SIMD of the stream's share of the chip one wave; the window
+// is on only where the running waves exceed those SIMDs.  CDDP_HIP_K4_SLICE_US = 0: never; n > 0: a window of about n us on EVERY launch,
+// those of cddp_hip_forward included (the tests); CDDP_HIP_K4_LATE_PRIO=1: a fixed priority 3 for the late class instead of the window
+// (the comparison row).  A speed heuristic only: HIP promises no dispatch order and no result depends on either figure.
+// The default window, microseconds (rounded to a power of two of 10-ns ticks: 2.56 us, about one and a half producer steps of the cart-pole).
+// Headline sweep of profiles/r17_simd_sharing.md section 3: the shorter the window the better down to this one; a fixed priority is worse than none.
+constexpr int kK4SliceUs = 2;
+static RollSlice roll_slice_for(const Inner *h, int conc, int n_run) {
+  RollSlice sl;
+  const Knobs &k = *h->knob;
+  if (k.k4_slice_us == 0 || h->P.solver != CDDP_HIP_SOLVER_IPDDP || h->route.rollout != Route::kPair) return sl;
+  const long simds = std::max(4L, (long)device_cu_count(h->device) * 4 / std::max(1, conc)), waves_per_wg = 2;
+  sl.late_from = (int)(simds / waves_per_wg);
+  const bool forced = k.k4_slice_us > 0;
+  if (!forced && (long)((h->d.B + 63) / 64) * n_run * waves_per_wg <= simds) return sl;
+  if (k.k4_late_prio) { sl.ticks = kSliceFixedLate; return sl; }
+  const long want = 100L * (forced ? k.k4_slice_us : kK4SliceUs);   // ticks of the 100 MHz clock, rounded to a power of two (3 / 4 < ratio <= 3 / 2)
+  sl.ticks = 1ull;
+  while ((long)sl.ticks * 4 < want * 3) sl.ticks <<= 1;
+  return sl;
+}
+
 static int in_forward(Inner *h, const double *alphas, int n_alphas, cddp_hip_trial *trials) {
   if (!h || !alphas || !trials) return fail(-1, "null argument");
   if (n_alphas <= 0 || n_alphas > h->d.n_alphas) return fail(-1, "n_alphas must be in [1, %d] (the handle's ladder size)", h->d.n_alphas);
@@ -985,7 +1009,7 @@ static int in_forward(Inner *h, const double *alphas, int n_alphas, cddp_hip_tri
   HIPCHK(hipMemcpyAsync(h->dP, &tmp, sizeof(ProblemDev), hipMemcpyHostToDevice, h->stream));
   DevBuf dcall = h->d;   // (the caller's ladder may be any set of step sizes)
   dcall.ladder_sorted = ladder_strictly_decreasing(tmp.alphas, h->d.n_alphas);
-  h->ks->forward(dcall, h->route, h->P.solver, 0, n_alphas, PH_FWD1, 1, 0, h->stream, 0, 0);
+  h->ks->forward(dcall, h->route, h->P.solver, 0, n_alphas, PH_FWD1, 1, 0, h->stream, 0, 0, roll_slice_for(h, 1, n_alphas));
   h->ks->costate(dcall, h->route, h->P.solver, 0, n_alphas, PH_FWD1, 1, 0, h->stream);
   HIPCHK(hipGetLastError());
   const DevBuf &d = h->d;
@@ -1113,7 +1137,11 @@ struct SolveRun {
       if (waves_all <= 2048) { one_stage = true; }
       else { one_stage = false; k1 = k_cap2; }
     } else {
-      one_stage = false; k1 = std::max(1, std::min(kq + h->knob->ls_margin, k_cap));   // + 1: the histogram drifts between polls (CDDP_HIP_LS_MARGIN)
+      // Margin (CDDP_HIP_LS_MARGIN; an explicit value holds everywhere): + 1 for the two-launch shapes, because the histogram drifts
+      // between polls and a miss costs a second group-wide rollout + update (+ flush); + 0 where both stages run in one rollout launch
+      // (`inkernel`), where a miss costs one tile's chain inside the launch (round 17).
+      const int margin = h->knob->ls_margin >= 0 ? h->knob->ls_margin : (inkernel ? 0 : 1);
+      one_stage = false; k1 = std::max(1, std::min(kq + margin, k_cap));
       // A chip that the whole ladder fills at most twice (one-stage territory) gains from a short first stage only what the
       // smaller launch saves over the rollout's latency floor (C2: 291 -> ~200 us at five step sizes), and loses a full second
       // rollout + costate + update (~235 us) whenever ONE trajectory walks past k1: kept only for a first stage of at most 768
@@ -1122,7 +1150,8 @@ struct SolveRun {
       // (Round 13: where both stages run in one rollout launch -- `inkernel` -- a miss costs one tile's chain inside the launch, not
       //  a second group-wide rollout + update + flush.  Re-swept under that cost, profiles/r13_inkernel_stages.md section 7: 768 /
       //  1024 / 2048 -> 37.0 / 37.2 / 37.2 ms per C2 solve, inside the spread: the threshold stays.  CDDP_HIP_LS_MARGIN=0 measured
-      //  -0.6 ms there and is recorded as a candidate, not adopted.)
+      //  -0.6 ms there; round 17 repeated it in alternated rounds and made it the default of the in-kernel form, see `margin` above and
+      //  profiles/r17_simd_sharing.md.)
       if (waves_all <= 2048 && (long)k1 * per_alpha_waves > two_stage_max_waves) one_stage = true;
       // A ladder that fits the chip once (at most one wavefront per SIMD) and light per-step work (nx <= 8): a first stage of more than
       // half of the ladder saves next to nothing over the whole ladder, while ONE trajectory past k1 costs a second full chain -- and
@@ -1140,6 +1169,8 @@ struct SolveRun {
       std::fprintf(stderr, "\n");
     }
   }
+
+  RollSlice roll_slice(int n_run) const { return roll_slice_for(h, conc, n_run); }
 
   int begin(Inner *h_, bool stats_, int conc_) {
     h = h_; want_stats = stats_; conc = std::max(1, conc_);
@@ -1250,7 +1281,7 @@ struct SolveRun {
     if (one_stage || split) {
       // (split: the workgroups of the step sizes >= k1 learn inside the launch which lanes of their tile still need them; cur[b] does not
       //  change between the stages, so every accept carries the deferred stamp and no flush sits between rollouts)
-      ks->forward(d, r, P.solver, 0, na, PH_FWD1, 0, first_rule ? 1 : 0, sf, split ? k1 : 0, poll_us);
+      ks->forward(d, r, P.solver, 0, na, PH_FWD1, 0, first_rule ? 1 : 0, sf, split ? k1 : 0, poll_us, roll_slice(split ? k1 : na));
       if (fwd_done) hipEventRecord(fwd_done, sf);
       from_fwd(1);
       mark(2);
@@ -1259,7 +1290,7 @@ struct SolveRun {
       mark(3);
       launches += shadow ? 3 : 4;
     } else {
-      ks->forward(d, r, P.solver, 0, k1, PH_FWD1, 0, 1, sf, 0, 0);
+      ks->forward(d, r, P.solver, 0, k1, PH_FWD1, 0, 1, sf, 0, 0, roll_slice(k1));
       from_fwd(1);
       mark(2);
       if (!shadow) ks->costate(d, r, P.solver, 0, k1, PH_FWD1, 0, 1, s);
@@ -1273,7 +1304,7 @@ struct SolveRun {
       ks->update(d, r, 1, k1, last, 0, s);
       mark(3);
       to_fwd(2);
-      ks->forward(d, r, P.solver, k1, na - k1, PH_FWD2, 0, 1, sf, 0, 0);
+      ks->forward(d, r, P.solver, k1, na - k1, PH_FWD2, 0, 1, sf, 0, 0, RollSlice());   // (few of its workgroups run: no slicing)
       if (fwd_done) hipEventRecord(fwd_done, sf);
       from_fwd(3);
       mark(4);

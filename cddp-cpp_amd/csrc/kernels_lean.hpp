@@ -758,9 +758,12 @@ __device__ __attribute__((noinline)) RollOut<Model::NX> roll_step_checked(int in
   return o;
 }
 
-template <class Model, class Cons, bool TERM = false, int NC = 1>
-__global__ __launch_bounds__(64 * (1 + NC)) void k_forward_ipddp_pc(DevBuf d, const ProblemDev *__restrict__ Pk, const double *__restrict__ xrt,
-                                                                    int a0, int phase_req, int force, int k1, int poll_us) {
+// The kernel's body.  SL = false: k_forward_ipddp_pc, with the signature it had before round 17 and none of the code below `kSlice`; SL = true:
+// k_forward_ipddp_pc_sl, the same launch with the time-sliced wave priority (slice_ticks, late_from: see kSlice below).
+template <class Model, class Cons, bool TERM, int NC, bool SL>
+__device__ __forceinline__ void forward_ipddp_pc(const DevBuf &d, const ProblemDev *__restrict__ Pk, const double *__restrict__ xrt,
+                                                 int a0, int phase_req, int force, int k1, int poll_us,
+                                                 [[maybe_unused]] const unsigned long long slice_ticks, [[maybe_unused]] const int late_from) {
   constexpr int NX = Model::NX, NU = Model::NU, M = Cons::M;
   typedef Objective<NX, NU> Obj;
   static_assert(M > 0, "two-role rollout is for path-constrained problems");
@@ -860,6 +863,20 @@ __global__ __launch_bounds__(64 * (1 + NC)) void k_forward_ipddp_pc(DevBuf d, co
     return v;
   };
   const int kAbort = 2 * N + kRing;   // s_cons value with which a consumer whose 64 trials have all failed releases AND stops the producer
+  // Time-sliced wave priority (round 17; SL: k_forward_ipddp_pc_sl, the layouts of launch.hpp::PcSlice, launched with slice_ticks != 0).  A launch with more waves than SIMDs puts two
+  // waves on some SIMDs, and the issue arbiter serves the older one first: the first-placed workgroups finish at the pace of a wave alone and
+  // the launch lasts as long as the last-placed (profiles/r03_k4_block_times.md).  Here the two classes -- workgroups below / from the linear
+  // index late_from, the count that gives every SIMD of the stream's CU share one wave -- take priority 3 in alternating windows of the
+  // 100 MHz clock: every wave reads the same clock, so the waves of a SIMD flip at the same instant and one class is favoured per window.
+  // slice_ticks is ONE bit (a power of two): bit k of the clock is the parity of clock / 2^k, and `slice_late` carries the same bit for the
+  // late class, so the favoured test is one AND and one XOR.  A bit the clock never reaches (launch.hpp, kSliceFixedLate) makes it a fixed
+  // priority 3 for the late class (the comparison row of profiles/r17_simd_sharing.md).  Priority is placement in time only: no wait, poll
+  // or flag reads it, HIP promises no dispatch order, and the results are the same bits with any value of either argument.
+  constexpr bool kSlice = SL && NC == 1;   // (&& the role's own kPing, below)
+  [[maybe_unused]] const unsigned long long slice_late = (int)(blockIdx.y * gridDim.x + blockIdx.x) >= late_from ? slice_ticks : 0ull;
+  [[maybe_unused]] auto slice_prio = [&](const unsigned long long clk) {
+    if (((clk & slice_ticks) ^ slice_late) != 0ull) __builtin_amdgcn_s_setprio(3); else __builtin_amdgcn_s_setprio(0);
+  };
 
   if (producer) {
     // ------------------------------------------------------------------ producer: the dynamics chain
@@ -942,7 +959,9 @@ __global__ __launch_bounds__(64 * (1 + NC)) void k_forward_ipddp_pc(DevBuf d, co
     constexpr bool kFlagged = kPing && HasTrigPolicy<Model>::value && NC == 1;
     auto step = [&](auto integ, const int t, StepIn &cs, StepIn &nxt) {
       constexpr int INTEG = decltype(integ)::value;
+      [[maybe_unused]] unsigned long long clk = 0ull;
       if constexpr (kPing) {
+        if constexpr (kSlice) clk = wall_clock64();   // read here, used at the step's end: the ring hand-over's lgkmcnt(0) below has returned it by then
         advance_ld(t);   // unconditional (clamped) prefetch
         load_row(nxt);
       }
@@ -1038,6 +1057,7 @@ __global__ __launch_bounds__(64 * (1 + NC)) void k_forward_ipddp_pc(DevBuf d, co
 #pragma unroll
         for (int i = 0; i < NX; ++i) x[i] = xn[i];
       }
+      if constexpr (kPing && kSlice) slice_prio(clk);
     };
     int t = 0;
     // The step loop, instantiated per integrator (round 10): ONE wave-uniform switch in front of it instead of Stepper::step's tests of
@@ -1152,7 +1172,9 @@ __global__ __launch_bounds__(64 * (1 + NC)) void k_forward_ipddp_pc(DevBuf d, co
   };
   Chunk ck0, ck1;
   auto step = [&](const int t, StepIn &cs, StepIn &nxt) {
+    [[maybe_unused]] unsigned long long clk = 0ull;
     if constexpr (kPing) {
+      if constexpr (kSlice) clk = wall_clock64();   // (see the producer: returned by the ring hand-over's lgkmcnt(0))
       const int tn = t + NC < N ? t + NC : N - 1;   // unconditional (clamped) prefetch: this consumer's next step
       load_step(tn, nxt);
     } else if constexpr (!kEarly && !kChunk) load_step(t, cs);
@@ -1281,6 +1303,7 @@ __global__ __launch_bounds__(64 * (1 + NC)) void k_forward_ipddp_pc(DevBuf d, co
       if (c == 0 && NC == 1) ev_total0 += n1; else ev[(size_t)(Cons::NSEG + c) * kLS] = n1;   // (NC = 2: the first object's terms are parked too)
       ev[(size_t)c * kLS] = ls;
     }
+    if constexpr (kPing && kSlice) slice_prio(clk);
   };
   StepIn ra;
   if constexpr (NC > 1) {
@@ -1447,6 +1470,19 @@ __global__ __launch_bounds__(64 * (1 + NC)) void k_forward_ipddp_pc(DevBuf d, co
   flagged = accept;
   }();
   publish_mask(flagged);
+}
+
+template <class Model, class Cons, bool TERM = false, int NC = 1>
+__global__ __launch_bounds__(64 * (1 + NC)) void k_forward_ipddp_pc(DevBuf d, const ProblemDev *__restrict__ Pk, const double *__restrict__ xrt,
+                                                                    int a0, int phase_req, int force, int k1, int poll_us) {
+  forward_ipddp_pc<Model, Cons, TERM, NC, false>(d, Pk, xrt, a0, phase_req, force, k1, poll_us, 0ull, 0);
+}
+// ... with the time-sliced wave priority: launched instead of the kernel above when a launch oversubscribes its SIMDs (launch.hpp, PcSlice)
+template <class Model, class Cons>
+__global__ __launch_bounds__(128) void k_forward_ipddp_pc_sl(DevBuf d, const ProblemDev *__restrict__ Pk, const double *__restrict__ xrt,
+                                                             int a0, int phase_req, int force, int k1, int poll_us,
+                                                             unsigned long long slice_ticks, int late_from) {
+  forward_ipddp_pc<Model, Cons, false, 1, true>(d, Pk, xrt, a0, phase_req, force, k1, poll_us, slice_ticks, late_from);
 }
 
 #undef GI

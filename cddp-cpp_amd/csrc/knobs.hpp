@@ -25,6 +25,13 @@ struct Knobs {
   bool coop_w1 = env_first("CDDP_HIP_COOP_W") == '1';            // COOP_W=1: the nx > 8 sweep on one wavefront instead of two
   int k4_na = env_num("CDDP_HIP_K4_NA", 1, 1, 3);                // step sizes per rollout workgroup of the small path-constrained layouts
   bool k4_consumers2 = env_first("CDDP_HIP_K4_CONSUMERS") == '2';   // two consumer waves in the IPDDP rollout where instantiated
+  // Time-sliced wave priority of the two-role IPDDP rollout (capi.hip::roll_slice_for; kernels_lean.hpp::k_forward_ipddp_pc_sl, cart-pole and
+  // unicycle layouts).  K4_SLICE_US unset: on the launches whose running waves exceed the SIMDs of the stream's share of the chip, early- and
+  // late-placed workgroups take wave priority 3 in alternating windows of 2.56 us (capi.hip, kK4SliceUs; chosen from the sweep of
+  // profiles/r17_simd_sharing.md section 3: 1.28 / 2.56 / 5.12 / 10.24 / 20.48 us -> 35.68 / 35.59 / 36.21 / 36.74 / 36.80 ms per C2 solve, off 37.11);
+  // 0: off; n: a window of about n us (rounded to a power of two of 10-ns ticks) on every launch (the tests)
+  int k4_slice_us = env_num("CDDP_HIP_K4_SLICE_US", -1, 0, 10000);
+  bool k4_late_prio = env_first("CDDP_HIP_K4_LATE_PRIO") == '1';    // comparison row: a fixed priority 3 for the late-placed workgroups instead of the window
   bool ms_lane_rollout = env_is("CDDP_HIP_MS_ROLLOUT", "lane");  // the one-wave MSIPDDP rollout
   bool lg_lane_rollout = env_is("CDDP_HIP_LG_ROLLOUT", "lane");  // the one-wave LogDDP rollout
   // solve loop (capi.hip::SolveRun)
@@ -33,7 +40,7 @@ struct Knobs {
   int ls_first = env_num("CDDP_HIP_LS_FIRST", 0, INT_MIN, INT_MAX);   // step sizes of stage 1 (used for 1 <= k < ladder length)
   long ls_two_max_waves = env_long("CDDP_HIP_LS_TWO_MAX_WAVES", 768);   // largest first stage (wavefronts) a two-stage ladder keeps
   int ls_small_frac = env_num("CDDP_HIP_LS_SMALL_FRAC", 3, 1, INT_MAX);   // one stage when more than 1 / n of a small ladder is needed
-  int ls_margin = env_num("CDDP_HIP_LS_MARGIN", 1, 0, 8);        // step sizes added to the histogram's first-stage count
+  int ls_margin = env_num("CDDP_HIP_LS_MARGIN", -1, 0, 8);       // step sizes added to the histogram's first-stage count (unset, -1: 0 where both stages run in one rollout launch, else 1)
   bool ls_inkernel = env_first("CDDP_HIP_LS_INKERNEL") != '0';   // LS_INKERNEL=0: a two-stage ladder is always two rollout launches (capi.hip::SolveRun::inkernel_stages)
   int ls_poll_us = env_num("CDDP_HIP_TEST_LS_POLL_US", -1, 0, INT_MAX);   // test hook: the stage-2 poll's give-up bound in microseconds (0: give up at once; unset: kLsPollUs)
   int run_ahead = env_num("CDDP_HIP_RUNAHEAD", 1, 0, 16);        // iterations enqueued behind a poll before the host waits for it

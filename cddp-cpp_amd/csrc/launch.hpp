@@ -48,6 +48,13 @@ struct Route {
   int t4 = 0;              // sub-tile-minor sweep-input stacks (kernels.hpp::GT); the handle's DevBuf::t4
 };
 
+// Time-sliced wave priority of an oversubscribed two-role IPDDP rollout launch (kernels_lean.hpp::k_forward_ipddp_pc_sl; chosen per launch by
+// capi.hip::SolveRun::roll_slice).  ticks: ONE bit of the 100 MHz clock, i.e. the window length as a power of two of 10-ns ticks (0 = off);
+// late_from: the linear workgroup index from which a workgroup counts as late-placed.  kSliceFixedLate as `ticks`: a bit the clock never
+// reaches, which gives the late class a fixed priority 3 (comparison only).
+struct RollSlice { unsigned long long ticks = 0; int late_from = 0; };
+constexpr unsigned long long kSliceFixedLate = 1ull << 62;
+
 struct KernelSet {
   int model, nx, nu, m;
   int cst_size;   // per-step doubles of the condensed-term stack (lean IPDDP backward), 0 = fused sweep
@@ -57,7 +64,7 @@ struct KernelSet {
   Route (*route)(const DevBuf &, int solver, const Knobs &);
   void (*derivs)(const DevBuf &, const Route &, int force, hipStream_t);
   void (*backward)(const DevBuf &, const Route &, int solver, int force, int count_iter, hipStream_t);
-  void (*forward)(const DevBuf &, const Route &, int solver, int a0, int na, int phase_req, int force, int first_only, hipStream_t, int k1, int poll_us);   // k1 > 0: the launch holds both line-search stages, split at step size k1 (two-role IPDDP rollout only)
+  void (*forward)(const DevBuf &, const Route &, int solver, int a0, int na, int phase_req, int force, int first_only, hipStream_t, int k1, int poll_us, RollSlice);   // k1 > 0: the launch holds both line-search stages, split at step size k1 (two-role IPDDP rollout only)
   void (*costate)(const DevBuf &, const Route &, int solver, int a0, int na, int phase_req, int force, int first_only, hipStream_t);
   void (*update)(const DevBuf &, const Route &, int stage, int n1, int is_last, int do_count, hipStream_t);
   void (*init)(const DevBuf &, int mode, hipStream_t);
@@ -80,6 +87,13 @@ template <class Cons> struct PcTwoConsumers<UnicycleModel, Cons> {
   static constexpr int kRec = 5 * Cons::M + UnicycleModel::NU * UnicycleModel::NX + (Cons::HAS_X ? UnicycleModel::NX : 1) + (Cons::NEEDS_U ? UnicycleModel::NU : 1);
   static constexpr bool value = Cons::M >= 4 && kRec > 16 && kRec <= 40;
 };
+
+// Layouts whose two-role rollout also exists with the time-sliced wave priority (k_forward_ipddp_pc_sl; round 17): the ping-pong forms of
+// the two plants it was measured and tested on.  Every other layout runs k_forward_ipddp_pc whatever the launch's size; that kernel keeps
+// its signature, and no instantiation of it changed LDS, scratch or occupancy (profiles/r17_simd_sharing.md section 5).
+template <class Model, class Cons> struct PcSlice { static constexpr bool value = false; };
+template <class Cons> struct PcSlice<CartPoleModel, Cons> { static constexpr bool value = Cons::M > 0; };
+template <class Cons> struct PcSlice<UnicycleModel, Cons> { static constexpr bool value = Cons::M > 0; };
 
 template <class Model, class Cons, bool TERM = false>
 struct Launcher {
@@ -307,7 +321,7 @@ struct Launcher {
       hipLaunchKernelGGL((k_backward_ipddp<Model, Cons, TERM>), gridB(d), dim3(64), 0, s, d, d.P, d.xref_traj, force, count_iter);
     }
   }
-  static void forward(const DevBuf &d, const Route &r, int solver, int a0, int na, int phase_req, int force, int first_only, hipStream_t s, int k1 = 0, int poll_us = 0) {
+  static void forward(const DevBuf &d, const Route &r, int solver, int a0, int na, int phase_req, int force, int first_only, hipStream_t s, int k1 = 0, int poll_us = 0, RollSlice sl = RollSlice()) {
     if (na <= 0) return;
     const dim3 grid((d.B + 63) / 64, na);
     if (solver == CDDP_HIP_SOLVER_LOGDDP) {
@@ -338,6 +352,9 @@ struct Launcher {
         // producer / consumer wave pair per (tile, alpha); CDDP_HIP_K4_CONSUMERS=2: two consumers where instantiated (opt-in, see route())
         if constexpr (PcTwoConsumers<Model, Cons>::value) {
           if (r.rollout == Route::kTwoConsumers) { hipLaunchKernelGGL((k_forward_ipddp_pc<Model, Cons, false, 2>), grid, dim3(192), 0, s, d, d.P, d.xref_traj, a0, phase_req, force, k1, poll_us); return; }
+        }
+        if constexpr (PcSlice<Model, Cons>::value) {   // an oversubscribed launch: the same kernel with the time-sliced wave priority
+          if (sl.ticks != 0ull) { hipLaunchKernelGGL((k_forward_ipddp_pc_sl<Model, Cons>), grid, dim3(128), 0, s, d, d.P, d.xref_traj, a0, phase_req, force, k1, poll_us, sl.ticks, sl.late_from); return; }
         }
         hipLaunchKernelGGL((k_forward_ipddp_pc<Model, Cons>), grid, dim3(128), 0, s, d, d.P, d.xref_traj, a0, phase_req, force, k1, poll_us);
       } else {
