@@ -17,6 +17,7 @@
 #include "plant.hpp"
 #include "io_kernels.hpp"
 #include "sens_kernels.hpp"
+#include "cov_kernels.hpp"
 #include "score_kernels.hpp"
 #include "mppi_kernels.hpp"
 
@@ -2351,6 +2352,59 @@ int cddp_hip_plan_vjp(cddp_hip_handle *h, int flags, int nvec, const double *gX,
   HIPCHK(hipGetLastError());
   for (Inner *q : h->g) HIPCHK(hipStreamSynchronize(q->stream));
   HIPCHK(hipMemcpy(gx0, t0.p, B * n0 * sizeof(double), hipMemcpyDeviceToHost));
+  return join_to_user(h);
+}
+
+// ---- state and control covariance along the plan (inst_cov.hip): the closed-loop covariance recursion over the A / Bm / K stacks ----
+int cddp_hip_plan_covariance(cddp_hip_handle *h, int flags, const double *Sigma0, const double *W, const double *Wu, double *SX, double *SU, double *dcost) {
+  static const char *const me = "cddp_hip_plan_covariance";
+  constexpr int known = CDDP_HIP_COV_DEVICE | CDDP_HIP_COV_DIAG | CDDP_HIP_COV_PER_TRAJ;
+  if (!h) return fail(-1, "%s: null handle", me);
+  if (flags & ~known) return fail(-2, "%s: unknown flag bits 0x%x (CDDP_HIP_COV_DEVICE, CDDP_HIP_COV_DIAG and CDDP_HIP_COV_PER_TRAJ are the flags)", me, (unsigned)(flags & ~known));
+  if (!Sigma0) return fail(-1, "%s: null Sigma0 pointer", me);
+  if (!SX && !SU && !dcost) return fail(-1, "%s: SX, SU and dcost are all null: nothing to compute", me);
+  { int rc = sens_refuse_handle(me, h); if (rc) return rc; }
+  HIPCHK(hipSetDevice(h->device));
+  const bool dev = (flags & CDDP_HIP_COV_DEVICE) != 0, diag = (flags & CDDP_HIP_COV_DIAG) != 0, per = (flags & CDDP_HIP_COV_PER_TRAJ) != 0;
+  const size_t nx = (size_t)h->nx, nu = (size_t)h->nu, B = (size_t)h->B;
+  const size_t nS = (per ? B : 1) * nx * nx, nWu = (per ? B : 1) * nu * nu;                       // doubles of Sigma0 / W, of Wu
+  const size_t eX = (size_t)(h->N + 1) * (diag ? nx : nx * nx), eU = (size_t)h->N * (diag ? nu : nu * nu);   // doubles per trajectory of SX, of SU
+  SensTmp t0, tW, tWu, tX, tU, tc;
+  const double *S0d = Sigma0, *Wd = W, *Wud = Wu; double *SXd = SX, *SUd = SU, *dcd = dcost;
+  if (dev) {
+    { int rc = io_check_pointer(h, Sigma0, nS * sizeof(double), me, "Sigma0"); if (rc) return rc; }
+    if (W) { int rc = io_check_pointer(h, W, nS * sizeof(double), me, "W"); if (rc) return rc; }
+    if (Wu) { int rc = io_check_pointer(h, Wu, nWu * sizeof(double), me, "Wu"); if (rc) return rc; }
+    if (SX) { int rc = io_check_pointer(h, SX, B * eX * sizeof(double), me, "SX"); if (rc) return rc; }
+    if (SU) { int rc = io_check_pointer(h, SU, B * eU * sizeof(double), me, "SU"); if (rc) return rc; }
+    if (dcost) { int rc = io_check_pointer(h, dcost, B * sizeof(double), me, "dcost"); if (rc) return rc; }
+  } else {
+    { int rc = t0.alloc(nS); if (rc) return rc; }
+    HIPCHK(hipMemcpy(t0.p, Sigma0, nS * sizeof(double), hipMemcpyHostToDevice)); S0d = t0.p;
+    if (W) { int rc = tW.alloc(nS); if (rc) return rc; HIPCHK(hipMemcpy(tW.p, W, nS * sizeof(double), hipMemcpyHostToDevice)); Wd = tW.p; }
+    if (Wu) { int rc = tWu.alloc(nWu); if (rc) return rc; HIPCHK(hipMemcpy(tWu.p, Wu, nWu * sizeof(double), hipMemcpyHostToDevice)); Wud = tWu.p; }
+    if (SX) { int rc = tX.alloc(B * eX); if (rc) return rc; SXd = tX.p; }
+    if (SU) { int rc = tU.alloc(B * eU); if (rc) return rc; SUd = tU.p; }
+    if (dcost) { int rc = tc.alloc(B); if (rc) return rc; dcd = tc.p; }
+  }
+  { int rc = fork_from_user(h); if (rc) return rc; }
+  for (size_t gi = 0; gi < h->g.size(); ++gi) {
+    const Inner *q = h->g[gi];
+    const size_t b0 = (size_t)h->b0[gi], p0 = per ? b0 : 0;
+    const double *pool = (const double *)((const char *)q->dP + offsetof(ProblemDev, pool));
+    CovArgs a;
+    a.Sigma0 = S0d + p0 * nx * nx; a.W = Wd ? Wd + p0 * nx * nx : nullptr; a.Wu = Wud ? Wud + p0 * nu * nu : nullptr;
+    a.SX = SXd ? SXd + b0 * eX : nullptr; a.SU = SUd ? SUd + b0 * eU : nullptr; a.dcost = dcd ? dcd + b0 : nullptr;
+    a.Qdt = pool + q->P.off_Qdt; a.Rdt = pool + q->P.off_Rdt; a.Qf = pool + q->P.off_Qf;
+    a.per_traj = per ? 1 : 0; a.diag = diag ? 1 : 0;
+    HIPCHK(plan_cov(sens_stacks(q), a, q->stream));
+  }
+  if (dev) return io_finish(h);
+  HIPCHK(hipGetLastError());
+  for (Inner *q : h->g) HIPCHK(hipStreamSynchronize(q->stream));
+  if (SX) HIPCHK(hipMemcpy(SX, tX.p, B * eX * sizeof(double), hipMemcpyDeviceToHost));
+  if (SU) HIPCHK(hipMemcpy(SU, tU.p, B * eU * sizeof(double), hipMemcpyDeviceToHost));
+  if (dcost) HIPCHK(hipMemcpy(dcost, tc.p, B * sizeof(double), hipMemcpyDeviceToHost));
   return join_to_user(h);
 }
 

@@ -885,6 +885,16 @@ class HipBatchSolver : public ISolverAlgorithm {
     if (!h_) throw std::runtime_error("cddp_hip: planVjp needs a resident batch (the plug-in route has no resident handle)");
     check(cddp_hip_plan_vjp(h_, flags, nvec, gX, gU, gx0));
   }
+  // NEW: covariance of the resident batch's states and controls under the plans' own feedback gains, and the expected increase of the
+  // quadratic objective (cddp_hip_plan_covariance), over the stacks of the last backward sweep.  flags: CDDP_HIP_COV_DEVICE (device pointers
+  // of the solver's device), CDDP_HIP_COV_DIAG (diagonals only), CDDP_HIP_COV_PER_TRAJ (Sigma0, W and Wu per trajectory).  W or Wu nullptr:
+  // no such noise; any output nullptr, not all.
+  void planCovariance(int flags, const double *Sigma0 /* nx*nx | batch*nx*nx */, const double *W /* as Sigma0, or nullptr */,
+                      const double *Wu /* nu*nu | batch*nu*nu, or nullptr */, double *SX /* batch*(N+1)*nx*nx (DIAG: batch*(N+1)*nx) */,
+                      double *SU /* batch*N*nu*nu (DIAG: batch*N*nu) */, double *dcost /* batch */) {
+    if (!h_) throw std::runtime_error("cddp_hip: planCovariance needs a resident batch (the plug-in route has no resident handle)");
+    check(cddp_hip_plan_covariance(h_, flags, Sigma0, W, Wu, SX, SU, dcost));
+  }
   // NEW: what ncand candidate control sequences per trajectory are worth, in one launch (cddp_hip_score_rollouts), and the seed taken from
   // the best of them (cddp_hip_seed_best).  Arrays are [batch][ncand][t][e]; flags: CDDP_HIP_SCORE_DEVICE (device pointers of the solver's
   // device), CDDP_HIP_SCORE_FEEDBACK (u = U + K_t (x - X_t) around the live plan, U may then be nullptr), CDDP_HIP_SCORE_X0_PER_CANDIDATE.

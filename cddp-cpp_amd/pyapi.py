@@ -167,6 +167,8 @@ MPC_KEEP_PLAN, MPC_SHIFT_EXISTING, MPC_SHIFT_PROVIDED = 0, 1, 2
 MPC_SHIFT_DUALS, MPC_X_DEVICE = 1, 2
 # cddp_hip_plan_jvp / cddp_hip_plan_vjp (include/cddp_hip.h, "linear response of a solved plan to its initial state")
 SENS_DEVICE = 1
+# cddp_hip_plan_covariance (include/cddp_hip.h, "state and control covariance along a solved plan")
+COV_DEVICE, COV_DIAG, COV_PER_TRAJ = 1, 2, 4
 # cddp_hip_score_rollouts / cddp_hip_seed_best (include/cddp_hip.h, "scoring candidate control sequences and seeding from the best")
 SCORE_DEVICE = 1
 SCORE_FEEDBACK = 2
@@ -837,6 +839,7 @@ DEVICE_IO_ARGTYPES = {
     # (host or device addresses, by the flag: plain pointer values)
     "cddp_hip_plan_jvp": [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
     "cddp_hip_plan_vjp": [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
+    "cddp_hip_plan_covariance": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
     "cddp_hip_score_rollouts": [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
     "cddp_hip_seed_best": [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p],
     "cddp_hip_sample_controls": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
@@ -858,7 +861,7 @@ EXPORTED_SYMBOLS = [
     "cddp_hip_costate_mode", "cddp_hip_costate_redos", "cddp_hip_ls_stage_counts", "cddp_hip_mpc_advance", "cddp_hip_mpc_run",
     "cddp_hip_plant_create", "cddp_hip_plant_destroy", "cddp_hip_plant_step", "cddp_hip_mpc_run_plant", "cddp_hip_track_plan",
     "cddp_hip_field_shape", "cddp_hip_get_field_device", "cddp_hip_get_results_device", "cddp_hip_set_initial_device", "cddp_hip_get_live_slots",
-    "cddp_hip_plan_jvp", "cddp_hip_plan_vjp",
+    "cddp_hip_plan_jvp", "cddp_hip_plan_vjp", "cddp_hip_plan_covariance",
     "cddp_hip_score_rollouts", "cddp_hip_seed_best",
     "cddp_hip_sample_controls", "cddp_hip_mppi_blend", "cddp_hip_mppi_refine",
 ]
@@ -1307,6 +1310,50 @@ class HipBatchSolver:
         eye = torch.eye(nx, dtype=torch.float64, device=self._torch_device()).expand(self.B, nx, nx).contiguous()
         dX, dU = self.plan_jvp(eye)
         return dX.permute(0, 2, 3, 1).contiguous(), dU.permute(0, 2, 3, 1).contiguous()
+
+    # ---- state and control covariance along the plan (cddp_hip_plan_covariance): numpy arrays take the host path, torch.float64 tensors on
+    # the handle's device the device path; every argument of a call is of one kind, and so is the result
+    def plan_covariance(self, Sigma0, W=None, Wu=None, diag=False, want=("SX", "SU", "dcost")):
+        """Covariance of the plan's states and controls under its own feedback gains (cddp_hip_plan_covariance): Sigma_{t+1} = Acl_t Sigma_t
+        Acl_t^T + W + B_t Wu B_t^T with Acl_t = A_t + B_t K_t over the stacks of the last backward sweep, cov(du_t) = K_t Sigma_t K_t^T + Wu,
+        and the expected increase of the quadratic objective.  Sigma0: (nx, nx) for the whole batch or (B, nx, nx) per trajectory; W
+        (process noise) and Wu (actuator noise, nu x nu) are None or of Sigma0's kind and batching.  Only the lower triangles are read.
+        numpy arrays or torch.float64 tensors on the handle's device.  Returns a dict of Sigma0's kind with the entries `want` names: "SX"
+        (B, N + 1, nx, nx), "SU" (B, N, nu, nu) -- diag=True: their diagonals, (B, N + 1, nx) and (B, N, nu) -- and "dcost" (B,).  The
+        handle's state is not modified."""
+        want = tuple(want)
+        if not want or any(w not in ("SX", "SU", "dcost") for w in want):
+            raise ValueError("want: a non-empty subset of ('SX', 'SU', 'dcost') is expected, got %r" % (want,))
+        if Sigma0 is None:
+            raise ValueError("plan_covariance: Sigma0 is None")
+        N, nx, nu, B = self.p.N, self.p.nx, self.p.nu, self.B
+        device = hasattr(Sigma0, "data_ptr") and not isinstance(Sigma0, np.ndarray)
+        if not device:
+            if isinstance(Sigma0, np.ndarray) and Sigma0.dtype != np.float64:
+                raise ValueError("plan_covariance: Sigma0: dtype float64 is expected, got %s" % Sigma0.dtype)
+            Sigma0 = np.ascontiguousarray(Sigma0, dtype=np.float64)      # (a list, as the other arguments may be)
+        ndim = len(tuple(Sigma0.shape))
+        if ndim not in (2, 3):
+            raise ValueError("plan_covariance: Sigma0: shape %s or %s is expected, got %s" % ((nx, nx), (B, nx, nx), tuple(Sigma0.shape)))
+        per = ndim == 3
+        lead = (B,) if per else ()
+        args = []
+        for name, a, n in (("Sigma0", Sigma0, nx), ("W", W, nx), ("Wu", Wu, nu)):
+            args.append(None if a is None else self._score_arg("plan_covariance", name, a, (lead + (n, n),), device))
+        s0, w, wu = args
+        flags = (COV_DEVICE if device else 0) | (COV_DIAG if diag else 0) | (COV_PER_TRAJ if per else 0)
+        shapes = {"SX": (B, N + 1, nx) if diag else (B, N + 1, nx, nx), "SU": (B, N, nu) if diag else (B, N, nu, nu), "dcost": (B,)}
+        if device:
+            import torch
+            dev = self._torch_device()
+            out = {k: torch.empty(shapes[k], dtype=torch.float64, device=dev) for k in want}
+            self._order_device_io()
+            ptr = lambda a: a.data_ptr() if a is not None else None
+        else:
+            out = {k: np.zeros(shapes[k]) for k in want}
+            ptr = lambda a: a.ctypes.data if a is not None else None
+        self._check(self.lib.cddp_hip_plan_covariance(self.h, flags, ptr(s0), ptr(w), ptr(wu), ptr(out.get("SX")), ptr(out.get("SU")), ptr(out.get("dcost"))))
+        return out
 
     # ---- scoring candidate control sequences and seeding from the best (cddp_hip_score_rollouts / cddp_hip_seed_best): numpy arrays take
     # the host path, torch.float64 tensors on the handle's device the device path; every argument of a call is of one kind

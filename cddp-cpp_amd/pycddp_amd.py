@@ -1187,6 +1187,51 @@ class CDDP:                         # cddp_core.hpp:214-423 / bind_solver.cpp:57
         out["solve_time_ms"] = float(st.solve_ms)
         return out
 
+    def solve_batch_cov(self, x0s, Sigma0, W=None, Wu=None, U0=None, X0=None, solver_type=SolverType.IPDDP, diag=False, want=("X", "U")):
+        """NEW (no reference counterpart): solve_batch_device, then the covariance of the solved plans under their own feedback gains
+        (cddp_hip_plan_covariance).  Sigma0: (nx, nx) or (B, nx, nx), the covariance of the initial state; W (nx x nx, process noise) and
+        Wu (nu x nu, actuator noise): None or batched as Sigma0 -- torch.float64, contiguous, on cuda:0.  Returns what solve_batch_device
+        returns, plus "SX" (B, N + 1, nx, nx), "SU" (B, N, nu, nu) (diag=True: the diagonals) and "expected_cost_increase" (B,).  The
+        linearisation is that of the last backward sweep, about the iterate before the last accepted step."""
+        import torch
+        api = _api()
+        name = solver_type.value if isinstance(solver_type, SolverType) else str(solver_type)
+        want = tuple(want)
+        unknown = [w for w in want if w not in api.FIELD_IDS]
+        if unknown:
+            raise ValueError("want: unknown fields %s (known: %s)" % (unknown, ", ".join(api.FIELD_NAMES)))
+        if self._sys is None:
+            raise RuntimeError("Dynamical system must be set before solving.")
+        kind = self._resident_kind(name)
+        if kind is None:
+            raise NotImplementedError("solve_batch_cov needs a problem of the resident route (built-in plant, objective and constraints): "
+                                      "solver '%s' with this problem runs on the plug-in route, which has no resident handle" % name)
+        if not isinstance(x0s, torch.Tensor) or x0s.dim() != 2:
+            raise ValueError("x0s: a (B, nx) torch tensor is expected")
+        if not isinstance(Sigma0, torch.Tensor):
+            raise ValueError("Sigma0: a (nx, nx) or (B, nx, nx) torch tensor is expected")
+        B = int(x0s.shape[0])
+        if B <= 0:
+            raise ValueError("x0s: an empty batch")
+        if U0 is None and self._U is not None and x0s.is_cuda:     # (the seed of set_initial_trajectory, as solve_batch_device takes it)
+            U0 = torch.as_tensor(np.ascontiguousarray(self._U, dtype=np.float64), device=x0s.device).expand(B, -1, -1).contiguous()
+        if X0 is None and self._X is not None and x0s.is_cuda:
+            X0 = torch.as_tensor(np.ascontiguousarray(self._X, dtype=np.float64), device=x0s.device).expand(B, -1, -1).contiguous()
+        p = self._problem(kind)
+        hs = api.HipBatchSolver(p, B)
+        try:
+            hs.set_initial_device(x0s, U0, X0)        # (shape, dtype, contiguity and device are checked there: ValueError)
+            st = hs.solve()
+            cov = hs.plan_covariance(Sigma0, W, Wu, diag=diag)
+            out = {w: hs.field_device(w) for w in want}
+            res = hs.results_device()
+        finally:
+            hs.close()
+        out["results"] = {k: v for k, v in res.items() if k not in ("cols", "icols")}
+        out["solve_time_ms"] = float(st.solve_ms)
+        out["SX"] = cov["SX"]; out["SU"] = cov["SU"]; out["expected_cost_increase"] = cov["dcost"]
+        return out
+
     def solve_batch_sampled(self, x0s, U_candidates, solver_type=SolverType.IPDDP, viol_tol=0.0, want=("X", "U")):
         """NEW (no reference counterpart): solve_batch_device started from the best of S candidate control sequences per trajectory
         (cddp_hip_score_rollouts, cddp_hip_seed_best): every candidate is rolled out on the device in one launch, the admissible one

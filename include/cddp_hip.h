@@ -668,6 +668,52 @@ int cddp_hip_plan_vjp(cddp_hip_handle *h, int flags, int nvec,
                       const double *gU /* B*nvec*N*nu or NULL = zeros */,
                       double *gx0 /* B*nvec*nx */);
 
+/* ---- state and control covariance along a solved plan ----------------------
+ * Given an uncertain initial state, process noise and actuator noise, how uncertain are the states and controls of the plan under its own
+ * feedback gains, and what does that uncertainty cost?  The perturbation follows dx_{t+1} = (A_t + B_t K_t) dx_t + B_t eps_t + w_t with
+ * cov(dx_0) = Sigma0, cov(w_t) = W, cov(eps_t) = Wu, white in time.  cddp_hip_plan_covariance runs the covariance recursion on the device
+ * over the stacks where the sweep left them (csrc/inst_cov.hip: one workgroup per 64-trajectory tile, Sigma_t in LDS): no stack is copied or
+ * un-tiled.  SX rows are Sigma_0 .. Sigma_N, SU rows cov(du_t) = K_t Sigma_t K_t^T + Wu for t = 0 .. N-1, and dcost is the expected increase
+ * of the quadratic objective under that uncertainty, sum_t tr(Q dt Sigma_t) + tr(R dt SU_t), plus tr(Qf Sigma_N) (the objective has no 1/2).
+ * WHICH SWEEP: K_t, A_t, B_t are the stacks cddp_hip_get_gains and cddp_hip_get_linearization read at the time of the call.  They belong to
+ * the LAST BACKWARD SWEEP, which ran at the iterate BEFORE the last accepted step, not at the returned plan; at a converged solve the
+ * difference is of the size of the last step.  A caller who wants them at the returned plan calls cddp_hip_backward first.
+ * Arrays: batch-major, contiguous doubles, matrices row-major.  Sigma0, W and Wu are ONE matrix each for the whole batch (nx*nx, nx*nx,
+ * nu*nu), or with CDDP_HIP_COV_PER_TRAJ one per trajectory, all three together (B*nx*nx, B*nx*nx, B*nu*nu); W and Wu may be NULL (no such
+ * noise).  SX is [b][t][i][j] and SU [b][t][i][j]; with CDDP_HIP_COV_DIAG only the diagonals are written, SX [b][t][i] and SU [b][t][i]
+ * (the recursion itself is the full one).  Any output may be NULL, not all.
+ * flags without CDDP_HIP_COV_DEVICE: host pointers; the call uploads, computes, downloads and returns when the outputs are written.
+ * CDDP_HIP_COV_DEVICE: every array argument is a device pointer of the handle's device, checked and ordered as cddp_hip_plan_jvp checks
+ * and orders its own; a handle of several tile groups offsets the pointers per group.  The handle's state is not modified.
+ * Arithmetic (the library is built with -ffp-contract=off: every product is rounded before it is added).  Every sum starts at the stated
+ * value and runs with the index ascending, so the result does not depend on how the work is spread over lanes.  Only the lower triangle
+ * (j <= i) of Sigma0, W and Wu is read: element [i][j] with j > i stands for element [j][i] wherever it appears below.  Every covariance
+ * is computed for j <= i and mirrored, so the outputs are exactly symmetric.  Sigma_0 = Sigma0 (mirrored).  Per trajectory, for
+ * t = 0 .. N-1:
+ *  1. Acl[i][j]: s = A_t[i][j]; for k ascending s += B_t[i][k] * K_t[k][j].
+ *  2. Z[i][j] (nu x nx): s = 0; for l ascending s += K_t[i][l] * Sigma_t[l][j].
+ *  3. SU_t[i][j]: s = 0; for l ascending s += Z[i][l] * K_t[j][l]; then s += Wu[i][j] if Wu is given.
+ *  4. Y[i][j]: s = 0; for l ascending s += Acl[i][l] * Sigma_t[l][j].
+ *  5. Sigma_{t+1}[i][j]: s = 0; for l ascending s += Acl[i][l] * Y[j][l].  If W is given: s += W[i][j].  If Wu is given: G[i][k]:
+ *     g = 0; for m ascending g += B_t[i][m] * Wu[m][k]; then h = 0; for k ascending h += G[i][k] * B_t[j][k]; s += h.
+ *  6. the cost of step t: r_i = 0; for j ascending r_i += Qdt[i][j] * Sigma_t[i][j] (Qdt = Q * dt, as the solver holds it); c = 0; for i
+ *     ascending c += r_i; then the same with Rdt = R * dt and SU_t, for i ascending added on the same c; dcost += c, with t ascending
+ *     from dcost = 0.
+ * After the loop the term of Qf and Sigma_N is formed the same way (r_i, then c from 0) and added last.
+ * Non-finite stack rows propagate; nothing is special-cased.  (The sign of an exact zero is not specified.)
+ * Refused before anything is launched, each with its own message, nothing changed: a NULL handle, unknown flag bits, a NULL Sigma0, SX, SU
+ * and dcost all NULL, a handle that was never solved or swept, an MSIPDDP handle (its plan carries defects and its gains belong to the
+ * gap-closing recursion, so this recursion is not its response), and with CDDP_HIP_COV_DEVICE a pointer cddp_hip_get_field_device would
+ * refuse.  (New entry point; ABI version unchanged.) */
+enum { CDDP_HIP_COV_DEVICE = 1, CDDP_HIP_COV_DIAG = 2, CDDP_HIP_COV_PER_TRAJ = 4 };
+int cddp_hip_plan_covariance(cddp_hip_handle *h, int flags,
+                             const double *Sigma0 /* nx*nx, or B*nx*nx with PER_TRAJ */,
+                             const double *W      /* process noise, nx*nx | B*nx*nx, or NULL */,
+                             const double *Wu     /* actuator noise, nu*nu | B*nu*nu, or NULL */,
+                             double *SX    /* B*(N+1)*nx*nx (DIAG: B*(N+1)*nx) or NULL */,
+                             double *SU    /* B*N*nu*nu     (DIAG: B*N*nu)     or NULL */,
+                             double *dcost /* B or NULL */);
+
 /* ---- scoring candidate control sequences and seeding from the best -----------
  * The plan a nonconvex solve ends in depends on the control sequence it starts from.  cddp_hip_score_rollouts rolls S candidate control
  * sequences per trajectory out in ONE launch (csrc/inst_score.hip, one lane per trajectory and candidate) and returns what each is worth:
