@@ -20,6 +20,7 @@
 #include "cov_kernels.hpp"
 #include "score_kernels.hpp"
 #include "mppi_kernels.hpp"
+#include "mc_kernels.hpp"
 
 // 1 when a[0] > a[1] > ... > a[n - 1] (NaN-free): the ladders cddp_hip_build_alphas makes; DevBuf::ladder_sorted
 static int ladder_strictly_decreasing(const double *a, int n) {
@@ -3020,6 +3021,139 @@ int cddp_hip_mppi_refine(cddp_hip_handle *h, cddp_hip_plant *plant, int flags, c
   if (cost_out) HIPCHK(hipMemcpy(cost_out, costd, B * S * sizeof(double), hipMemcpyDeviceToHost));
   if (viol_out) HIPCHK(hipMemcpy(viol_out, viold, B * S * sizeof(double), hipMemcpyDeviceToHost));
   if (stats) HIPCHK(hipMemcpy(stats, std_, B * 3 * sizeof(double), hipMemcpyDeviceToHost));
+  return join_to_user(h);
+}
+
+// ---- Monte-Carlo evaluation of a solved plan under noise (inst_mc.hip): noise drawn in the kernel, sums over the samples of csrc/plan_mc.hpp ----
+// The refusals the two entries share, in the order of the header: those that read nothing of the handle first.  Fills the draw and the factors.
+static int mc_refuse(const char *me, const cddp_hip_handle *h, int flags, int known, const cddp_hip_mc_desc *desc, McArgs *a, McFactors *f) {
+  if (!h) return fail(-1, "%s: null handle", me);
+  if (!desc) return fail(-1, "%s: null descriptor", me);
+  if (flags & ~known) return fail(-2, "%s: unknown flag bits 0x%x", me, (unsigned)(flags & ~known));
+  if (desc->nsamp < 1) return fail(-2, "%s: nsamp = %d, at least one sample is needed", me, desc->nsamp);
+  if (desc->nsamp > kMcMaxSamples) return fail(-2, "%s: nsamp = %d, one workgroup holds at most %d samples of a trajectory", me, desc->nsamp, kMcMaxSamples);
+  if (desc->viol_tol != desc->viol_tol) return fail(-2, "%s: viol_tol is NaN", me);
+  const int nx = h->nx, nu = h->nu;
+  if (nx > kMcMaxNx || nu > kMcMaxNu) return fail(-3, "%s: nx = %d, nu = %d, the sampling kernels hold at most %d states and %d controls", me, nx, nu, kMcMaxNx, kMcMaxNu);
+  std::memset(a, 0, sizeof(*a));
+  std::memset(f, 0, sizeof(*f));
+  const struct { const double *L; int n; double *out; const char *name; } fac[3] = {{desc->L0, nx, f->l0, "L0"}, {desc->Lw, nx, f->lw, "Lw"}, {desc->Lu, nu, f->lu, "Lu"}};
+  for (const auto &m : fac) {
+    if (!m.L) continue;
+    for (int i = 0; i < m.n; ++i)
+      for (int j = 0; j <= i; ++j) {
+        const double v = m.L[i * m.n + j];
+        if (!std::isfinite(v)) return fail(-2, "%s: %s[%d][%d] = %g is not finite", me, m.name, i, j, v);
+        m.out[i * (i + 1) / 2 + j] = v;
+      }
+  }
+  a->seed = desc->seed; a->stream = desc->stream; a->S = desc->nsamp; a->keep_nominal = desc->keep_nominal ? 1 : 0; a->viol_tol = desc->viol_tol;
+  a->have0 = desc->L0 ? 1 : 0; a->havew = desc->Lw ? 1 : 0; a->haveu = desc->Lu ? 1 : 0;
+  return 0;
+}
+
+int cddp_hip_mc_sample_noise(cddp_hip_handle *h, int flags, const cddp_hip_mc_desc *desc, double *Z0, double *E, double *Wn) {
+  static const char *const me = "cddp_hip_mc_sample_noise";
+  McArgs a;
+  McFactors f;
+  { int rc = mc_refuse(me, h, flags, CDDP_HIP_MC_DEVICE, desc, &a, &f); if (rc) return rc; }
+  if (!Z0 && !E && !Wn) return fail(-1, "%s: Z0, E and Wn are all NULL: there is nothing to write", me);
+  const bool dev = (flags & CDDP_HIP_MC_DEVICE) != 0;
+  const size_t B = (size_t)h->B, S = (size_t)desc->nsamp, nx = (size_t)h->nx, nu = (size_t)h->nu, N = (size_t)h->N;
+  const size_t n0 = S * nx, nE = S * N * nu, nW = S * N * nx;   // per trajectory
+  HIPCHK(hipSetDevice(h->device));
+  double *Zd = Z0, *Ed = E, *Wd = Wn;
+  if (dev) {
+    if (Z0) { int rc = io_check_pointer(h, Z0, B * n0 * sizeof(double), me, "Z0"); if (rc) return rc; }
+    if (E) { int rc = io_check_pointer(h, E, B * nE * sizeof(double), me, "E"); if (rc) return rc; }
+    if (Wn) { int rc = io_check_pointer(h, Wn, B * nW * sizeof(double), me, "Wn"); if (rc) return rc; }
+  } else {
+    { int rc = score_scratch(h, B * ((Z0 ? n0 : 0) + (E ? nE : 0) + (Wn ? nW : 0))); if (rc) return rc; }
+    double *top = h->d_score;
+    if (Z0) { Zd = top; top += B * n0; }
+    if (E) { Ed = top; top += B * nE; }
+    if (Wn) { Wd = top; top += B * nW; }
+  }
+  { int rc = fork_from_user(h); if (rc) return rc; }
+  for (size_t gi = 0; gi < h->g.size(); ++gi) {
+    const Inner *q = h->g[gi];
+    const size_t b0 = (size_t)h->b0[gi];
+    a.b0 = (int)b0;
+    HIPCHK(mc_noise_launch(a, f, q->d.B, h->N, h->nx, h->nu, Zd ? Zd + b0 * n0 : nullptr, Ed ? Ed + b0 * nE : nullptr, Wd ? Wd + b0 * nW : nullptr, q->stream));
+  }
+  if (dev) return io_finish(h);
+  HIPCHK(hipGetLastError());
+  for (Inner *q : h->g) HIPCHK(hipStreamSynchronize(q->stream));
+  if (Z0) HIPCHK(hipMemcpy(Z0, Zd, B * n0 * sizeof(double), hipMemcpyDeviceToHost));
+  if (E) HIPCHK(hipMemcpy(E, Ed, B * nE * sizeof(double), hipMemcpyDeviceToHost));
+  if (Wn) HIPCHK(hipMemcpy(Wn, Wd, B * nW * sizeof(double), hipMemcpyDeviceToHost));
+  return join_to_user(h);
+}
+
+int cddp_hip_plan_montecarlo(cddp_hip_handle *h, cddp_hip_plant *plant, int flags, const cddp_hip_mc_desc *desc, const double *x0, double *cost, double *viol,
+                             double *stats, int32_t *nviol_step, double *dXmean, double *SX, double *dUmean, double *SU, double *X_out, double *U_out) {
+  static const char *const me = "cddp_hip_plan_montecarlo";
+  McArgs a;
+  McFactors f;
+  { int rc = mc_refuse(me, h, flags, CDDP_HIP_MC_DEVICE | CDDP_HIP_MC_DIAG, desc, &a, &f); if (rc) return rc; }
+  if (!cost && !viol && !stats && !nviol_step && !dXmean && !SX && !dUmean && !SU && !X_out && !U_out) return fail(-1, "%s: every output is NULL: there is nothing to write", me);
+  if (h->g[0]->P.solver == CDDP_HIP_SOLVER_MSIPDDP)
+    return fail(-1, "%s: not for an MSIPDDP handle: its plan carries defects and its gains belong to the gap-closing recursion, so they are no tracking policy", me);
+  { int rc = plan_tracked(me, h); if (rc) return rc; }
+  if (plant) { int rc = plant_fits(me, h, plant); if (rc) return rc; }
+  const bool dev = (flags & CDDP_HIP_MC_DEVICE) != 0, diag = (flags & CDDP_HIP_MC_DIAG) != 0;
+  a.diag = diag ? 1 : 0;
+  const size_t B = (size_t)h->B, S = (size_t)desc->nsamp, nx = (size_t)h->nx, nu = (size_t)h->nu, N = (size_t)h->N;
+  // doubles per trajectory of every double output, in the order of the argument list
+  const size_t nSX = (N + 1) * nx * (diag ? 1 : nx), nSU = N * nu * (diag ? 1 : nu), nXo = S * (N + 1) * nx, nUo = S * N * nu, nCnt = N + 1;
+  double *outs[9] = {cost, viol, stats, dXmean, SX, dUmean, SU, X_out, U_out};
+  const size_t per[9] = {S, S, 8, (N + 1) * nx, nSX, N * nu, nSU, nXo, nUo};
+  static const char *const names[9] = {"cost", "viol", "stats", "dXmean", "SX", "dUmean", "SU", "X_out", "U_out"};
+  HIPCHK(hipSetDevice(h->device));
+  const double *x0d = x0;
+  double *od[9];
+  int32_t *cntd = nviol_step;
+  for (int i = 0; i < 9; ++i) od[i] = outs[i];
+  if (dev) {
+    if (x0) { int rc = io_check_pointer(h, x0, B * nx * sizeof(double), me, "x0"); if (rc) return rc; }
+    for (int i = 0; i < 9; ++i) if (outs[i]) { int rc = io_check_pointer(h, outs[i], B * per[i] * sizeof(double), me, names[i]); if (rc) return rc; }
+    if (nviol_step) { int rc = io_check_pointer(h, nviol_step, B * nCnt * sizeof(int32_t), me, "nviol_step"); if (rc) return rc; }
+  } else {
+    size_t total = x0 ? B * nx : 0;
+    for (int i = 0; i < 9; ++i) if (outs[i]) total += B * per[i];
+    if (nviol_step) total += (B * nCnt + 1) / 2;
+    { int rc = score_scratch(h, total); if (rc) return rc; }
+    double *top = h->d_score;
+    if (x0) { HIPCHK(hipMemcpy(top, x0, B * nx * sizeof(double), hipMemcpyHostToDevice)); x0d = top; top += B * nx; }
+    for (int i = 0; i < 9; ++i) if (outs[i]) { od[i] = top; top += B * per[i]; }
+    if (nviol_step) cntd = (int32_t *)top;
+  }
+  { int rc = fork_from_user(h); if (rc) return rc; }
+  for (size_t gi = 0; gi < h->g.size(); ++gi) {
+    const Inner *q = h->g[gi];
+    const size_t b0 = (size_t)h->b0[gi];
+    PlantDev pd;
+    if (plant) pd = plant->pd;
+    else {   // the handle's own model as a plant, as cddp_hip_score_rollouts dresses it
+      std::memset(&pd, 0, sizeof(pd));
+      pd.model = q->P.model; pd.integrator = q->P.integrator; pd.substeps = 1; pd.nx = q->P.nx; pd.nu = q->P.nu; pd.Bp = q->d.Bp; pd.h = q->P.dt;
+      pd.params = (const double *)((const char *)q->dP + offsetof(ProblemDev, mp));
+    }
+    a.b0 = (int)b0;
+    a.x0 = x0d ? x0d + b0 * nx : nullptr;
+    double *go[9];
+    for (int i = 0; i < 9; ++i) go[i] = od[i] ? od[i] + b0 * per[i] : nullptr;
+    a.cost = go[0]; a.viol = go[1]; a.stats = go[2]; a.dXmean = go[3]; a.SX = go[4]; a.dUmean = go[5]; a.SU = go[6]; a.X_out = go[7]; a.U_out = go[8];
+    a.nviol_step = cntd ? cntd + b0 * nCnt : nullptr;
+    const hipError_t e = mc_launch(pd, q->d, a, f, q->stream);
+    if (e == hipErrorInvalidValue) return fail(-3, "%s: the library has no sampling kernel for model id %d with nx = %d, nu = %d", me, pd.model, pd.nx, pd.nu);
+    HIPCHK(e);
+  }
+  if (dev) return io_finish(h);
+  HIPCHK(hipGetLastError());
+  for (Inner *q : h->g) HIPCHK(hipStreamSynchronize(q->stream));
+  for (int i = 0; i < 9; ++i) if (outs[i]) HIPCHK(hipMemcpy(outs[i], od[i], B * per[i] * sizeof(double), hipMemcpyDeviceToHost));
+  if (nviol_step) HIPCHK(hipMemcpy(nviol_step, cntd, B * nCnt * sizeof(int32_t), hipMemcpyDeviceToHost));
   return join_to_user(h);
 }
 

@@ -928,6 +928,23 @@ class HipBatchSolver : public ISolverAlgorithm {
     if (!h_) throw std::runtime_error("cddp_hip: mppiRefine needs a resident batch (the plug-in route has no resident handle)");
     check(cddp_hip_mppi_refine(h_, plant ? plant->get() : nullptr, flags, &desc, x0, U_mean, U_out, cost_out, viol_out, stats));
   }
+  // NEW: Monte-Carlo evaluation of the plans under noise (include/cddp_hip.h "Monte-Carlo evaluation of a solved plan under noise").  desc:
+  // seed, stream, nsamp, keep_nominal, viol_tol and the host factors L0[nx][nx], Lw[nx][nx], Lu[nu][nu] (any nullptr: no such noise).
+  // mcSampleNoise writes the coloured noise; planMonteCarlo rolls desc.nsamp noisy closed loops per trajectory out around the live plan and
+  // reduces over the samples on the device.  flags: CDDP_HIP_MC_DEVICE (device pointers of the solver's device), CDDP_HIP_MC_DIAG (SX, SU:
+  // diagonals).  plant: nullptr = the batch's own model.  Any output nullptr, not all.
+  void mcSampleNoise(int flags, const cddp_hip_mc_desc &desc, double *Z0 /* batch*nsamp*nx */, double *E /* batch*nsamp*N*nu */, double *Wn /* batch*nsamp*N*nx */) {
+    if (!h_) throw std::runtime_error("cddp_hip: mcSampleNoise needs a resident batch (the plug-in route has no resident handle)");
+    check(cddp_hip_mc_sample_noise(h_, flags, &desc, Z0, E, Wn));
+  }
+  void planMonteCarlo(Plant *plant, int flags, const cddp_hip_mc_desc &desc, const double *x0 /* batch*nx | nullptr */, double *cost /* batch*nsamp */,
+                      double *viol /* batch*nsamp */, double *stats /* batch*8 */, int32_t *nviol_step = nullptr /* batch*(N+1) */,
+                      double *dXmean = nullptr /* batch*(N+1)*nx */, double *SX = nullptr /* batch*(N+1)*nx*nx (DIAG: batch*(N+1)*nx) */,
+                      double *dUmean = nullptr /* batch*N*nu */, double *SU = nullptr /* batch*N*nu*nu (DIAG: batch*N*nu) */,
+                      double *X_out = nullptr /* batch*nsamp*(N+1)*nx */, double *U_out = nullptr /* batch*nsamp*N*nu */) {
+    if (!h_) throw std::runtime_error("cddp_hip: planMonteCarlo needs a resident batch (the plug-in route has no resident handle)");
+    check(cddp_hip_plan_montecarlo(h_, plant ? plant->get() : nullptr, flags, &desc, x0, cost, viol, stats, nviol_step, dXmean, SX, dUmean, SU, X_out, U_out));
+  }
   // NEW: solve the resident batch again from the seed it holds now (setInitialDevice, mpcAdvance) -- solveBatch() without creating and uploading
   std::vector<CDDPSolution> resolveBatch(CDDP &ctx) {
     if (!h_) throw std::runtime_error("cddp_hip: resolveBatch needs a resident batch (the plug-in route has no resident handle)");

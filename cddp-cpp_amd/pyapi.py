@@ -175,6 +175,11 @@ SCORE_FEEDBACK = 2
 SCORE_X0_PER_CANDIDATE = 4
 # cddp_hip_sample_controls / cddp_hip_mppi_blend / cddp_hip_mppi_refine (include/cddp_hip.h, "sampling-based plan refinement")
 MPPI_SEED = 8
+# cddp_hip_mc_sample_noise / cddp_hip_plan_montecarlo (include/cddp_hip.h, "Monte-Carlo evaluation of a solved plan under noise")
+MC_DEVICE, MC_DIAG = 1, 2
+MC_MAX_SAMPLES = 1024
+MC_STATS = ("n_finite", "n_viol", "cost_mean", "cost_var", "cost_min", "cost_max", "viol_mean", "viol_max")
+MC_OUTPUTS = ("cost", "viol", "stats", "nviol_step", "dXmean", "SX", "dUmean", "SU", "X", "U")
 # cddp_hip_get_field_device / cddp_hip_field_shape (include/cddp_hip.h, "device-resident inputs and outputs"): enum cddp_hip_field
 FIELD_NAMES = ("X", "U", "K", "KFF", "VX", "VXX", "A", "B", "S", "Y", "G", "LAMBDA")
 FIELD_IDS = {name: i for i, name in enumerate(FIELD_NAMES)}
@@ -199,6 +204,13 @@ class MppiDesc(C.Structure):   # cddp_hip_mppi_desc
     _fields_ = [
         ("seed", C.c_uint64), ("stream", C.c_uint32), ("iters", C.c_int32), ("ncand", C.c_int32), ("keep_mean", C.c_int32),
         ("lam", C.c_double), ("viol_tol", C.c_double), ("sigma", _dp), ("u_lower", _dp), ("u_upper", _dp),
+    ]
+
+
+class McDesc(C.Structure):   # cddp_hip_mc_desc
+    _fields_ = [
+        ("seed", C.c_uint64), ("stream", C.c_uint32), ("nsamp", C.c_int32), ("keep_nominal", C.c_int32), ("_pad", C.c_int32),
+        ("viol_tol", C.c_double), ("L0", _dp), ("Lw", _dp), ("Lu", _dp),
     ]
 
 
@@ -845,6 +857,8 @@ DEVICE_IO_ARGTYPES = {
     "cddp_hip_sample_controls": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
     "cddp_hip_mppi_blend": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
     "cddp_hip_mppi_refine": [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    "cddp_hip_mc_sample_noise": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    "cddp_hip_plan_montecarlo": [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p] + [C.c_void_p] * 11,
 }
 
 EXPORTED_SYMBOLS = [
@@ -864,6 +878,7 @@ EXPORTED_SYMBOLS = [
     "cddp_hip_plan_jvp", "cddp_hip_plan_vjp", "cddp_hip_plan_covariance",
     "cddp_hip_score_rollouts", "cddp_hip_seed_best",
     "cddp_hip_sample_controls", "cddp_hip_mppi_blend", "cddp_hip_mppi_refine",
+    "cddp_hip_mc_sample_noise", "cddp_hip_plan_montecarlo",
 ]
 
 
@@ -1570,6 +1585,101 @@ class HipBatchSolver:
         self._check(self.lib.cddp_hip_mppi_refine(self.h, plant.h if plant is not None else None, flags, C.addressof(d), self._addr(x0),
                                                   self._addr(U_mean), self._addr(out["U"]), self._addr(out["cost"]), self._addr(out["viol"]),
                                                   self._addr(out["stats"])))
+        return out
+
+    # ---- Monte-Carlo evaluation of the plan under noise (cddp_hip_mc_sample_noise / cddp_hip_plan_montecarlo): the conventions of
+    # score_rollouts for the arrays; the covariances (or their factors) are small host arrays
+    def _mc_desc(self, who, Sigma0, W, Wu, nsamp, seed=0, stream=0, keep_nominal=False, viol_tol=0.0, factors=False):
+        """-> (McDesc, the arrays it points into).  Covariances are factored on the host with numpy.linalg.cholesky; factors=True takes the
+        lower-triangular factors themselves.  What can be refused without the library is refused here with ValueError."""
+        nx, nu = self.p.nx, self.p.nu
+        nsamp = int(nsamp); seed = int(seed); stream = int(stream); viol_tol = float(viol_tol)
+        if not 1 <= nsamp <= MC_MAX_SAMPLES:
+            raise ValueError("%s: nsamp: 1 to %d samples are expected, got %d" % (who, MC_MAX_SAMPLES, nsamp))
+        if not 0 <= seed < 2 ** 64 or not 0 <= stream < 2 ** 32:
+            raise ValueError("%s: seed is a 64-bit and stream a 32-bit unsigned number, got %r and %r" % (who, seed, stream))
+        if viol_tol != viol_tol:
+            raise ValueError("%s: viol_tol is NaN" % who)
+        d = McDesc()
+        d.seed = seed; d.stream = stream; d.nsamp = nsamp; d.keep_nominal = 1 if keep_nominal else 0; d.viol_tol = viol_tol
+        keep = []
+        for field, name, a, n in (("L0", "Sigma0", Sigma0, nx), ("Lw", "W", W, nx), ("Lu", "Wu", Wu, nu)):
+            if a is None:
+                continue
+            if hasattr(a, "data_ptr") and not isinstance(a, np.ndarray):
+                a = a.detach().cpu().numpy()     # (nx x nx at most: the factors are host arrays of the C entry)
+            a = np.asarray(a, dtype=np.float64)
+            if a.shape != (n, n) or not np.isfinite(a).all():
+                raise ValueError("%s: %s: a finite (%d, %d) matrix is expected, got shape %s" % (who, name, n, n, a.shape))
+            if not factors:
+                try:
+                    a = np.linalg.cholesky(a)
+                except np.linalg.LinAlgError:
+                    raise ValueError("%s: %s is not positive definite (pass a factor with factors=True for a semidefinite one)" % (who, name))
+            L = np.ascontiguousarray(np.tril(a))
+            keep.append(L)
+            setattr(d, field, _ptr(L))
+        return d, keep
+
+    def mc_sample_noise(self, Sigma0=None, W=None, Wu=None, nsamp=1, device=False, want=("Z0", "E", "Wn"), **draw):
+        """The coloured noise plan_montecarlo draws (cddp_hip_mc_sample_noise): a dict of "Z0" (B, S, nx), "E" (B, S, N, nu), "Wn" (B, S, N,
+        nx), each L z with z a standard normal that is a function of (seed, stream, trajectory, sample, element) alone; a source whose
+        covariance is None is all zeros.  draw: seed, stream, keep_nominal, factors.  numpy arrays, or device tensors with device=True."""
+        who = "mc_sample_noise"
+        want = tuple(want)
+        if not want or any(w not in ("Z0", "E", "Wn") for w in want):
+            raise ValueError("%s: want: a non-empty subset of ('Z0', 'E', 'Wn') is expected, got %r" % (who, want))
+        B, N, nx, nu = self.B, self.p.N, self.p.nx, self.p.nu
+        d, keep = self._mc_desc(who, Sigma0, W, Wu, nsamp, **draw)
+        S = d.nsamp
+        shapes = {"Z0": (B, S, nx), "E": (B, S, N, nu), "Wn": (B, S, N, nx)}
+        out = {k: self._mppi_out(shapes[k], device) for k in want}
+        if device:
+            self._order_device_io()
+        self._check(self.lib.cddp_hip_mc_sample_noise(self.h, MC_DEVICE if device else 0, C.addressof(d), self._addr(out.get("Z0")),
+                                                      self._addr(out.get("E")), self._addr(out.get("Wn"))))
+        return out
+
+    def plan_montecarlo(self, Sigma0=None, W=None, Wu=None, nsamp=64, seed=0, stream=0, keep_nominal=False, plant=None, x0=None, viol_tol=0.0,
+                        diag=False, factors=False, want=("stats", "nviol_step", "dXmean", "SX", "dUmean", "SU"), device=None):
+        """S = nsamp noisy closed-loop rollouts per trajectory around the live plan, reduced on the device (cddp_hip_plan_montecarlo):
+        x_0 = x0 + L0 z, u_t = clip(U_t + Lu z + K_t (x_t - X_t)), x_{t+1} = f(x_t, u_t) + Lw z on the handle's model or a DevicePlant, with
+        Sigma0 = L0 L0^T, W = Lw Lw^T, Wu = Lu Lu^T (None: no such noise; factors=True: the arguments are the lower-triangular factors).
+        x0: (B, nx) or None (row 0 of the live plan), a numpy array or a torch.float64 tensor on the handle's device; device tensors in (or
+        device=True) give device tensors back.  want: any of MC_OUTPUTS -- "cost", "viol" (B, S); "stats" (B, 8) in the order of MC_STATS;
+        "nviol_step" (B, N + 1) int32, the samples whose rows of step t exceed viol_tol; "dXmean" (B, N + 1, nx), "SX" (B, N + 1, nx, nx),
+        "dUmean" (B, N, nu), "SU" (B, N, nu, nu): sample mean and covariance of x - X_t and of the applied control minus U_t (diag=True:
+        the diagonals, (B, N + 1, nx) and (B, N, nu)); "X" (B, S, N + 1, nx) and "U" (B, S, N, nu), the only outputs of that size.  The
+        noise is a function of (seed, stream, trajectory, sample, element) alone; keep_nominal makes sample 0 noise-free.  The handle's
+        solver state is not modified."""
+        who = "plan_montecarlo"
+        want = tuple(want)
+        if not want or any(w not in MC_OUTPUTS for w in want):
+            raise ValueError("%s: want: a non-empty subset of %r is expected, got %r" % (who, MC_OUTPUTS, want))
+        B, N, nx, nu = self.B, self.p.N, self.p.nx, self.p.nu
+        d, keep = self._mc_desc(who, Sigma0, W, Wu, nsamp, seed=seed, stream=stream, keep_nominal=keep_nominal, viol_tol=viol_tol, factors=factors)
+        S = d.nsamp
+        dev = self._is_device(x0) if device is None else bool(device)
+        if x0 is not None:
+            x0 = self._score_arg(who, "x0", x0, [(B, nx)], dev)
+        shapes = {"cost": (B, S), "viol": (B, S), "stats": (B, 8), "nviol_step": (B, N + 1), "dXmean": (B, N + 1, nx),
+                  "SX": (B, N + 1, nx) if diag else (B, N + 1, nx, nx), "dUmean": (B, N, nu), "SU": (B, N, nu) if diag else (B, N, nu, nu),
+                  "X": (B, S, N + 1, nx), "U": (B, S, N, nu)}
+        out = {}
+        for k in want:
+            if k == "nviol_step":
+                if dev:
+                    import torch
+                    out[k] = torch.empty(shapes[k], dtype=torch.int32, device=self._torch_device())
+                else:
+                    out[k] = np.zeros(shapes[k], dtype=np.int32)
+            else:
+                out[k] = self._mppi_out(shapes[k], dev)
+        if dev:
+            self._order_device_io()
+        flags = (MC_DEVICE if dev else 0) | (MC_DIAG if diag else 0)
+        self._check(self.lib.cddp_hip_plan_montecarlo(self.h, plant.h if plant is not None else None, flags, C.addressof(d), self._addr(x0),
+                                                      *[self._addr(out.get(k)) for k in MC_OUTPUTS]))
         return out
 
 

@@ -1232,6 +1232,52 @@ class CDDP:                         # cddp_core.hpp:214-423 / bind_solver.cpp:57
         out["SX"] = cov["SX"]; out["SU"] = cov["SU"]; out["expected_cost_increase"] = cov["dcost"]
         return out
 
+    def solve_batch_mc(self, x0s, Sigma0=None, W=None, Wu=None, nsamp=64, seed=0, stream=0, keep_nominal=False, viol_tol=0.0, diag=False,
+                       factors=False, mc_want=("stats", "nviol_step", "dXmean", "SX", "dUmean", "SU"), U0=None, X0=None,
+                       solver_type=SolverType.IPDDP, want=("X", "U")):
+        """NEW (no reference counterpart): solve_batch_device, then a Monte-Carlo evaluation of the solved plans' closed loop under noise
+        (cddp_hip_plan_montecarlo): nsamp noisy rollouts per trajectory on the nonlinear model with the plan's feedback gains, the noise
+        drawn and the samples reduced on the device.  Sigma0, W (nx x nx) and Wu (nu x nu): covariances of the initial state, the process
+        noise and the actuator noise (None: no such noise; factors=True: their lower-triangular factors), numpy arrays or torch tensors.
+        Returns what solve_batch_device returns, plus "mc": the dict of HipBatchSolver.plan_montecarlo for mc_want, as device tensors."""
+        import torch
+        api = _api()
+        name = solver_type.value if isinstance(solver_type, SolverType) else str(solver_type)
+        want = tuple(want)
+        unknown = [w for w in want if w not in api.FIELD_IDS]
+        if unknown:
+            raise ValueError("want: unknown fields %s (known: %s)" % (unknown, ", ".join(api.FIELD_NAMES)))
+        if self._sys is None:
+            raise RuntimeError("Dynamical system must be set before solving.")
+        kind = self._resident_kind(name)
+        if kind is None:
+            raise NotImplementedError("solve_batch_mc needs a problem of the resident route (built-in plant, objective and constraints): "
+                                      "solver '%s' with this problem runs on the plug-in route, which has no resident handle" % name)
+        if not isinstance(x0s, torch.Tensor) or x0s.dim() != 2:
+            raise ValueError("x0s: a (B, nx) torch tensor is expected")
+        B = int(x0s.shape[0])
+        if B <= 0:
+            raise ValueError("x0s: an empty batch")
+        if U0 is None and self._U is not None and x0s.is_cuda:     # (the seed of set_initial_trajectory, as solve_batch_device takes it)
+            U0 = torch.as_tensor(np.ascontiguousarray(self._U, dtype=np.float64), device=x0s.device).expand(B, -1, -1).contiguous()
+        if X0 is None and self._X is not None and x0s.is_cuda:
+            X0 = torch.as_tensor(np.ascontiguousarray(self._X, dtype=np.float64), device=x0s.device).expand(B, -1, -1).contiguous()
+        p = self._problem(kind)
+        hs = api.HipBatchSolver(p, B)
+        try:
+            hs.set_initial_device(x0s, U0, X0)        # (shape, dtype, contiguity and device are checked there: ValueError)
+            st = hs.solve()
+            mc = hs.plan_montecarlo(Sigma0, W, Wu, nsamp=nsamp, seed=seed, stream=stream, keep_nominal=keep_nominal, viol_tol=viol_tol, diag=diag,
+                                    factors=factors, want=mc_want, device=True)
+            out = {w: hs.field_device(w) for w in want}
+            res = hs.results_device()
+        finally:
+            hs.close()
+        out["results"] = {k: v for k, v in res.items() if k not in ("cols", "icols")}
+        out["solve_time_ms"] = float(st.solve_ms)
+        out["mc"] = mc
+        return out
+
     def solve_batch_sampled(self, x0s, U_candidates, solver_type=SolverType.IPDDP, viol_tol=0.0, want=("X", "U")):
         """NEW (no reference counterpart): solve_batch_device started from the best of S candidate control sequences per trajectory
         (cddp_hip_score_rollouts, cddp_hip_seed_best): every candidate is rolled out on the device in one launch, the admissible one

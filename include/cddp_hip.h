@@ -827,6 +827,59 @@ int cddp_hip_mppi_refine(cddp_hip_handle *h, cddp_hip_plant *plant /* or NULL */
                          double *U_out /* [B][N][nu] */, double *cost_out /* [B][S] or NULL */, double *viol_out /* [B][S] or NULL */,
                          double *stats /* [B][3] or NULL */);
 
+/* ---- Monte-Carlo evaluation of a solved plan under noise --------------------------------
+ * What do the true nonlinear plant, the actuator box and the constraint rows do to the Gaussian picture of cddp_hip_plan_covariance?
+ * cddp_hip_plan_montecarlo rolls S noisy closed loops per trajectory around the live plan in ONE launch (csrc/inst_mc.hip: one workgroup per
+ * trajectory, one lane per sample), draws the initial-state, actuator and process noise in the lane from the counter-based generator of
+ * "sampling-based plan refinement" and reduces across the samples on the device in a fixed order: moments, counts and per-sample scalars
+ * leave the GPU, no [B][S][N][..] array exists unless X_out / U_out ask for one.  cddp_hip_mc_sample_noise writes the coloured noise
+ * itself.  csrc/plan_mc.hpp is the normative statement (host and device compile it), restated here; the library is built with
+ * -ffp-contract=off and the tests are bitwise.
+ * Noise: L0, Lw, Lu are lower-triangular factors of cov(dx_0) = Sigma0, cov(w_t) = W, cov(eps_t) = Wu, one matrix each for the whole
+ *  batch, row-major HOST arrays read during the call (only j <= i is read); a NULL factor means no such noise.
+ * Normals: sample c of trajectory b (its index in the whole batch) uses z(e) = the normal of element e of candidate c of trajectory b of
+ *  the generator above (counter (e >> 1, c, b, stream), even / odd half), with e = i (i < nx) for the initial state,
+ *  e = nx + t (nu + nx) + i (i < nu) for the actuator noise of step t and e = nx + t (nu + nx) + nu + i (i < nx) for its process noise.  A
+ *  NULL factor skips its draws and leaves the indices where they are.  With keep_nominal sample 0 takes z = 0 everywhere.  An MPPI call
+ *  with the same (seed, stream) shares this counter space.
+ * Coloured noise: v[i] = s, s = 0; for j ascending, j <= i: s += L[i][j] * z[j].
+ * Rollout of sample c: x[i] = xbase[i] + v0[i] (xbase = x0[b], or row 0 of the live plan), cost = 0, viol = 0; for t = 0 .. N-1 in the
+ *  order of cddp_hip_score_rollouts: uc[i] = U_t[i] + eps[i]; u[i] = uc[i] + s, s = 0; for j ascending s += K_t[i][j] * (x[j] - X_t[j]); the
+ *  plant's box; cost += the running cost; v_t = 0 folded over the path rows, viol = max(viol, v_t); the step(s); with Lw
+ *  x[i] = xn[i] + w[i] (cddp_hip_plant_step's line).  Then the terminal cost, and the terminal inequality rows folded from 0 as v_N.
+ * Tree sum over the samples: c = 64 k + l, absent lanes contribute +0.0; for m = 1, 2, 4, 8, 16, 32: v[l] = v[l] + v[l ^ m]; lane 0 holds
+ *  the chunk total; chunk totals are added with k ascending, starting from chunk 0's.
+ * Moments of step t: d_c[i] = x_c,t[i] - X_t[i]; m1[i] = tree(d_c[i]), dXmean = m1[i] / S; q[i][j] = tree(d_c[i] * d_c[j]) for j <= i;
+ *  SX[i][j] = (q[i][j] - (m1[i] * m1[j]) / S) / (S - 1), mirrored, 0 when S == 1.  dUmean and SU likewise from the applied control minus
+ *  U_t.  nviol_step[b][t] = the number of samples with v_t > viol_tol, t = 0 .. N.  With CDDP_HIP_MC_DIAG SX and SU hold the diagonals.
+ * stats[b][8] = n_finite (cost and viol finite), n_viol (viol > viol_tol), cost_mean = tree(cost) / S, cost_var = tree((cost_c -
+ *  cost_mean)^2) / (S - 1) (0 when S == 1), cost_min, cost_max (by <, c ascending from sample 0), viol_mean = tree(viol) / S, viol_max
+ *  (as cost_max).  Non-finite values propagate; nothing is special-cased.  (The sign of an exact zero is not specified.)
+ * Pointer flags (CDDP_HIP_MC_DEVICE = device pointers for every array but the factors), checks, stream ordering, tile-group offsets and the
+ * handle-owned scratch are those of cddp_hip_score_rollouts.  Any output may be NULL, not all.  The handle's solver state is not modified.
+ * Refused before anything is launched, each with its own message: a NULL handle or descriptor, unknown flag bits, nsamp < 1, nsamp > 1024,
+ * a NaN viol_tol, a non-finite factor entry, every output NULL, an MSIPDDP handle, a handle or plant cddp_hip_track_plan would refuse, and
+ * with CDDP_HIP_MC_DEVICE a pointer cddp_hip_get_field_device would refuse.  (New entry points; ABI version unchanged.) */
+typedef struct cddp_hip_mc_desc {
+  uint64_t seed;
+  uint32_t stream;
+  int32_t nsamp;                       /* S, 1 .. 1024 */
+  int32_t keep_nominal;                /* nonzero: sample 0 draws z = 0 everywhere */
+  int32_t _pad;
+  double viol_tol;
+  const double *L0, *Lw, *Lu;          /* host; [nx][nx], [nx][nx], [nu][nu]; any may be NULL */
+} cddp_hip_mc_desc;                    /* 56 bytes */
+enum { CDDP_HIP_MC_DEVICE = 1, CDDP_HIP_MC_DIAG = 2 };
+int cddp_hip_mc_sample_noise(cddp_hip_handle *h, int flags, const cddp_hip_mc_desc *desc, double *Z0 /* [B][S][nx] or NULL */,
+                             double *E /* [B][S][N][nu] or NULL */, double *Wn /* [B][S][N][nx] or NULL */);
+int cddp_hip_plan_montecarlo(cddp_hip_handle *h, cddp_hip_plant *plant /* or NULL */, int flags, const cddp_hip_mc_desc *desc,
+                             const double *x0 /* [B][nx] or NULL = row 0 of the live plan */,
+                             double *cost /* [B][S] */, double *viol /* [B][S] */, double *stats /* [B][8] */,
+                             int32_t *nviol_step /* [B][N+1] */, double *dXmean /* [B][N+1][nx] */,
+                             double *SX /* [B][N+1][nx][nx] | DIAG [B][N+1][nx] */, double *dUmean /* [B][N][nu] */,
+                             double *SU /* [B][N][nu][nu] | DIAG [B][N][nu] */, double *X_out /* [B][S][N+1][nx] */,
+                             double *U_out /* [B][S][N][nu] */);   /* any output may be NULL, not all */
+
 /* ---- multi-GPU: the single collective of the path --------------------------------------
  * One process (or host thread) per GPU, each with its own handle over a contiguous block of the global batch; nothing
  * is exchanged during a solve.  After it, ONE RCCL all-gather collects every trajectory's 16-byte record.
