@@ -1,4 +1,4 @@
-"""Helper of tests/test_model_cases.py, test_score_every_model.py, test_mppi_every_model.py and test_plan_sens_shapes.py: one row per model
+"""Helper of tests/test_model_cases.py, test_score_every_model.py, test_mppi_every_model.py, test_plan_sens_shapes.py and test_mpc_every_model.py: one row per model
 struct of PLANT_MODEL_LIST (csrc/plant_models.hpp: what k_score and k_mppi_score are instantiated over), one model per pair of
 SENS_PAIR_LIST (csrc/inst_sens.hip: what k_plan_jvp / k_plan_vjp are instantiated over), and one scoring case per registered kernel set
 that carries a constraint.  Both lists are parsed from the sources, and tests/test_model_cases.py holds the tables to them: a model or a

@@ -42,6 +42,38 @@ def test_tables_are_the_compiled_lists(api):
     assert {s.split("/")[0] for s in registered} == {s.split("/")[0] for s in constrained}
 
 
+def test_mpc_tables_are_the_compiled_lists(api):
+    """tests/test_mpc_every_model.py: its model cases are PLANT_MODEL_LIST, its T4 cases the models with nx > 8, its constrained cases every
+    scoring case but the named sets without path duals, its other-solver cases `compare` rows of plant_matrix.MATRIX"""
+    import plant_matrix as PM
+    import test_mpc_every_model as E
+    nx = {row.key: MC.build_row(api, row).nx for row in MC.MODELS.values()}
+    default = [key for key, layout in E.MODEL_CASES if layout == "default"]
+    assert sorted(MC.KEYS[key] for key in default) == sorted(MC.plant_model_list()) and len(default) == 25
+    assert sorted(key for key, layout in E.MODEL_CASES if layout == "t4=0") == sorted(E.T4_KEYS) == sorted(k for k in nx if nx[k] > 8)
+    assert {layout for _, layout in E.MODEL_CASES} == {"default", "t4=0"} and len(set(E.MODEL_CASES)) == len(E.MODEL_CASES) == 25 + len(E.T4_KEYS)
+    # the constrained cases: SET_NAMES minus the refused names, and the refused names are exactly the sets without path duals
+    assert sorted(E.SET_CASES + E.REFUSED_SETS) == sorted(MC.SET_NAMES) and not set(E.SET_CASES) & set(E.REFUSED_SETS)
+    for name in MC.SET_NAMES:
+        p = MC.set_case(api, name)[0]
+        assert p.c.solver == api.SOLVER_IPDDP and (p.dual_dim() == 0) == (name in E.REFUSED_SETS), name
+    # two tile groups: a model of 10 states and manip7
+    assert len(E.GROUP_KEYS) == 2 and "manip7" in E.GROUP_KEYS and sorted(nx[k] for k in E.GROUP_KEYS) == [10, 14] and E.GROUP_B > 128
+    # the other resident solvers: `compare` rows, per solver one plant with nx <= 8 and one with nx = 10
+    sizes = {}
+    for case in E.SOLVER_CASES:
+        plant, box, solver = PM.parse(case)
+        assert PM.mode_of(case) == PM.C, case
+        sizes.setdefault(solver, []).append(PM.PLANTS[plant][0])
+        assert solver != "msipddp" or not box, case
+    assert sorted(sizes) == ["clddp", "logddp", "msipddp"]
+    for solver, ns in sizes.items():
+        assert len(ns) == 2 and min(ns) <= 8 and max(ns) == 10, (solver, ns)
+    # the rows that must show two live slots in one advance: one on each side of nx = 8; the raised rows are models
+    assert any(nx[k] <= 8 for k in E.MIXED_SLOT_KEYS) and any(nx[k] > 8 for k in E.MIXED_SLOT_KEYS)
+    assert set(E.RAISED) <= set(MC.MODEL_KEYS) and all(set(v) <= {"spread", "max_iterations"} for v in E.RAISED.values())
+
+
 def test_inputs_meet_the_conditions_on_host_references(api):
     """4. on the CPU, no device: the builder's problem, x0 and U of every row and every constrained case"""
     lo_all, hi_all = np.inf, -np.inf

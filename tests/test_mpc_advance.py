@@ -22,10 +22,12 @@ def same(a, b):
     return np.array_equal(np.asarray(a), np.asarray(b), equal_nan=np.asarray(a).dtype.kind == "f")
 
 
-def pair(api, p, B, seed, spread=None):
-    """two handles of one problem, cold-solved from the same seed, then warm start switched on (the flag lives in the shared problem object)"""
+def pair(api, p, B, seed, spread=None, x0=None):
+    """two handles of one problem, cold-solved from the same seed (or from the x0 given), then warm start switched on (the flag lives in the
+    shared problem object)"""
     import test_gpu_parity as T
-    x0 = api.batch_x0(p, B, seed, T.spread_for(p) if spread is None else spread)
+    if x0 is None:
+        x0 = api.batch_x0(p, B, seed, T.spread_for(p) if spread is None else spread)
     U0 = api.batch_U0(p, B)
     hs = []
     for _ in range(2):

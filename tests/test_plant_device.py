@@ -154,8 +154,9 @@ def test_step_is_the_oracles_dynamics(api, oracle_built, name, substeps):
 
 
 # ---- 3. the loop is the hand-written loop --------------------------------------------------------------------------------------------
-def plant_loop(api, h, plant, steps, mode, shift_duals=False, W=None, box=None):
-    """cddp_hip_mpc_run_plant written out; also the seed of every solve after the first and the model's own x_1 of every step"""
+def plant_loop(api, h, plant, steps, mode, shift_duals=False, W=None, box=None, heads=None):
+    """cddp_hip_mpc_run_plant written out; also the seed of every solve after the first and the model's own x_1 of every step (and, into the
+    list `heads`, the handle's own u_0 of every step: the control before the plant's box)"""
     B = h.B
     U = np.zeros((B, steps, h.p.nu)); X = np.zeros((B, steps + 1, h.p.nx))
     it = np.zeros((B, steps), dtype=np.int32); st = np.zeros((B, steps), dtype=np.int32)
@@ -169,6 +170,8 @@ def plant_loop(api, h, plant, steps, mode, shift_duals=False, W=None, box=None):
         U[:, k] = u0 if box is None else clip(u0, box[0], box[1])
         X[:, k + 1] = xn; it[:, k] = r["iterations"]; st[:, k] = r["status"]
         model_x1.append(x1)
+        if heads is not None:
+            heads.append(u0)
         Xs, Us = shift(Xp), shift(Up); Xs[:, 0] = xn
         seeds.append((Xs, Us))
         h.mpc_advance(mode, x_next=xn, shift_duals=shift_duals)
