@@ -21,6 +21,7 @@
 #include "score_kernels.hpp"
 #include "mppi_kernels.hpp"
 #include "mc_kernels.hpp"
+#include "ref_kernels.hpp"
 
 // 1 when a[0] > a[1] > ... > a[n - 1] (NaN-free): the ladders cddp_hip_build_alphas makes; DevBuf::ladder_sorted
 static int ladder_strictly_decreasing(const double *a, int n) {
@@ -237,6 +238,12 @@ struct Inner {
   bool has_plan = false;         // an initialize() or solve() has run: slot cur[b] holds every trajectory's current plan
   double *d_xnext = nullptr;     // staging of a host x_next (B * nx doubles, batch-major): the one upload of an MPC step
   double *d_log_u = nullptr, *d_log_x = nullptr; int32_t *d_log_it = nullptr, *d_log_st = nullptr; int log_steps = 0;   // closed-loop log of cddp_hip_mpc_run
+  // movable goal / per-step reference (cddp_hip_set_reference, cddp_hip_mpc_set_reference_path)
+  bool goal_on_device = false;   // the goal slot of dP was last written ON the device (device-pointer setter, window kernel): P.pool's copy is
+                                 // stale and is read back (goal_to_host) before P is uploaded whole again
+  double *d_path = nullptr;      // the bound reference path, [path_L][nx], this group's own copy; nullptr: no path bound
+  long long path_L = 0, path_cursor = -1;
+  double path_rps = 1.0;
 };
 
 namespace {
@@ -755,6 +762,7 @@ static int in_destroy(Inner *h) {
   if (h->h_head) hipHostFree(h->h_head);
   if (h->d_xnext) hipFree(h->d_xnext);
   if (h->d_log_u) { hipFree(h->d_log_u); hipFree(h->d_log_x); hipFree(h->d_log_it); hipFree(h->d_log_st); }
+  if (h->d_path) hipFree(h->d_path);
   if (h->own_stream && h->stream) hipStreamDestroy(h->stream);
   if (h->cu.fwd) hipStreamDestroy(h->cu.fwd);
   if (h->cu.sweep) hipStreamDestroy(h->cu.sweep);
@@ -865,12 +873,113 @@ static int in_initialize(Inner *h) {
   return 0;
 }
 
+// ---- movable goal and per-step reference (cddp_hip_set_reference, cddp_hip_mpc_set_reference_path) --------------------
+// The kernels read the goal from dP->pool + off_xref and the per-step reference through DevBuf::xref_traj on every launch, so new CONTENTS
+// need nothing but the write; captured windows bake in the DevBuf and are dropped only when xref_traj changes between null and non-null.
+// ProblemDev::has_xref_traj (read by no kernel) follows DevBuf::xref_traj in h->P and, through push_has_traj, in dP.
+static double *goal_slot(Inner *h) { return h->dP->pool + h->P.off_xref; }   // a device address, formed but not read on the host
+
+// P.pool's goal from the device when the device holds the newer one: before the host reads it or uploads P whole (in_set_options,
+// in_set_reference, in_forward -- every place that copies sizeof(ProblemDev) to dP after create)
+static int goal_to_host(Inner *h) {
+  if (!h->goal_on_device) return 0;
+  HIPCHK(hipMemcpyAsync(h->P.pool + h->P.off_xref, goal_slot(h), sizeof(double) * h->P.nx, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  h->goal_on_device = false;
+  return 0;
+}
+
+static void drop_graphs(Inner *h) { for (auto &kv : h->graphs) hipGraphExecDestroy(kv.second); h->graphs.clear(); }
+
+static int push_has_traj(Inner *h) {
+  HIPCHK(hipMemcpyAsync(&h->dP->has_xref_traj, &h->P.has_xref_traj, sizeof(int), hipMemcpyHostToDevice, h->stream));
+  return 0;
+}
+
+// the per-step reference buffer: allocated on first use, kept for the handle's life (ref_alloc_traj); attached, it is what the kernels read
+static int ref_alloc_traj(Inner *h) {
+  if (h->d_xref_traj) return 0;
+  return dalloc(h, &h->d_xref_traj, (size_t)(h->d.N + 1) * h->P.nx);
+}
+static int ref_attach_traj(Inner *h) {
+  { int rc = ref_alloc_traj(h); if (rc) return rc; }
+  if (!h->d.xref_traj) { h->d.xref_traj = h->d_xref_traj; h->P.has_xref_traj = 1; drop_graphs(h); return push_has_traj(h); }
+  return 0;
+}
+
+// one group's cddp_hip_set_reference (checked by the caller): copies enqueued on the group's stream; host pointers: complete on return
+static int in_set_reference(Inner *h, int flags, const double *x_ref, const double *x_ref_traj) {
+  HIPCHK(hipSetDevice(h->device));
+  const bool dev = (flags & CDDP_HIP_REF_DEVICE) != 0;
+  const int nx = h->P.nx;
+  if (x_ref_traj) {
+    { int rc = ref_attach_traj(h); if (rc) return rc; }
+    HIPCHK(hipMemcpyAsync(h->d_xref_traj, x_ref_traj, sizeof(double) * (size_t)(h->d.N + 1) * nx, dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream));
+  }
+  if ((flags & CDDP_HIP_REF_CLEAR_TRAJ) && h->d.xref_traj) {
+    h->d.xref_traj = nullptr; h->P.has_xref_traj = 0; drop_graphs(h);
+    int rc = push_has_traj(h); if (rc) return rc;
+  }
+  if (dev) {
+    if (x_ref) { HIPCHK(hipMemcpyAsync(goal_slot(h), x_ref, sizeof(double) * nx, hipMemcpyDeviceToDevice, h->stream)); h->goal_on_device = true; }
+    return 0;
+  }
+  if (x_ref) { for (int i = 0; i < nx; ++i) h->P.pool[h->P.off_xref + i] = x_ref[i]; h->goal_on_device = false; }
+  else { int rc = goal_to_host(h); if (rc) return rc; }
+  HIPCHK(hipMemcpyAsync(h->dP, &h->P, sizeof(ProblemDev), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+// the window of the group's cursor into its per-step reference buffer and goal slot (inst_ref.hip), on the group's stream
+static int ref_install_window(Inner *h) {
+  const hipError_t e = ref_window_launch(h->d_path, h->path_L, h->P.nx, h->d.N, h->path_cursor, h->path_rps, h->d_xref_traj, goal_slot(h), h->stream);
+  if (e != hipSuccess) return fail(-10, "reference window launch failed: %s", hipGetErrorString(e));
+  h->goal_on_device = true;
+  return 0;
+}
+
+// one group's cddp_hip_mpc_set_reference_path (checked by the caller), in two parts so that a failure in any group leaves every group as it
+// was.  Stage: everything that allocates -- the per-step reference buffer (kept, not attached) and this group's own copy of the rows.
+static int in_stage_path(Inner *h, const cddp_hip_ref_path *c, double **out) {
+  HIPCHK(hipSetDevice(h->device));
+  { int rc = ref_alloc_traj(h); if (rc) return rc; }
+  const bool dev = (c->flags & CDDP_HIP_REF_DEVICE) != 0;
+  const size_t bytes = (size_t)c->rows * (size_t)h->P.nx * sizeof(double);
+  double *p = nullptr;
+  HIPCHK(hipMalloc((void **)&p, bytes));
+  const hipError_t e = hipMemcpyAsync(p, c->path, bytes, dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream);
+  if (e != hipSuccess) { hipFree(p); return fail(-10, "cddp_hip_mpc_set_reference_path: copy of the path failed: %s", hipGetErrorString(e)); }
+  *out = p;
+  return 0;
+}
+// Commit: the staged rows become the bound path and the window of cursor `start` is installed
+static int in_commit_path(Inner *h, const cddp_hip_ref_path *c, double *p) {
+  HIPCHK(hipSetDevice(h->device));
+  if (h->d_path) { hipStreamSynchronize(h->stream); hipFree(h->d_path); }   // (a window kernel of the old path may still be queued)
+  h->d_path = p; h->path_L = c->rows; h->path_cursor = c->start; h->path_rps = c->rows_per_step;
+  { int rc = ref_attach_traj(h); if (rc) return rc; }
+  { int rc = ref_install_window(h); if (rc) return rc; }
+  if (!(c->flags & CDDP_HIP_REF_DEVICE)) HIPCHK(hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+static int in_unbind_path(Inner *h) {
+  if (!h->d_path) return 0;
+  HIPCHK(hipSetDevice(h->device));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  hipFree(h->d_path);
+  h->d_path = nullptr; h->path_L = 0; h->path_cursor = -1;
+  return 0;
+}
+
 static int in_set_options(Inner *h, const cddp_hip_options *opt) {
   if (!h || !opt) return fail(-1, "null argument");
   if (!(opt->reg_update_factor > 1.0) || !(opt->reg_max_value > 0.0))
     return fail(-2, "regularization.update_factor must be > 1 and max_value > 0 (got %g, %g)", opt->reg_update_factor, opt->reg_max_value);
   if (!opt->use_ilqr && !model_has_hessians(h->P.model)) return fail_no_hessians(h->P.model);
   HIPCHK(hipSetDevice(h->device));
+  { int rc = goal_to_host(h); if (rc) return rc; }   // P goes up whole below: with the goal the device holds
   double al[CDDP_HIP_MAX_ALPHAS];
   const int na = cddp_hip_build_alphas(opt, al, CDDP_HIP_MAX_ALPHAS);
   if (na != h->P.n_alphas) return fail(-3, "the line-search ladder size is fixed at create time (%d alphas, new options give %d)", h->P.n_alphas, na);
@@ -1005,6 +1114,7 @@ static int in_forward(Inner *h, const double *alphas, int n_alphas, cddp_hip_tri
   if (!h || !alphas || !trials) return fail(-1, "null argument");
   if (n_alphas <= 0 || n_alphas > h->d.n_alphas) return fail(-1, "n_alphas must be in [1, %d] (the handle's ladder size)", h->d.n_alphas);
   HIPCHK(hipSetDevice(h->device));
+  { int rc = goal_to_host(h); if (rc) return rc; }   // P goes up whole, twice, below: with the goal the device holds
   // temporarily install the caller's alphas in the device problem block
   ProblemDev tmp = h->P;
   for (int i = 0; i < n_alphas; ++i) tmp.alphas[i] = alphas[i];
@@ -1708,6 +1818,8 @@ static int in_mpc_advance(Inner *h, int mode, int flags, const double *x_next, b
     if (xdev) hipLaunchKernelGGL(k_mpc_state, dim3((d.Bp + 255) / 256), dim3(256), 0, h->stream, d, nx, xdev, 0, h->d_Xinit);
   }
   HIPCHK(hipGetLastError());
+  // a bound reference path (cddp_hip_mpc_set_reference_path): the step moves the cursor, the next solve reads the next window
+  if (h->d_path) { ++h->path_cursor; int rc = ref_install_window(h); if (rc) return rc; }
   // the caller's buffer is free again on return (a device x_next of a handle on the caller's own stream is ordered by that stream instead)
   if (host_x || (x_next && sync_device_x)) HIPCHK(hipStreamSynchronize(h->stream));
   h->initialized = false;
@@ -2257,6 +2369,117 @@ int cddp_hip_set_initial_device(cddp_hip_handle *h, const double *x0_dev, const 
     q->have_initial = true; q->initialized = false; q->initial_dirty = true;   // as in_set_initial leaves them
   }
   return io_finish(h);
+}
+
+// ---- moving the goal and the per-step reference of a live handle (include/cddp_hip.h; window kernel: inst_ref.hip) ----
+static int ref_all_finite(const double *v, size_t n) {
+  for (size_t i = 0; i < n; ++i) if (!std::isfinite(v[i])) return 0;
+  return 1;
+}
+
+int cddp_hip_set_reference(cddp_hip_handle *h, int flags, const double *x_ref, const double *x_ref_traj) {
+  if (!h) return fail(-1, "cddp_hip_set_reference: null handle");
+  if (flags & ~(CDDP_HIP_REF_DEVICE | CDDP_HIP_REF_CLEAR_TRAJ)) return fail(-2, "cddp_hip_set_reference: unknown flag bits 0x%x", flags);
+  if ((flags & CDDP_HIP_REF_CLEAR_TRAJ) && x_ref_traj) return fail(-2, "cddp_hip_set_reference: CDDP_HIP_REF_CLEAR_TRAJ drops the per-step reference, x_ref_traj must be NULL with it");
+  if (!x_ref && !x_ref_traj && !(flags & CDDP_HIP_REF_CLEAR_TRAJ)) return fail(-2, "cddp_hip_set_reference: nothing to change (x_ref and x_ref_traj are NULL and CDDP_HIP_REF_CLEAR_TRAJ is not set)");
+  if (h->g[0]->d_path) return fail(-1, "cddp_hip_set_reference: a reference path is bound to this handle (cddp_hip_mpc_set_reference_path(h, NULL) unbinds it)");
+  HIPCHK(hipSetDevice(h->device));
+  const int nx = h->nx;
+  const size_t nT = (size_t)(h->N + 1) * nx;
+  if (flags & CDDP_HIP_REF_DEVICE) {
+    if (x_ref) { int rc = io_check_pointer(h, x_ref, sizeof(double) * nx, "cddp_hip_set_reference", "x_ref"); if (rc) return rc; }
+    if (x_ref_traj) { int rc = io_check_pointer(h, x_ref_traj, sizeof(double) * nT, "cddp_hip_set_reference", "x_ref_traj"); if (rc) return rc; }
+  } else {
+    if (x_ref && !ref_all_finite(x_ref, nx)) return fail(-2, "cddp_hip_set_reference: x_ref holds a non-finite value");
+    if (x_ref_traj && !ref_all_finite(x_ref_traj, nT)) return fail(-2, "cddp_hip_set_reference: x_ref_traj holds a non-finite value");
+    // the reference's constructor rule (objective.cpp:55-63) on the state this call leaves behind
+    Inner *q = h->g[0];
+    if (x_ref_traj || (q->d.xref_traj && !(flags & CDDP_HIP_REF_CLEAR_TRAJ))) {
+      std::vector<double> goal(nx), last(nx);
+      { int rc = fork_from_user(h); if (rc) return rc; }
+      if (x_ref) for (int i = 0; i < nx; ++i) goal[i] = x_ref[i];
+      else { int rc = goal_to_host(q); if (rc) return rc; for (int i = 0; i < nx; ++i) goal[i] = q->P.pool[q->P.off_xref + i]; }
+      if (x_ref_traj) for (int i = 0; i < nx; ++i) last[i] = x_ref_traj[(size_t)h->N * nx + i];
+      else {
+        HIPCHK(hipMemcpyAsync(last.data(), q->d.xref_traj + (size_t)h->N * nx, sizeof(double) * nx, hipMemcpyDeviceToHost, q->stream));
+        HIPCHK(hipStreamSynchronize(q->stream));
+      }
+      double s = 0.0;
+      for (int i = 0; i < nx; ++i) s += (last[i] - goal[i]) * (last[i] - goal[i]);
+      if (std::sqrt(s) > 1e-6) return fail(-2, "cddp_hip_set_reference: Last reference state must be same as the reference state (distance %g > 1e-6)", std::sqrt(s));
+    }
+  }
+  { int rc = fork_from_user(h); if (rc) return rc; }
+  for (Inner *q : h->g) { int rc = in_set_reference(q, flags, x_ref, x_ref_traj); if (rc) return rc; }
+  return io_finish(h);
+}
+
+int cddp_hip_get_reference(cddp_hip_handle *h, double *x_ref, double *x_ref_traj, int32_t *has_traj) {
+  if (!h) return fail(-1, "cddp_hip_get_reference: null handle");
+  HIPCHK(hipSetDevice(h->device));
+  { int rc = fork_from_user(h); if (rc) return rc; }
+  const int nx = h->nx;
+  const size_t nT = (size_t)(h->N + 1) * nx;
+  const bool traj = h->g[0]->d.xref_traj != nullptr;
+  std::vector<double> first(nx + (traj ? nT : 0)), other(first.size());
+  for (size_t gi = 0; gi < h->g.size(); ++gi) {   // every tile group reads its own copy: they must all hold the same reference
+    Inner *q = h->g[gi];
+    std::vector<double> &o = gi == 0 ? first : other;
+    if ((q->d.xref_traj != nullptr) != traj) return fail(-11, "cddp_hip_get_reference: tile group %zu disagrees on the per-step reference", gi);
+    HIPCHK(hipMemcpyAsync(o.data(), goal_slot(q), sizeof(double) * nx, hipMemcpyDeviceToHost, q->stream));
+    if (traj) HIPCHK(hipMemcpyAsync(o.data() + nx, q->d.xref_traj, sizeof(double) * nT, hipMemcpyDeviceToHost, q->stream));
+    HIPCHK(hipStreamSynchronize(q->stream));
+    if (gi > 0 && std::memcmp(first.data(), other.data(), first.size() * sizeof(double)) != 0)
+      return fail(-11, "cddp_hip_get_reference: tile group %zu holds another reference than group 0", gi);
+  }
+  if (x_ref) std::memcpy(x_ref, first.data(), sizeof(double) * nx);
+  if (x_ref_traj && traj) std::memcpy(x_ref_traj, first.data() + nx, sizeof(double) * nT);
+  if (has_traj) *has_traj = traj ? 1 : 0;
+  return join_to_user(h);
+}
+
+int cddp_hip_mpc_set_reference_path(cddp_hip_handle *h, const cddp_hip_ref_path *desc) {
+  if (!h) return fail(-1, "cddp_hip_mpc_set_reference_path: null handle");
+  if (!desc) {
+    for (Inner *q : h->g) { int rc = in_unbind_path(q); if (rc) return rc; }
+    return 0;
+  }
+  if (desc->abi_version != CDDP_HIP_ABI_VERSION) return fail(-2, "cddp_hip_mpc_set_reference_path: ABI version mismatch: got %d want %d", desc->abi_version, CDDP_HIP_ABI_VERSION);
+  if (desc->flags & ~CDDP_HIP_REF_DEVICE) return fail(-2, "cddp_hip_mpc_set_reference_path: unknown flag bits 0x%x", desc->flags);
+  if (desc->rows < 1) return fail(-2, "cddp_hip_mpc_set_reference_path: the path needs at least one row (rows = %lld)", (long long)desc->rows);
+  if (desc->start < 0) return fail(-2, "cddp_hip_mpc_set_reference_path: the cursor cannot start before the path (start = %lld)", (long long)desc->start);
+  if (!std::isfinite(desc->rows_per_step) || !(desc->rows_per_step > 0.0))
+    return fail(-2, "cddp_hip_mpc_set_reference_path: rows_per_step must be finite and positive (got %g)", desc->rows_per_step);
+  if (!desc->path) return fail(-1, "cddp_hip_mpc_set_reference_path: null path");
+  if (desc->rows > (int64_t)1 << 40 || desc->start > (int64_t)1 << 60) return fail(-3, "cddp_hip_mpc_set_reference_path: rows or start out of range");
+  HIPCHK(hipSetDevice(h->device));
+  const size_t n = (size_t)desc->rows * (size_t)h->nx;
+  if (desc->flags & CDDP_HIP_REF_DEVICE) { int rc = io_check_pointer(h, desc->path, n * sizeof(double), "cddp_hip_mpc_set_reference_path", "the path"); if (rc) return rc; }
+  else if (!ref_all_finite(desc->path, n)) return fail(-2, "cddp_hip_mpc_set_reference_path: the path holds a non-finite value");
+  { int rc = fork_from_user(h); if (rc) return rc; }
+  // every group stages its copy before any group binds; a failure after that unbinds them all, so the groups never disagree
+  std::vector<double *> staged(h->g.size(), nullptr);
+  for (size_t gi = 0; gi < h->g.size(); ++gi) {
+    int rc = in_stage_path(h->g[gi], desc, &staged[gi]);
+    if (rc) { const std::string err = g_err; for (double *p : staged) if (p) hipFree(p); g_err = err; return rc; }
+  }
+  for (size_t gi = 0; gi < h->g.size(); ++gi) {
+    int rc = in_commit_path(h->g[gi], desc, staged[gi]);
+    if (rc) {
+      const std::string err = g_err;
+      for (size_t k = gi + 1; k < staged.size(); ++k) hipFree(staged[k]);
+      for (Inner *q : h->g) in_unbind_path(q);
+      g_err = err;
+      return rc;
+    }
+  }
+  return io_finish(h);
+}
+
+int cddp_hip_mpc_reference_cursor(cddp_hip_handle *h, int64_t *cursor) {
+  if (!h || !cursor) return fail(-1, "cddp_hip_mpc_reference_cursor: null argument");
+  *cursor = h->g[0]->d_path ? (int64_t)h->g[0]->path_cursor : (int64_t)-1;
+  return 0;
 }
 
 // ---- linear response of the plan to its initial state (inst_sens.hip): forward and adjoint recursions over the A / Bm / K stacks ----

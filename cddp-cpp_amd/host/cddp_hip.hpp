@@ -815,6 +815,39 @@ class HipBatchSolver : public ISolverAlgorithm {
     if (!h_) throw std::runtime_error("cddp_hip: mpcAdvance needs a resident batch (the plug-in route keeps no plan on the device)");
     check(cddp_hip_mpc_advance(h_, mode, flags, x_next));
   }
+  // NEW: move the goal and the per-step reference of the resident batch (cddp_hip_set_reference): x_ref (nx) and / or x_ref_traj ((N + 1) * nx),
+  // nullptr = keep; flags: CDDP_HIP_REF_DEVICE (device pointers), CDDP_HIP_REF_CLEAR_TRAJ (drop the per-step reference).  From the next solve on;
+  // the plan, the solver state and the handle stay.  Refused while a reference path is bound.
+  void setReference(const double *x_ref, const double *x_ref_traj = nullptr, int flags = 0) {
+    if (!h_) throw std::runtime_error("cddp_hip: setReference needs a resident batch (the plug-in route has no resident handle)");
+    check(cddp_hip_set_reference(h_, flags, x_ref, x_ref_traj));
+  }
+  struct Reference { std::vector<double> x_ref, x_ref_traj; bool has_traj = false; };   // nx, (N + 1) * nx (empty without a per-step reference)
+  Reference getReference() {
+    if (!h_) throw std::runtime_error("cddp_hip: getReference needs a resident batch (the plug-in route has no resident handle)");
+    Reference r;
+    int32_t has = 0;
+    r.x_ref.assign((size_t)nx_, 0.0); r.x_ref_traj.assign((size_t)(N_ + 1) * nx_, 0.0);
+    check(cddp_hip_get_reference(h_, r.x_ref.data(), r.x_ref_traj.data(), &has));
+    r.has_traj = has != 0;
+    if (!r.has_traj) r.x_ref_traj.clear();
+    return r;
+  }
+  // NEW: bind a path of `rows` rows of nx doubles to the resident batch (cddp_hip_mpc_set_reference_path): the window of cursor `start` is
+  // installed at once and every mpcAdvance / mpcRun / mpcRunPlant step installs the next one on the device.  path == nullptr unbinds.
+  void setReferencePath(const double *path, int64_t rows, int64_t start = 0, double rows_per_step = 1.0, int flags = 0) {
+    if (!h_) throw std::runtime_error("cddp_hip: setReferencePath needs a resident batch (the plug-in route has no resident handle)");
+    if (!path) { check(cddp_hip_mpc_set_reference_path(h_, nullptr)); return; }
+    cddp_hip_ref_path d{};
+    d.abi_version = CDDP_HIP_ABI_VERSION; d.flags = flags; d.rows = rows; d.start = start; d.rows_per_step = rows_per_step; d.path = path;
+    check(cddp_hip_mpc_set_reference_path(h_, &d));
+  }
+  int64_t referenceCursor() {   // -1: no path bound
+    if (!h_) throw std::runtime_error("cddp_hip: referenceCursor needs a resident batch (the plug-in route has no resident handle)");
+    int64_t c = -1;
+    check(cddp_hip_mpc_reference_cursor(h_, &c));
+    return c;
+  }
   struct MpcLog { std::vector<double> U_applied, X_visited; std::vector<int32_t> iterations, status; cddp_hip_stats stats_sum{}; };   // [b][k][nu], [b][k][nx] (k <= steps), [b][k]
   MpcLog mpcRun(int steps, int mode, int flags = 0) {
     if (!h_) throw std::runtime_error("cddp_hip: mpcRun needs a resident batch (the plug-in route keeps no plan on the device)");

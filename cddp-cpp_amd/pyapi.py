@@ -200,6 +200,17 @@ class PlantDesc(C.Structure):   # cddp_hip_plant_desc
     ]
 
 
+# cddp_hip_set_reference / cddp_hip_mpc_set_reference_path (include/cddp_hip.h, "moving the goal and the per-step reference of a live handle")
+REF_DEVICE, REF_CLEAR_TRAJ = 1, 2
+
+
+class RefPathDesc(C.Structure):   # cddp_hip_ref_path
+    _fields_ = [
+        ("abi_version", C.c_int32), ("flags", C.c_int32), ("rows", C.c_int64), ("start", C.c_int64),
+        ("rows_per_step", C.c_double), ("path", C.c_void_p),   # (a host OR a device address, by the flag: a plain pointer value)
+    ]
+
+
 class MppiDesc(C.Structure):   # cddp_hip_mppi_desc
     _fields_ = [
         ("seed", C.c_uint64), ("stream", C.c_uint32), ("iters", C.c_int32), ("ncand", C.c_int32), ("keep_mean", C.c_int32),
@@ -859,6 +870,10 @@ DEVICE_IO_ARGTYPES = {
     "cddp_hip_mppi_refine": [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
     "cddp_hip_mc_sample_noise": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
     "cddp_hip_plan_montecarlo": [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p] + [C.c_void_p] * 11,
+    "cddp_hip_set_reference": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p],
+    "cddp_hip_get_reference": [C.c_void_p, _dp, _dp, C.POINTER(C.c_int32)],
+    "cddp_hip_mpc_set_reference_path": [C.c_void_p, C.POINTER(RefPathDesc)],
+    "cddp_hip_mpc_reference_cursor": [C.c_void_p, C.POINTER(C.c_int64)],
 }
 
 EXPORTED_SYMBOLS = [
@@ -879,6 +894,7 @@ EXPORTED_SYMBOLS = [
     "cddp_hip_score_rollouts", "cddp_hip_seed_best",
     "cddp_hip_sample_controls", "cddp_hip_mppi_blend", "cddp_hip_mppi_refine",
     "cddp_hip_mc_sample_noise", "cddp_hip_plan_montecarlo",
+    "cddp_hip_set_reference", "cddp_hip_get_reference", "cddp_hip_mpc_set_reference_path", "cddp_hip_mpc_reference_cursor",
 ]
 
 
@@ -1078,6 +1094,72 @@ class HipBatchSolver:
         X = np.zeros((self.B, self.p.N + 1, self.p.nx)); U = np.zeros((self.B, self.p.N, self.p.nu))
         self._check(self.lib.cddp_hip_track_plan(self.h, plant.h if plant is not None else None, _ptr(x0a), _ptr(Wa), _ptr(X), _ptr(U)))
         return X, U
+
+    # ---- moving the goal and the per-step reference of the live handle
+    def _ref_arg(self, name, a, shape, device):
+        """A reference array as a plain address: a numpy array (host) or a float64 tensor on the handle's device."""
+        if a is None:
+            return None, None
+        if device:
+            t = self._device_tensor(name, a, shape)
+            return t, t.data_ptr()
+        k = _arr(a).reshape(shape)
+        return k, k.ctypes.data
+
+    def set_reference(self, x_ref=None, x_ref_traj=None, clear_traj=False):
+        """Replace the goal x_ref (nx,) and / or the per-step reference x_ref_traj (N + 1, nx) of the live handle (cddp_hip_set_reference);
+        None keeps what the handle has, clear_traj drops the per-step reference.  numpy arrays are uploaded (finite values and the rule
+        |x_ref_traj[N] - x_ref| <= 1e-6 are checked); float64 tensors on the handle's device are read in place, ordered on the stream given to
+        set_stream or after a synchronisation of torch's current stream -- all arrays of one call are of one kind.  Takes effect from the next
+        initialize / solve; score_rollouts, mppi_refine, plan_montecarlo and forward use it at once.  Refused while a reference path is bound."""
+        nx, N = self.p.nx, self.p.N
+        given = [a for a in (x_ref, x_ref_traj) if a is not None]
+        device = any(hasattr(a, "data_ptr") for a in given)
+        if device and not all(hasattr(a, "data_ptr") for a in given):
+            raise ValueError("set_reference: x_ref and x_ref_traj must both be numpy arrays or both be device tensors")
+        k0, p0 = self._ref_arg("x_ref", x_ref, (nx,), device)
+        k1, p1 = self._ref_arg("x_ref_traj", x_ref_traj, (N + 1, nx), device)
+        if device:
+            self._order_device_io()
+        flags = (REF_DEVICE if device else 0) | (REF_CLEAR_TRAJ if clear_traj else 0)
+        self._check(self.lib.cddp_hip_set_reference(self.h, flags, p0, p1))
+
+    def get_reference(self):
+        """(x_ref (nx,), x_ref_traj (N + 1, nx) or None): the goal and the per-step reference as the device holds them, what the kernels
+        of the next launch read (cddp_hip_get_reference)."""
+        x = np.zeros(self.p.nx); T = np.zeros((self.p.N + 1, self.p.nx)); has = C.c_int32(0)
+        self._check(self.lib.cddp_hip_get_reference(self.h, _ptr(x), _ptr(T), C.byref(has)))
+        return x, (T if has.value else None)
+
+    def mpc_set_reference_path(self, path, start=0, rows_per_step=1.0):
+        """Bind a path (L, nx) to the handle (cddp_hip_mpc_set_reference_path): the window of cursor `start` becomes the per-step reference
+        and its last row the goal at once, and every mpc_advance -- mpc_run and mpc_run_plant included -- moves the cursor by one and installs
+        the next window on the device.  Window row t of cursor k is the path at (k + t) * rows_per_step, linearly interpolated between rows,
+        the last row past the end.  path: a numpy array (copied) or a float64 device tensor (copied on the device); None unbinds and leaves
+        the reference as it stands."""
+        if path is None:
+            self._check(self.lib.cddp_hip_mpc_set_reference_path(self.h, None))
+            return
+        d = RefPathDesc()
+        d.abi_version = ABI_VERSION; d.start = int(start); d.rows_per_step = float(rows_per_step)
+        if hasattr(path, "data_ptr"):
+            if path.dim() != 2:
+                raise ValueError("path: shape (L, %d) is expected, got %s" % (self.p.nx, tuple(path.shape)))
+            keep = self._device_tensor("path", path, (path.shape[0], self.p.nx))
+            d.flags = REF_DEVICE; d.rows = int(keep.shape[0]); d.path = keep.data_ptr()
+            self._order_device_io()
+        else:
+            keep = _arr(path)
+            if keep.ndim != 2 or keep.shape[1] != self.p.nx:
+                raise ValueError("path: shape (L, %d) is expected, got %s" % (self.p.nx, keep.shape))
+            d.flags = 0; d.rows = int(keep.shape[0]); d.path = keep.ctypes.data if keep.size else None
+        self._check(self.lib.cddp_hip_mpc_set_reference_path(self.h, C.byref(d)))
+
+    def mpc_reference_cursor(self):
+        """The cursor of the window now installed (start + the advances since the path was bound); -1 without a path."""
+        c = C.c_int64(0)
+        self._check(self.lib.cddp_hip_mpc_reference_cursor(self.h, C.byref(c)))
+        return int(c.value)
 
     def gains(self):
         K = np.zeros((self.B, self.p.N, self.p.nu, self.p.nx)); k = np.zeros((self.B, self.p.N, self.p.nu))

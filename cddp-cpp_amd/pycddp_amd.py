@@ -1081,7 +1081,8 @@ class CDDP:                         # cddp_core.hpp:214-423 / bind_solver.cpp:57
                 return None
         return {"CLDDP": api.SOLVER_CLDDP, "IPDDP": api.SOLVER_IPDDP, "LogDDP": api.SOLVER_LOGDDP, "MSIPDDP": api.SOLVER_MSIPDDP}[name]
 
-    def solve_mpc_batch(self, x0s, steps, solver_type=SolverType.IPDDP, warm_start="provided", shift_duals=False, plant=None, disturbances=None):
+    def solve_mpc_batch(self, x0s, steps, solver_type=SolverType.IPDDP, warm_start="provided", shift_duals=False, plant=None, disturbances=None,
+                        reference_path=None, rows_per_step=1.0):
         """NEW (no reference counterpart): `steps` closed-loop MPC steps of one device-resident batch, the model as the plant -- solve, apply
         u_0, start the next solve at x_1 -- without the plan leaving the device between solves (cddp_hip_mpc_run).  Trajectory i starts at
         x0s[i]; the first solve is seeded as solve_batch seeds it.  warm_start names how every later solve is seeded:
@@ -1097,7 +1098,11 @@ class CDDP:                         # cddp_core.hpp:214-423 / bind_solver.cpp:57
         that many steps of timestep / substeps per control interval), "integrator" ("euler", "heun", "rk3", "rk4"), "u_lower" / "u_upper"
         (actuator saturation, as a pair); every key is optional and defaults to the model's value.  disturbances: (B, steps, nx), added
         to the plant's state after every step; needs a plant ({} = the model itself).  control_trajectory then holds the saturated
-        controls and state_trajectory the plant's states."""
+        controls and state_trajectory the plant's states.
+        reference_path (None = the objective's fixed goal and reference states, today's call): (L, nx), a path the run follows
+        (cddp_hip_mpc_set_reference_path) -- solve k tracks the window of rows (k + t) * rows_per_step, t = 0 .. horizon, linearly
+        interpolated between rows and held at the last row past the end, with the window's last row as its goal; the windows are made
+        on the device, one small launch per step."""
         api = _api()
         name = solver_type.value if isinstance(solver_type, SolverType) else str(solver_type)
         modes = {"provided": api.MPC_SHIFT_PROVIDED, "existing": api.MPC_SHIFT_EXISTING, "keep": api.MPC_KEEP_PLAN}
@@ -1127,6 +1132,8 @@ class CDDP:                         # cddp_core.hpp:214-423 / bind_solver.cpp:57
         dp = None
         try:
             hs.set_initial(x0, U0, X0)
+            if reference_path is not None:
+                hs.mpc_set_reference_path(reference_path, 0, rows_per_step)
             if plant is None:
                 r = hs.mpc_run(int(steps), modes[warm_start], shift_duals=shift_duals)
             else:

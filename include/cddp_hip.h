@@ -561,6 +561,60 @@ int cddp_hip_mpc_run_plant(cddp_hip_handle *h, cddp_hip_plant *plant, int steps,
 int cddp_hip_track_plan(cddp_hip_handle *h, cddp_hip_plant *plant, const double *x0 /* B*nx or NULL = row 0 of the plan */,
                         const double *W /* B*N*nx or NULL */, double *X_out /* B*(N+1)*nx */, double *U_out /* B*N*nu */);
 
+/* ---- moving the goal and the per-step reference of a live handle ------------
+ * The objective's goal x_ref and per-step reference x_ref_traj (shared by the batch) can be replaced on a live handle, so a receding-
+ * horizon caller follows a moving set-point or a path without re-creating the handle: the device-resident plan, the solver state and
+ * captured iteration windows stay.  (New entry points; ABI version unchanged; the path descriptor carries its own abi_version.)
+ *
+ * cddp_hip_set_reference replaces the goal (x_ref, nx doubles, NULL = keep) and / or the per-step reference (x_ref_traj, (N+1)*nx doubles,
+ * NULL = keep) in every tile group.  A handle created without a per-step reference gets its buffer on first use and keeps it;
+ * CDDP_HIP_REF_CLEAR_TRAJ puts the running cost back on x_ref.  Semantics:
+ *  - the change takes effect from the next cddp_hip_initialize / cddp_hip_solve, which then equals, bit for bit, the same call on a handle
+ *    created with the new reference and brought to the same state; the scalars of the current iterate (cost, merit) stay those evaluated
+ *    under the old reference until then;
+ *  - entries that evaluate the objective on the spot use the new reference at once: cddp_hip_score_rollouts, cddp_hip_mppi_refine,
+ *    cddp_hip_plan_montecarlo, cddp_hip_forward;
+ *  - terminal-constraint targets are separate data and are not touched;
+ *  - ordering: as every other setter, on the handle's stream.  Host pointers: the call returns after the upload.  CDDP_HIP_REF_DEVICE:
+ *    device pointers, checked and ordered as cddp_hip_set_initial_device's -- on a stream given by cddp_hip_set_stream the call does not block;
+ *  - the reference's constructor rule (objective.cpp:55-63), || x_ref_traj[N] - x_ref ||_2 <= 1e-6, is enforced on the state the call would
+ *    leave behind when the pointers are host pointers.  With CDDP_HIP_REF_DEVICE the contents are not read by the host: the rule, and finite
+ *    values, are the caller's responsibility.
+ * Refused, each with its own message, nothing launched and nothing changed: a NULL handle; an unknown flag; CDDP_HIP_REF_CLEAR_TRAJ together
+ * with an x_ref_traj; a call that changes nothing (no x_ref, no x_ref_traj, no CDDP_HIP_REF_CLEAR_TRAJ); a device pointer that is not memory
+ * of the handle's device or too short; a non-finite host value; the last-row rule; a handle with a reference path bound (unbind first).
+ *
+ * cddp_hip_get_reference reads back from the device exactly what the kernels will read: x_ref (nx), x_ref_traj ((N+1)*nx, left untouched
+ * when the handle has no per-step reference) and *has_traj (1 / 0).  Any output may be NULL.  Host pointers.
+ *
+ * cddp_hip_mpc_set_reference_path binds a path of L rows to the handle: the rows are copied into device memory the handle owns, the window
+ * of cursor `start` is installed at once, and from then on EVERY cddp_hip_mpc_advance (all three modes; cddp_hip_mpc_run and
+ * cddp_hip_mpc_run_plant go through it) moves the cursor by one and installs the next window before it returns -- one small kernel per tile
+ * group on the group's stream, no upload.  Window of cursor k, rows t = 0 .. N (the library is built without FMA contraction):
+ *     pos = (double)(k + t) * rows_per_step;  i = floor(pos);  a = pos - i;
+ *     row t = path[L-1]                                  when i >= L-1  (past the end of the path the window holds the last row),
+ *     row t[e] = p_i[e] + a * (p_{i+1}[e] - p_i[e])        otherwise      (with a == 0 this is p_i[e]);
+ *     the goal x_ref becomes row N of the window (the last-row rule holds exactly).
+ * Every element is blended alike: wrapping angles is the caller's business.  desc == NULL unbinds: the reference is left as it stands and
+ * cddp_hip_set_reference is accepted again.  Binding again replaces the path and the cursor.  With host rows the call returns after the
+ * upload and refuses non-finite values; with CDDP_HIP_REF_DEVICE the rows are checked as a device pointer and copied on the handle's stream.
+ * Refused: a NULL handle; a wrong abi_version; an unknown flag; rows < 1; start < 0; rows_per_step not finite or <= 0; a NULL path.
+ * cddp_hip_mpc_reference_cursor: the cursor of the window now installed (start + the advances since), -1 when no path is bound. */
+enum { CDDP_HIP_REF_DEVICE = 1,      /* pointers are device pointers, checked and ordered as cddp_hip_set_initial_device's */
+       CDDP_HIP_REF_CLEAR_TRAJ = 2 };/* drop the per-step reference: running cost back on x_ref (x_ref_traj must be NULL) */
+int cddp_hip_set_reference(cddp_hip_handle *h, int flags, const double *x_ref /* nx or NULL = keep */,
+                           const double *x_ref_traj /* (N+1)*nx or NULL = keep */);
+int cddp_hip_get_reference(cddp_hip_handle *h, double *x_ref /* nx */, double *x_ref_traj /* (N+1)*nx */, int32_t *has_traj);
+typedef struct cddp_hip_ref_path {
+  int32_t abi_version, flags;   /* CDDP_HIP_ABI_VERSION; CDDP_HIP_REF_DEVICE or 0 */
+  int64_t rows;                 /* L >= 1 */
+  int64_t start;                /* cursor k0 >= 0 */
+  double rows_per_step;         /* > 0, finite; 1.0: window row t of step k is path row k + t exactly */
+  const double *path;           /* [L][nx]; copied, need not outlive the call */
+} cddp_hip_ref_path;            /* 40 bytes */
+int cddp_hip_mpc_set_reference_path(cddp_hip_handle *h, const cddp_hip_ref_path *desc /* NULL: unbind, reference left as it stands */);
+int cddp_hip_mpc_reference_cursor(cddp_hip_handle *h, int64_t *cursor /* -1: no path bound */);
+
 /* ---- getters (host buffers, batch-major) -------------------------------- */
 int cddp_hip_get_results(cddp_hip_handle *h, cddp_hip_result *results /* batch */);
 /* Head of the plan (round 4): u_0[batch][nu] and x_1[batch][nx] of every trajectory's current iterate -- what a receding-horizon
