@@ -814,6 +814,9 @@ static void from_t4(const double *src, double *dst, int B, int Bp, int T, int E)
       for (int e = 0; e < E; ++e) dst[((size_t)b * T + t) * E + e] = src[((((size_t)t * NB16 + (size_t)(b >> 2)) * (size_t)E + (size_t)e) * 4) + (size_t)(b & 3)];
 }
 
+// a new initial trajectory lies in d_Xinit / d_Uinit: the next initialize is cold and starts from it
+static void mark_seeded(Inner *q) { q->have_initial = true; q->initialized = false; q->initial_dirty = true; }
+
 static int in_set_initial(Inner *h, const double *x0, const double *U0, const double *X0) {
   if (!h || !x0) return fail(-1, "null argument");
   HIPCHK(hipSetDevice(h->device));
@@ -831,9 +834,7 @@ static int in_set_initial(Inner *h, const double *x0, const double *U0, const do
   HIPCHK(hipMemcpyAsync(h->d_Xinit, hx.data(), hx.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
   HIPCHK(hipMemcpyAsync(h->d_Uinit, hu.data(), hu.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
-  h->have_initial = true;
-  h->initialized = false;
-  h->initial_dirty = true;
+  mark_seeded(h);
   return 0;
 }
 
@@ -1890,7 +1891,8 @@ struct cddp_hip_handle {
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
   void *d_send = nullptr;              // send buffer of cddp_hip_allgather_results (shard_capacity records)
   int send_cap = 0;
-  double *d_score = nullptr; size_t score_cap = 0;   // cddp_hip_score_rollouts / cddp_hip_seed_best: staging of host arrays, grown on demand
+  char *d_staging = nullptr; size_t staging_cap = 0;   // the staging scratch of the host-or-device entries (struct Staging), in bytes, grown on demand
+  bool staging_busy = false;                           // a call that used it returned without synchronising: the next acquisition waits for the group streams
   int32_t *d_winner = nullptr;                       // cddp_hip_seed_best: winner[B], the gather index of the seed
 };
 
@@ -1966,6 +1968,14 @@ static int drive_runs(SolveRun *run, int n) {
   return 0;
 }
 
+// one solve's statistics added to the totals of an MPC run (timing_detail is a setting, not a sum)
+static void stats_add(cddp_hip_stats *sum, const cddp_hip_stats &st) {
+  sum->solve_ms += st.solve_ms; sum->backward_ms += st.backward_ms; sum->forward_ms += st.forward_ms; sum->update_ms += st.update_ms;
+  sum->sweeps += st.sweeps; sum->rollouts += st.rollouts; sum->rollouts_launched += st.rollouts_launched;
+  sum->traj_iterations += st.traj_iterations; sum->outer_iterations += st.outer_iterations; sum->n_converged += st.n_converged;
+  sum->kernel_launches += st.kernel_launches; sum->timing_detail = st.timing_detail; sum->rollout_steps += st.rollout_steps;
+}
+
 extern "C" {
 
 int cddp_hip_create(const cddp_hip_problem *problem, int batch, int device, cddp_hip_handle **out) {
@@ -2010,7 +2020,7 @@ int cddp_hip_destroy(cddp_hip_handle *h) {
   if (h->ev_fork) { hipEventDestroy(h->ev_fork); hipEventDestroy(h->ev_join); }
   for (int k = 0; k < 2; ++k) if (h->ev_pp[k]) hipEventDestroy(h->ev_pp[k]);
   if (h->d_send) hipFree(h->d_send);
-  if (h->d_score) hipFree(h->d_score);
+  if (h->d_staging) hipFree(h->d_staging);
   if (h->d_winner) hipFree(h->d_winner);
   delete h;
   return 0;
@@ -2296,6 +2306,90 @@ static int io_finish(cddp_hip_handle *h) {
   return join_to_user(h);
 }
 
+// ---- staging of array arguments that are host pointers, or device pointers under the entry's *_DEVICE flag ----
+// THE SCRATCH RULE.  h->d_staging is the handle's one staging scratch: grow-only, kept until cddp_hip_destroy, used by every entry below.
+// It belongs to the call that acquired it until that call's work on the group streams is known to have completed.  The host forms and a
+// device form without a caller's stream synchronise before they return; a device form on the stream of cddp_hip_set_stream does not (nor
+// does a call that failed half-way), so the scratch stays marked busy and the NEXT acquisition first synchronises the group streams --
+// the streams are non-blocking (make_stream), a null-stream hipMemcpy into the scratch would not wait for them by itself.
+static int staging_acquire(cddp_hip_handle *h, size_t bytes) {
+  if (h->staging_busy) { for (Inner *q : h->g) HIPCHK(hipStreamSynchronize(q->stream)); h->staging_busy = false; }
+  if (h->staging_cap < bytes) {
+    if (h->d_staging) hipFree(h->d_staging);
+    h->d_staging = nullptr; h->staging_cap = 0;
+    HIPCHK(hipMalloc((void **)&h->d_staging, bytes));
+    h->staging_cap = bytes;
+  }
+  h->staging_busy = true;
+  return 0;
+}
+
+// An entry declares its arrays in argument order; every declaration names the pointer variable ("slot") the kernels are to use, which
+// begin() fills.  Device form: the caller's pointers, each checked by io_check_pointer in declaration order; scratch only for the
+// internal blocks.  Host form: every array is a block of the scratch (8-byte aligned, carried by its byte count); begin() uploads the
+// inputs, finish() synchronises and downloads the outputs.  An absent (NULL) array yields a NULL slot and is otherwise ignored.
+}  // extern "C" (reopened below: the declarations are templates)
+struct Staging {
+  struct Arr { const char *name; const void *caller; size_t bytes; void *slot; size_t off; int dir; };   // dir: +1 input, -1 output, 0 internal
+  static constexpr size_t kNoBlock = ~(size_t)0;                                                         // off of an array that owns no block
+  cddp_hip_handle *h; const char *me; bool dev;
+  std::vector<Arr> arr;
+  size_t total = 0;
+  Staging(cddp_hip_handle *h_, const char *me_, bool dev_) : h(h_), me(me_), dev(dev_) {}
+  static void put(void *slot, const void *p) { std::memcpy(slot, &p, sizeof(p)); }
+  static void *get(const void *slot) { void *p; std::memcpy(&p, slot, sizeof(p)); return p; }
+  void add(const char *name, const void *caller, size_t bytes, void *slot, int dir, bool own) {
+    if (dir != 0 && !caller) { if (own) put(slot, nullptr); return; }
+    const bool block = own && (dir == 0 || !dev);
+    if (own && !block) put(slot, caller);
+    arr.push_back(Arr{name, caller, bytes, slot, block ? total : kNoBlock, dir});
+    if (block) total += (bytes + 7) & ~(size_t)7;
+  }
+  template <class T> void in(const char *name, const T *p, size_t bytes, const T **slot) { add(name, p, bytes, slot, +1, true); }
+  template <class T> void out(const char *name, T *p, size_t bytes, T **slot) { add(name, p, bytes, slot, -1, true); }
+  template <class T> void scratch(size_t bytes, T **slot) { add(nullptr, nullptr, bytes, slot, 0, true); }
+  // a caller's array that lives in an internal block (*block, declared before): the host form uploads to / downloads from the block,
+  // the device form only checks the pointer -- the entry copies device to device, per group on the group's stream
+  template <class T> void in_via(const char *name, const T *p, size_t bytes, T *const *block) { add(name, p, bytes, (void *)block, +1, false); }
+  template <class T> void out_via(const char *name, T *p, size_t bytes, T *const *block) { add(name, p, bytes, (void *)block, -1, false); }
+  // everything that precedes fork_from_user
+  int begin() {
+    if (dev) for (const Arr &a : arr) if (a.caller) { int rc = io_check_pointer(h, a.caller, a.bytes, me, a.name); if (rc) return rc; }
+    if (total) { int rc = staging_acquire(h, total); if (rc) return rc; }
+    for (const Arr &a : arr) if (a.off != kNoBlock) put(a.slot, h->d_staging + a.off);
+    if (!dev) for (const Arr &a : arr) if (a.dir > 0) HIPCHK(hipMemcpy(get(a.slot), a.caller, a.bytes, hipMemcpyHostToDevice));
+    return 0;
+  }
+  // everything that follows the loop over the tile groups
+  int finish() {
+    if (dev) { int rc = io_finish(h); if (rc) return rc; }
+    else {
+      HIPCHK(hipGetLastError());
+      for (Inner *q : h->g) HIPCHK(hipStreamSynchronize(q->stream));
+      for (const Arr &a : arr) if (a.dir < 0) HIPCHK(hipMemcpy(const_cast<void *>(a.caller), get(a.slot), a.bytes, hipMemcpyDeviceToHost));
+    }
+    if (!dev || !h->have_user_stream) h->staging_busy = false;   // the group streams were synchronised
+    return dev ? 0 : join_to_user(h);
+  }
+};
+extern "C" {
+
+// the handle's own model as a plant: one step of dt, no box, the derived block of the ProblemDev on the device
+static PlantDev own_model_plant(const Inner *q) {
+  PlantDev pd;
+  std::memset(&pd, 0, sizeof(pd));
+  pd.model = q->P.model; pd.integrator = q->P.integrator; pd.substeps = 1; pd.nx = q->P.nx; pd.nu = q->P.nu; pd.Bp = q->d.Bp; pd.h = q->P.dt;
+  pd.params = (const double *)((const char *)q->dP + offsetof(ProblemDev, mp));
+  return pd;
+}
+
+// the result of a launch that picks its kernel by the plant's model id (what: "scoring" / "sampling"): hipErrorInvalidValue = no such kernel
+static int plant_launch_rc(hipError_t e, const char *me, const char *what, const PlantDev &pd) {
+  if (e == hipErrorInvalidValue) return fail(-3, "%s: the library has no %s kernel for model id %d with nx = %d, nu = %d", me, what, pd.model, pd.nx, pd.nu);
+  HIPCHK(e);
+  return 0;
+}
+
 // which plane of the slotted fields holds every trajectory's current iterate (the slot rule the slotted getters follow), for tests and diagnosis
 int cddp_hip_get_live_slots(cddp_hip_handle *h, int32_t *slots, int32_t *n_slots) {
   if (!h) return fail(-1, "null handle");
@@ -2366,7 +2460,7 @@ int cddp_hip_set_initial_device(cddp_hip_handle *h, const double *x0_dev, const 
     const size_t b0 = (size_t)h->b0[gi];
     io_tile(X0_dev ? X0_dev + b0 * nX : nullptr, x0_dev + b0 * h->nx, q->d.B, q->d.NB, h->N + 1, h->nx, q->d_Xinit, q->stream);
     io_tile(U0_dev ? U0_dev + b0 * nU : nullptr, nullptr, q->d.B, q->d.NB, h->N, h->nu, q->d_Uinit, q->stream);
-    q->have_initial = true; q->initialized = false; q->initial_dirty = true;   // as in_set_initial leaves them
+    mark_seeded(q);
   }
   return io_finish(h);
 }
@@ -2503,12 +2597,6 @@ static SensStacks sens_stacks(const Inner *q) {
   const DevBuf &d = q->d;
   return SensStacks{d.A, d.Bm, d.K, q->route.t4 ? cddp_io::kT4 : cddp_io::kTiled, d.B, d.NB, d.N, q->P.nx, q->P.nu};   // (io_field: the layout of A / Bm)
 }
-// a temporary device array of a host-pointer call, freed when the call returns
-struct SensTmp {
-  double *p = nullptr;
-  ~SensTmp() { if (p) (void)hipFree(p); }
-  int alloc(size_t n) { HIPCHK(hipMalloc((void **)&p, n * sizeof(double))); return 0; }
-};
 
 int cddp_hip_plan_jvp(cddp_hip_handle *h, int flags, int nvec, const double *dx0, double *dX, double *dU) {
   static const char *const me = "cddp_hip_plan_jvp";
@@ -2518,32 +2606,19 @@ int cddp_hip_plan_jvp(cddp_hip_handle *h, int flags, int nvec, const double *dx0
   { int rc = sens_refuse_handle(me, h); if (rc) return rc; }
   HIPCHK(hipSetDevice(h->device));
   const size_t n0 = (size_t)nvec * h->nx, nX = (size_t)nvec * (h->N + 1) * h->nx, nU = (size_t)nvec * h->N * h->nu, B = (size_t)h->B;
-  const bool dev = (flags & CDDP_HIP_SENS_DEVICE) != 0;
-  SensTmp t0, tX, tU;
-  const double *d0 = dx0; double *dXd = dX, *dUd = dU;
-  if (dev) {
-    { int rc = io_check_pointer(h, dx0, B * n0 * sizeof(double), me, "dx0"); if (rc) return rc; }
-    if (dX) { int rc = io_check_pointer(h, dX, B * nX * sizeof(double), me, "dX"); if (rc) return rc; }
-    if (dU) { int rc = io_check_pointer(h, dU, B * nU * sizeof(double), me, "dU"); if (rc) return rc; }
-  } else {
-    { int rc = t0.alloc(B * n0); if (rc) return rc; }
-    HIPCHK(hipMemcpy(t0.p, dx0, B * n0 * sizeof(double), hipMemcpyHostToDevice));
-    d0 = t0.p;
-    if (dX) { int rc = tX.alloc(B * nX); if (rc) return rc; dXd = tX.p; }
-    if (dU) { int rc = tU.alloc(B * nU); if (rc) return rc; dUd = tU.p; }
-  }
+  Staging st(h, me, (flags & CDDP_HIP_SENS_DEVICE) != 0);
+  const double *d0; double *dXd, *dUd;
+  st.in("dx0", dx0, B * n0 * sizeof(double), &d0);
+  st.out("dX", dX, B * nX * sizeof(double), &dXd);
+  st.out("dU", dU, B * nU * sizeof(double), &dUd);
+  { int rc = st.begin(); if (rc) return rc; }
   { int rc = fork_from_user(h); if (rc) return rc; }
   for (size_t gi = 0; gi < h->g.size(); ++gi) {
     const Inner *q = h->g[gi];
     const size_t b0 = (size_t)h->b0[gi];
     HIPCHK(sens_jvp(sens_stacks(q), nvec, d0 + b0 * n0, dXd ? dXd + b0 * nX : nullptr, dUd ? dUd + b0 * nU : nullptr, q->stream));
   }
-  if (dev) return io_finish(h);
-  HIPCHK(hipGetLastError());
-  for (Inner *q : h->g) HIPCHK(hipStreamSynchronize(q->stream));
-  if (dX) HIPCHK(hipMemcpy(dX, tX.p, B * nX * sizeof(double), hipMemcpyDeviceToHost));
-  if (dU) HIPCHK(hipMemcpy(dU, tU.p, B * nU * sizeof(double), hipMemcpyDeviceToHost));
-  return join_to_user(h);
+  return st.finish();
 }
 
 int cddp_hip_plan_vjp(cddp_hip_handle *h, int flags, int nvec, const double *gX, const double *gU, double *gx0) {
@@ -2553,30 +2628,19 @@ int cddp_hip_plan_vjp(cddp_hip_handle *h, int flags, int nvec, const double *gX,
   { int rc = sens_refuse_handle(me, h); if (rc) return rc; }
   HIPCHK(hipSetDevice(h->device));
   const size_t n0 = (size_t)nvec * h->nx, nX = (size_t)nvec * (h->N + 1) * h->nx, nU = (size_t)nvec * h->N * h->nu, B = (size_t)h->B;
-  const bool dev = (flags & CDDP_HIP_SENS_DEVICE) != 0;
-  SensTmp t0, tX, tU;
-  const double *gXd = gX, *gUd = gU; double *g0 = gx0;
-  if (dev) {
-    if (gX) { int rc = io_check_pointer(h, gX, B * nX * sizeof(double), me, "gX"); if (rc) return rc; }
-    if (gU) { int rc = io_check_pointer(h, gU, B * nU * sizeof(double), me, "gU"); if (rc) return rc; }
-    { int rc = io_check_pointer(h, gx0, B * n0 * sizeof(double), me, "gx0"); if (rc) return rc; }
-  } else {
-    { int rc = t0.alloc(B * n0); if (rc) return rc; }
-    g0 = t0.p;
-    if (gX) { int rc = tX.alloc(B * nX); if (rc) return rc; HIPCHK(hipMemcpy(tX.p, gX, B * nX * sizeof(double), hipMemcpyHostToDevice)); gXd = tX.p; }
-    if (gU) { int rc = tU.alloc(B * nU); if (rc) return rc; HIPCHK(hipMemcpy(tU.p, gU, B * nU * sizeof(double), hipMemcpyHostToDevice)); gUd = tU.p; }
-  }
+  Staging st(h, me, (flags & CDDP_HIP_SENS_DEVICE) != 0);
+  const double *gXd, *gUd; double *g0;
+  st.in("gX", gX, B * nX * sizeof(double), &gXd);
+  st.in("gU", gU, B * nU * sizeof(double), &gUd);
+  st.out("gx0", gx0, B * n0 * sizeof(double), &g0);
+  { int rc = st.begin(); if (rc) return rc; }
   { int rc = fork_from_user(h); if (rc) return rc; }
   for (size_t gi = 0; gi < h->g.size(); ++gi) {
     const Inner *q = h->g[gi];
     const size_t b0 = (size_t)h->b0[gi];
     HIPCHK(sens_vjp(sens_stacks(q), nvec, gXd ? gXd + b0 * nX : nullptr, gUd ? gUd + b0 * nU : nullptr, g0 + b0 * n0, q->stream));
   }
-  if (dev) return io_finish(h);
-  HIPCHK(hipGetLastError());
-  for (Inner *q : h->g) HIPCHK(hipStreamSynchronize(q->stream));
-  HIPCHK(hipMemcpy(gx0, t0.p, B * n0 * sizeof(double), hipMemcpyDeviceToHost));
-  return join_to_user(h);
+  return st.finish();
 }
 
 // ---- state and control covariance along the plan (inst_cov.hip): the closed-loop covariance recursion over the A / Bm / K stacks ----
@@ -2593,24 +2657,15 @@ int cddp_hip_plan_covariance(cddp_hip_handle *h, int flags, const double *Sigma0
   const size_t nx = (size_t)h->nx, nu = (size_t)h->nu, B = (size_t)h->B;
   const size_t nS = (per ? B : 1) * nx * nx, nWu = (per ? B : 1) * nu * nu;                       // doubles of Sigma0 / W, of Wu
   const size_t eX = (size_t)(h->N + 1) * (diag ? nx : nx * nx), eU = (size_t)h->N * (diag ? nu : nu * nu);   // doubles per trajectory of SX, of SU
-  SensTmp t0, tW, tWu, tX, tU, tc;
-  const double *S0d = Sigma0, *Wd = W, *Wud = Wu; double *SXd = SX, *SUd = SU, *dcd = dcost;
-  if (dev) {
-    { int rc = io_check_pointer(h, Sigma0, nS * sizeof(double), me, "Sigma0"); if (rc) return rc; }
-    if (W) { int rc = io_check_pointer(h, W, nS * sizeof(double), me, "W"); if (rc) return rc; }
-    if (Wu) { int rc = io_check_pointer(h, Wu, nWu * sizeof(double), me, "Wu"); if (rc) return rc; }
-    if (SX) { int rc = io_check_pointer(h, SX, B * eX * sizeof(double), me, "SX"); if (rc) return rc; }
-    if (SU) { int rc = io_check_pointer(h, SU, B * eU * sizeof(double), me, "SU"); if (rc) return rc; }
-    if (dcost) { int rc = io_check_pointer(h, dcost, B * sizeof(double), me, "dcost"); if (rc) return rc; }
-  } else {
-    { int rc = t0.alloc(nS); if (rc) return rc; }
-    HIPCHK(hipMemcpy(t0.p, Sigma0, nS * sizeof(double), hipMemcpyHostToDevice)); S0d = t0.p;
-    if (W) { int rc = tW.alloc(nS); if (rc) return rc; HIPCHK(hipMemcpy(tW.p, W, nS * sizeof(double), hipMemcpyHostToDevice)); Wd = tW.p; }
-    if (Wu) { int rc = tWu.alloc(nWu); if (rc) return rc; HIPCHK(hipMemcpy(tWu.p, Wu, nWu * sizeof(double), hipMemcpyHostToDevice)); Wud = tWu.p; }
-    if (SX) { int rc = tX.alloc(B * eX); if (rc) return rc; SXd = tX.p; }
-    if (SU) { int rc = tU.alloc(B * eU); if (rc) return rc; SUd = tU.p; }
-    if (dcost) { int rc = tc.alloc(B); if (rc) return rc; dcd = tc.p; }
-  }
+  Staging st(h, me, dev);
+  const double *S0d, *Wd, *Wud; double *SXd, *SUd, *dcd;
+  st.in("Sigma0", Sigma0, nS * sizeof(double), &S0d);
+  st.in("W", W, nS * sizeof(double), &Wd);
+  st.in("Wu", Wu, nWu * sizeof(double), &Wud);
+  st.out("SX", SX, B * eX * sizeof(double), &SXd);
+  st.out("SU", SU, B * eU * sizeof(double), &SUd);
+  st.out("dcost", dcost, B * sizeof(double), &dcd);
+  { int rc = st.begin(); if (rc) return rc; }
   { int rc = fork_from_user(h); if (rc) return rc; }
   for (size_t gi = 0; gi < h->g.size(); ++gi) {
     const Inner *q = h->g[gi];
@@ -2623,13 +2678,7 @@ int cddp_hip_plan_covariance(cddp_hip_handle *h, int flags, const double *Sigma0
     a.per_traj = per ? 1 : 0; a.diag = diag ? 1 : 0;
     HIPCHK(plan_cov(sens_stacks(q), a, q->stream));
   }
-  if (dev) return io_finish(h);
-  HIPCHK(hipGetLastError());
-  for (Inner *q : h->g) HIPCHK(hipStreamSynchronize(q->stream));
-  if (SX) HIPCHK(hipMemcpy(SX, tX.p, B * eX * sizeof(double), hipMemcpyDeviceToHost));
-  if (SU) HIPCHK(hipMemcpy(SU, tU.p, B * eU * sizeof(double), hipMemcpyDeviceToHost));
-  if (dcost) HIPCHK(hipMemcpy(dcost, tc.p, B * sizeof(double), hipMemcpyDeviceToHost));
-  return join_to_user(h);
+  return st.finish();
 }
 
 int cddp_hip_mpc_run(cddp_hip_handle *h, int steps, int mode, int flags, double *U_applied, double *X_visited, int32_t *iterations, int32_t *status,
@@ -2647,12 +2696,7 @@ int cddp_hip_mpc_run(cddp_hip_handle *h, int steps, int mode, int flags, double 
     cddp_hip_stats st;
     rc_run = cddp_hip_solve(h, stats_sum ? &st : nullptr);
     if (rc_run) break;
-    if (stats_sum) {
-      stats_sum->solve_ms += st.solve_ms; stats_sum->backward_ms += st.backward_ms; stats_sum->forward_ms += st.forward_ms; stats_sum->update_ms += st.update_ms;
-      stats_sum->sweeps += st.sweeps; stats_sum->rollouts += st.rollouts; stats_sum->rollouts_launched += st.rollouts_launched;
-      stats_sum->traj_iterations += st.traj_iterations; stats_sum->outer_iterations += st.outer_iterations; stats_sum->n_converged += st.n_converged;
-      stats_sum->kernel_launches += st.kernel_launches; stats_sum->timing_detail = st.timing_detail; stats_sum->rollout_steps += st.rollout_steps;
-    }
+    if (stats_sum) stats_add(stats_sum, st);
     for (Inner *q : h->g) { rc_run = in_mpc_log(q, steps, k); if (rc_run) break; }
     if (rc_run) break;
     rc_run = cddp_hip_mpc_advance(h, mode, flags, nullptr);
@@ -2856,12 +2900,7 @@ int cddp_hip_mpc_run_plant(cddp_hip_handle *h, cddp_hip_plant *plant, int steps,
     cddp_hip_stats st;
     rc_run = cddp_hip_solve(h, stats_sum ? &st : nullptr);
     if (rc_run) break;
-    if (stats_sum) {
-      stats_sum->solve_ms += st.solve_ms; stats_sum->backward_ms += st.backward_ms; stats_sum->forward_ms += st.forward_ms; stats_sum->update_ms += st.update_ms;
-      stats_sum->sweeps += st.sweeps; stats_sum->rollouts += st.rollouts; stats_sum->rollouts_launched += st.rollouts_launched;
-      stats_sum->traj_iterations += st.traj_iterations; stats_sum->outer_iterations += st.outer_iterations; stats_sum->n_converged += st.n_converged;
-      stats_sum->kernel_launches += st.kernel_launches; stats_sum->timing_detail = st.timing_detail; stats_sum->rollout_steps += st.rollout_steps;
-    }
+    if (stats_sum) stats_add(stats_sum, st);
     // per group, on its stream: iterations and status (and the model's own head, which the plant's rows then replace), the plant on row 0
     // of the live slot, the advance from the staged x_next -- no synchronisation, the next solve is ordered behind them
     for (Inner *q : h->g) { rc_run = in_mpc_check(q, mode, aflags); if (rc_run) break; }
@@ -2919,16 +2958,6 @@ int cddp_hip_track_plan(cddp_hip_handle *h, cddp_hip_plant *plant, const double 
 }
 
 // ---- scoring candidate control sequences (inst_score.hip) and seeding from the best of them ----
-// the handle's staging buffer of the host-pointer forms: at least n doubles
-static int score_scratch(cddp_hip_handle *h, size_t n) {
-  if (h->score_cap >= n) return 0;
-  if (h->d_score) hipFree(h->d_score);
-  h->d_score = nullptr; h->score_cap = 0;
-  HIPCHK(hipMalloc((void **)&h->d_score, n * sizeof(double)));
-  h->score_cap = n;
-  return 0;
-}
-
 int cddp_hip_score_rollouts(cddp_hip_handle *h, cddp_hip_plant *plant, int flags, int ncand, const double *x0, const double *U,
                             double *cost, double *viol, double *X_out, double *U_out) {
   static const char *const me = "cddp_hip_score_rollouts";
@@ -2947,54 +2976,29 @@ int cddp_hip_score_rollouts(cddp_hip_handle *h, cddp_hip_plant *plant, int flags
   if (((size_t)((h->B + 63) / 64 * 64) * S + 63) / 64 > 0x7fffffffull) return fail(-2, "%s: batch * ncand = %zu exceeds what one launch holds", me, B * S);
   HIPCHK(hipSetDevice(h->device));
   const size_t n0 = xpc ? S * nx : nx, nU = S * N * nu, nX = S * (N + 1) * nx;   // per trajectory
-  const double *x0d = x0, *Ud = U;
-  double *costd = cost, *viold = viol, *Xd = X_out, *Uod = U_out;
-  if (dev) {
-    if (x0) { int rc = io_check_pointer(h, x0, B * n0 * sizeof(double), me, "x0"); if (rc) return rc; }
-    if (U) { int rc = io_check_pointer(h, U, B * nU * sizeof(double), me, "U"); if (rc) return rc; }
-    { int rc = io_check_pointer(h, cost, B * S * sizeof(double), me, "cost"); if (rc) return rc; }
-    if (viol) { int rc = io_check_pointer(h, viol, B * S * sizeof(double), me, "viol"); if (rc) return rc; }
-    if (X_out) { int rc = io_check_pointer(h, X_out, B * nX * sizeof(double), me, "X_out"); if (rc) return rc; }
-    if (U_out) { int rc = io_check_pointer(h, U_out, B * nU * sizeof(double), me, "U_out"); if (rc) return rc; }
-  } else {
-    const size_t total = B * ((x0 ? n0 : 0) + (U ? nU : 0) + S + (viol ? S : 0) + (X_out ? nX : 0) + (U_out ? nU : 0));
-    { int rc = score_scratch(h, total); if (rc) return rc; }
-    double *top = h->d_score;
-    if (x0) { HIPCHK(hipMemcpy(top, x0, B * n0 * sizeof(double), hipMemcpyHostToDevice)); x0d = top; top += B * n0; }
-    if (U) { HIPCHK(hipMemcpy(top, U, B * nU * sizeof(double), hipMemcpyHostToDevice)); Ud = top; top += B * nU; }
-    costd = top; top += B * S;
-    if (viol) { viold = top; top += B * S; }
-    if (X_out) { Xd = top; top += B * nX; }
-    if (U_out) { Uod = top; top += B * nU; }
-  }
+  Staging st(h, me, dev);
+  const double *x0d, *Ud;
+  double *costd, *viold, *Xd, *Uod;
+  st.in("x0", x0, B * n0 * sizeof(double), &x0d);
+  st.in("U", U, B * nU * sizeof(double), &Ud);
+  st.out("cost", cost, B * S * sizeof(double), &costd);
+  st.out("viol", viol, B * S * sizeof(double), &viold);
+  st.out("X_out", X_out, B * nX * sizeof(double), &Xd);
+  st.out("U_out", U_out, B * nU * sizeof(double), &Uod);
+  { int rc = st.begin(); if (rc) return rc; }
   { int rc = fork_from_user(h); if (rc) return rc; }
   for (size_t gi = 0; gi < h->g.size(); ++gi) {
     const Inner *q = h->g[gi];
     const size_t b0 = (size_t)h->b0[gi];
-    PlantDev pd;
-    if (plant) pd = plant->pd;
-    else {   // the handle's own model as a plant: one step of dt, no box, the derived block of the ProblemDev on the device
-      std::memset(&pd, 0, sizeof(pd));
-      pd.model = q->P.model; pd.integrator = q->P.integrator; pd.substeps = 1; pd.nx = q->P.nx; pd.nu = q->P.nu; pd.Bp = q->d.Bp; pd.h = q->P.dt;
-      pd.params = (const double *)((const char *)q->dP + offsetof(ProblemDev, mp));
-    }
+    const PlantDev pd = plant ? plant->pd : own_model_plant(q);
     ScoreArgs a;
     a.S = ncand; a.b0 = (int)b0; a.feedback = fb ? 1 : 0; a.x0_per_cand = xpc ? 1 : 0;
     a.x0 = x0d ? x0d + b0 * n0 : nullptr; a.U = Ud ? Ud + b0 * nU : nullptr;
     a.cost = costd + b0 * S; a.viol = viold ? viold + b0 * S : nullptr;
     a.X_out = Xd ? Xd + b0 * nX : nullptr; a.U_out = Uod ? Uod + b0 * nU : nullptr;
-    const hipError_t e = score_launch(pd, q->d, a, q->stream);
-    if (e == hipErrorInvalidValue) return fail(-3, "%s: the library has no scoring kernel for model id %d with nx = %d, nu = %d", me, pd.model, pd.nx, pd.nu);
-    HIPCHK(e);
+    { int rc = plant_launch_rc(score_launch(pd, q->d, a, q->stream), me, "scoring", pd); if (rc) return rc; }
   }
-  if (dev) return io_finish(h);
-  HIPCHK(hipGetLastError());
-  for (Inner *q : h->g) HIPCHK(hipStreamSynchronize(q->stream));
-  HIPCHK(hipMemcpy(cost, costd, B * S * sizeof(double), hipMemcpyDeviceToHost));
-  if (viol) HIPCHK(hipMemcpy(viol, viold, B * S * sizeof(double), hipMemcpyDeviceToHost));
-  if (X_out) HIPCHK(hipMemcpy(X_out, Xd, B * nX * sizeof(double), hipMemcpyDeviceToHost));
-  if (U_out) HIPCHK(hipMemcpy(U_out, Uod, B * nU * sizeof(double), hipMemcpyDeviceToHost));
-  return join_to_user(h);
+  return st.finish();
 }
 
 int cddp_hip_seed_best(cddp_hip_handle *h, int flags, int ncand, const double *x0, const double *U, const double *cost, const double *viol,
@@ -3009,21 +3013,14 @@ int cddp_hip_seed_best(cddp_hip_handle *h, int flags, int ncand, const double *x
   HIPCHK(hipSetDevice(h->device));
   const bool dev = (flags & CDDP_HIP_SCORE_DEVICE) != 0;
   const size_t B = (size_t)h->B, S = (size_t)ncand, nx = (size_t)h->nx, nU = (size_t)h->N * h->nu;
-  const double *x0d = x0, *Ud = U, *costd = cost, *viold = viol;
-  if (dev) {
-    if (x0) { int rc = io_check_pointer(h, x0, B * nx * sizeof(double), me, "x0"); if (rc) return rc; }
-    { int rc = io_check_pointer(h, U, B * S * nU * sizeof(double), me, "U"); if (rc) return rc; }
-    { int rc = io_check_pointer(h, cost, B * S * sizeof(double), me, "cost"); if (rc) return rc; }
-    if (viol) { int rc = io_check_pointer(h, viol, B * S * sizeof(double), me, "viol"); if (rc) return rc; }
-    if (winner) { int rc = io_check_pointer(h, winner, B * sizeof(int32_t), me, "winner"); if (rc) return rc; }
-  } else {
-    { int rc = score_scratch(h, B * ((x0 ? nx : 0) + S * nU + S + (viol ? S : 0))); if (rc) return rc; }
-    double *top = h->d_score;
-    if (x0) { HIPCHK(hipMemcpy(top, x0, B * nx * sizeof(double), hipMemcpyHostToDevice)); x0d = top; top += B * nx; }
-    HIPCHK(hipMemcpy(top, U, B * S * nU * sizeof(double), hipMemcpyHostToDevice)); Ud = top; top += B * S * nU;
-    HIPCHK(hipMemcpy(top, cost, B * S * sizeof(double), hipMemcpyHostToDevice)); costd = top; top += B * S;
-    if (viol) { HIPCHK(hipMemcpy(top, viol, B * S * sizeof(double), hipMemcpyHostToDevice)); viold = top; top += B * S; }
-  }
+  Staging st(h, me, dev);
+  const double *x0d, *Ud, *costd, *viold;
+  st.in("x0", x0, B * nx * sizeof(double), &x0d);
+  st.in("U", U, B * S * nU * sizeof(double), &Ud);
+  st.in("cost", cost, B * S * sizeof(double), &costd);
+  st.in("viol", viol, B * S * sizeof(double), &viold);
+  st.out_via("winner", winner, B * sizeof(int32_t), &h->d_winner);   // the selection always writes the handle's own winner[B], both forms
+  { int rc = st.begin(); if (rc) return rc; }
   if (!h->d_winner) HIPCHK(hipMalloc((void **)&h->d_winner, B * sizeof(int32_t)));
   { int rc = fork_from_user(h); if (rc) return rc; }
   for (size_t gi = 0; gi < h->g.size(); ++gi) {
@@ -3035,13 +3032,9 @@ int cddp_hip_seed_best(cddp_hip_handle *h, int flags, int ncand, const double *x
     if (x0d) io_tile(nullptr, x0d + b0 * nx, q->d.B, q->d.NB, h->N + 1, h->nx, q->d_Xinit, q->stream);
     io_tile(Ud + b0 * S * nU, nullptr, q->d.B, q->d.NB, h->N, h->nu, q->d_Uinit, q->stream, w, ncand);
     if (winner && dev) HIPCHK(hipMemcpyAsync(winner + b0, w, (size_t)q->d.B * sizeof(int32_t), hipMemcpyDeviceToDevice, q->stream));
-    q->have_initial = true; q->initialized = false; q->initial_dirty = true;   // as cddp_hip_set_initial_device leaves them
+    mark_seeded(q);
   }
-  if (dev) return io_finish(h);
-  HIPCHK(hipGetLastError());
-  for (Inner *q : h->g) HIPCHK(hipStreamSynchronize(q->stream));
-  if (winner) HIPCHK(hipMemcpy(winner, h->d_winner, B * sizeof(int32_t), hipMemcpyDeviceToHost));
-  return join_to_user(h);
+  return st.finish();
 }
 
 // ---- sampling-based plan refinement (inst_mppi.hip): candidates drawn in the kernels, weights and blend of csrc/mppi.hpp ----
@@ -3091,17 +3084,13 @@ int cddp_hip_sample_controls(cddp_hip_handle *h, int flags, const cddp_hip_mppi_
   const size_t B = (size_t)h->B, S = (size_t)desc->ncand, nU = (size_t)h->N * h->nu;
   if ((B * S * ((nU + 1) / 2) + 255) / 256 > 0x7fffffffull) return fail(-2, "%s: batch * ncand * N * nu / 2 = %zu lanes exceed what one launch holds", me, B * S * ((nU + 1) / 2));
   HIPCHK(hipSetDevice(h->device));
-  const double *meand = U_mean;
-  double *outd = U_out;
-  if (dev) {
-    if (U_mean) { int rc = io_check_pointer(h, U_mean, B * nU * sizeof(double), me, "U_mean"); if (rc) return rc; }
-    { int rc = io_check_pointer(h, U_out, B * S * nU * sizeof(double), me, "U_out"); if (rc) return rc; }
-    if (!U_mean) { int rc = score_scratch(h, B * nU); if (rc) return rc; meand = h->d_score; }
-  } else {
-    { int rc = score_scratch(h, B * nU + B * S * nU); if (rc) return rc; }
-    if (U_mean) HIPCHK(hipMemcpy(h->d_score, U_mean, B * nU * sizeof(double), hipMemcpyHostToDevice));
-    meand = h->d_score; outd = h->d_score + B * nU;
-  }
+  Staging st(h, me, dev);
+  const double *meand;
+  double *outd;
+  if (U_mean) st.in("U_mean", U_mean, B * nU * sizeof(double), &meand);
+  else st.scratch(B * nU * sizeof(double), &meand);   // the plan's U, un-tiled per group below
+  st.out("U_out", U_out, B * S * nU * sizeof(double), &outd);
+  { int rc = st.begin(); if (rc) return rc; }
   { int rc = fork_from_user(h); if (rc) return rc; }
   for (size_t gi = 0; gi < h->g.size(); ++gi) {
     const Inner *q = h->g[gi];
@@ -3110,11 +3099,7 @@ int cddp_hip_sample_controls(cddp_hip_handle *h, int flags, const cddp_hip_mppi_
     a.b0 = (int)b0;
     HIPCHK(mppi_sample_launch(a, q->d.B, h->N, h->nu, meand + b0 * nU, outd + b0 * S * nU, q->stream));
   }
-  if (dev) return io_finish(h);
-  HIPCHK(hipGetLastError());
-  for (Inner *q : h->g) HIPCHK(hipStreamSynchronize(q->stream));
-  HIPCHK(hipMemcpy(U_out, outd, B * S * nU * sizeof(double), hipMemcpyDeviceToHost));
-  return join_to_user(h);
+  return st.finish();
 }
 
 int cddp_hip_mppi_blend(cddp_hip_handle *h, int flags, const cddp_hip_mppi_desc *desc, const double *U_mean, const double *U_cand, const double *cost,
@@ -3129,29 +3114,18 @@ int cddp_hip_mppi_blend(cddp_hip_handle *h, int flags, const cddp_hip_mppi_desc 
   const bool dev = (flags & CDDP_HIP_SCORE_DEVICE) != 0;
   const size_t B = (size_t)h->B, S = (size_t)desc->ncand, nU = (size_t)h->N * h->nu;
   HIPCHK(hipSetDevice(h->device));
-  const double *meand = U_mean, *candd = U_cand, *costd = cost, *viold = viol;
-  double *outd = U_out, *wd, *std_;
-  if (dev) {
-    { int rc = io_check_pointer(h, U_mean, B * nU * sizeof(double), me, "U_mean"); if (rc) return rc; }
-    { int rc = io_check_pointer(h, U_cand, B * S * nU * sizeof(double), me, "U_cand"); if (rc) return rc; }
-    { int rc = io_check_pointer(h, cost, B * S * sizeof(double), me, "cost"); if (rc) return rc; }
-    if (viol) { int rc = io_check_pointer(h, viol, B * S * sizeof(double), me, "viol"); if (rc) return rc; }
-    { int rc = io_check_pointer(h, U_out, B * nU * sizeof(double), me, "U_out"); if (rc) return rc; }
-    if (stats) { int rc = io_check_pointer(h, stats, B * 3 * sizeof(double), me, "stats"); if (rc) return rc; }
-    { int rc = score_scratch(h, B * S + B * 3); if (rc) return rc; }
-    wd = h->d_score; std_ = wd + B * S;
-  } else {
-    { int rc = score_scratch(h, B * S + B * 3 + 2 * B * nU + B * S * nU + 2 * B * S); if (rc) return rc; }
-    double *top = h->d_score;
-    wd = top; top += B * S;
-    std_ = top; top += B * 3;
-    HIPCHK(hipMemcpy(top, U_mean, B * nU * sizeof(double), hipMemcpyHostToDevice)); meand = top; top += B * nU;
-    HIPCHK(hipMemcpy(top, U_cand, B * S * nU * sizeof(double), hipMemcpyHostToDevice)); candd = top; top += B * S * nU;
-    HIPCHK(hipMemcpy(top, cost, B * S * sizeof(double), hipMemcpyHostToDevice)); costd = top; top += B * S;
-    if (viol) { HIPCHK(hipMemcpy(top, viol, B * S * sizeof(double), hipMemcpyHostToDevice)); viold = top; }
-    top += B * S;
-    outd = top;
-  }
+  Staging st(h, me, dev);
+  const double *meand, *candd, *costd, *viold;
+  double *outd, *wd, *std_;
+  st.scratch(B * S * sizeof(double), &wd);      // the weights [B][S]
+  st.scratch(B * 3 * sizeof(double), &std_);    // the statistics [B][3], wherever the caller wants them
+  st.in("U_mean", U_mean, B * nU * sizeof(double), &meand);
+  st.in("U_cand", U_cand, B * S * nU * sizeof(double), &candd);
+  st.in("cost", cost, B * S * sizeof(double), &costd);
+  st.in("viol", viol, B * S * sizeof(double), &viold);
+  st.out("U_out", U_out, B * nU * sizeof(double), &outd);
+  st.out_via("stats", stats, B * 3 * sizeof(double), &std_);
+  { int rc = st.begin(); if (rc) return rc; }
   { int rc = fork_from_user(h); if (rc) return rc; }
   for (size_t gi = 0; gi < h->g.size(); ++gi) {
     const Inner *q = h->g[gi];
@@ -3161,12 +3135,7 @@ int cddp_hip_mppi_blend(cddp_hip_handle *h, int flags, const cddp_hip_mppi_desc 
     HIPCHK(mppi_blend_launch(a, q->d.B, h->N, h->nu, meand + b0 * nU, candd + b0 * S * nU, wd + b0 * S, std_ + b0 * 3, outd + b0 * nU, q->stream));
     if (dev && stats) HIPCHK(hipMemcpyAsync(stats + b0 * 3, std_ + b0 * 3, (size_t)q->d.B * 3 * sizeof(double), hipMemcpyDeviceToDevice, q->stream));
   }
-  if (dev) return io_finish(h);
-  HIPCHK(hipGetLastError());
-  for (Inner *q : h->g) HIPCHK(hipStreamSynchronize(q->stream));
-  HIPCHK(hipMemcpy(U_out, outd, B * nU * sizeof(double), hipMemcpyDeviceToHost));
-  if (stats) HIPCHK(hipMemcpy(stats, std_, B * 3 * sizeof(double), hipMemcpyDeviceToHost));
-  return join_to_user(h);
+  return st.finish();
 }
 
 int cddp_hip_mppi_refine(cddp_hip_handle *h, cddp_hip_plant *plant, int flags, const cddp_hip_mppi_desc *desc, const double *x0, const double *U_mean,
@@ -3183,35 +3152,27 @@ int cddp_hip_mppi_refine(cddp_hip_handle *h, cddp_hip_plant *plant, int flags, c
   const size_t B = (size_t)h->B, S = (size_t)desc->ncand, nx = (size_t)h->nx, nU = (size_t)h->N * h->nu;
   if (((size_t)((h->B + 63) / 64 * 64) * S + 63) / 64 > 0x7fffffffull) return fail(-2, "%s: batch * ncand = %zu exceeds what one launch holds", me, B * S);
   HIPCHK(hipSetDevice(h->device));
-  if (dev) {
-    if (x0) { int rc = io_check_pointer(h, x0, B * nx * sizeof(double), me, "x0"); if (rc) return rc; }
-    if (U_mean) { int rc = io_check_pointer(h, U_mean, B * nU * sizeof(double), me, "U_mean"); if (rc) return rc; }
-    { int rc = io_check_pointer(h, U_out, B * nU * sizeof(double), me, "U_out"); if (rc) return rc; }
-    if (cost_out) { int rc = io_check_pointer(h, cost_out, B * S * sizeof(double), me, "cost_out"); if (rc) return rc; }
-    if (viol_out) { int rc = io_check_pointer(h, viol_out, B * S * sizeof(double), me, "viol_out"); if (rc) return rc; }
-    if (stats) { int rc = io_check_pointer(h, stats, B * 3 * sizeof(double), me, "stats"); if (rc) return rc; }
-  }
-  // scratch: the mean ping-ponged between two [B][N][nu] buffers, cost | viol | w [B][S], stats [B][3], the staged x0 of the host form
-  { int rc = score_scratch(h, 2 * B * nU + 3 * B * S + 3 * B + (dev ? 0 : B * nx)); if (rc) return rc; }
-  double *mean[2] = {h->d_score, h->d_score + B * nU};
-  double *costd = mean[1] + B * nU, *viold = costd + B * S, *wd = viold + B * S, *std_ = wd + B * S;
-  const double *x0d = x0;
-  if (!dev) {
-    if (x0) { double *xs = std_ + 3 * B; HIPCHK(hipMemcpy(xs, x0, B * nx * sizeof(double), hipMemcpyHostToDevice)); x0d = xs; }
-    if (U_mean) HIPCHK(hipMemcpy(mean[0], U_mean, B * nU * sizeof(double), hipMemcpyHostToDevice));
-  }
+  // internal blocks: the mean ping-ponged between two [B][N][nu] buffers, cost | viol | w [B][S], stats [B][3]; the results lie in them in
+  // both forms (the device form copies them out per group below)
+  Staging st(h, me, dev);
+  double *mean[2], *costd, *viold, *wd, *std_;
+  const double *x0d;
+  for (int k = 0; k < 2; ++k) st.scratch(B * nU * sizeof(double), &mean[k]);
+  for (double **p : {&costd, &viold, &wd}) st.scratch(B * S * sizeof(double), p);
+  st.scratch(B * 3 * sizeof(double), &std_);
+  st.in("x0", x0, B * nx * sizeof(double), &x0d);
+  st.in_via("U_mean", U_mean, B * nU * sizeof(double), &mean[0]);
+  st.out_via("U_out", U_out, B * nU * sizeof(double), &mean[desc->iters & 1]);   // where the mean lies after the last round
+  st.out_via("cost_out", cost_out, B * S * sizeof(double), &costd);
+  st.out_via("viol_out", viol_out, B * S * sizeof(double), &viold);
+  st.out_via("stats", stats, B * 3 * sizeof(double), &std_);
+  { int rc = st.begin(); if (rc) return rc; }
   { int rc = fork_from_user(h); if (rc) return rc; }
-  const double *last = mean[desc->iters & 1];   // where the mean lies after the last round
+  const double *last = mean[desc->iters & 1];
   for (size_t gi = 0; gi < h->g.size(); ++gi) {
     Inner *q = h->g[gi];
     const size_t b0 = (size_t)h->b0[gi], Bg = (size_t)q->d.B;
-    PlantDev pd;
-    if (plant) pd = plant->pd;
-    else {   // the handle's own model as a plant, as cddp_hip_score_rollouts dresses it
-      std::memset(&pd, 0, sizeof(pd));
-      pd.model = q->P.model; pd.integrator = q->P.integrator; pd.substeps = 1; pd.nx = q->P.nx; pd.nu = q->P.nu; pd.Bp = q->d.Bp; pd.h = q->P.dt;
-      pd.params = (const double *)((const char *)q->dP + offsetof(ProblemDev, mp));
-    }
+    const PlantDev pd = plant ? plant->pd : own_model_plant(q);
     if (!U_mean) mppi_plan_U(h, q, mean[0] + b0 * nU);
     else if (dev) HIPCHK(hipMemcpyAsync(mean[0] + b0 * nU, U_mean + b0 * nU, Bg * nU * sizeof(double), hipMemcpyDeviceToDevice, q->stream));
     a.b0 = (int)b0;
@@ -3219,16 +3180,14 @@ int cddp_hip_mppi_refine(cddp_hip_handle *h, cddp_hip_plant *plant, int flags, c
       const double *in = mean[k & 1] + b0 * nU;
       double *out = mean[(k + 1) & 1] + b0 * nU;
       a.stream = desc->stream + (uint32_t)k;
-      const hipError_t e = mppi_score_launch(pd, q->d, a, x0d ? x0d + b0 * nx : nullptr, in, costd + b0 * S, viold + b0 * S, q->stream);
-      if (e == hipErrorInvalidValue) return fail(-3, "%s: the library has no scoring kernel for model id %d with nx = %d, nu = %d", me, pd.model, pd.nx, pd.nu);
-      HIPCHK(e);
+      { int rc = plant_launch_rc(mppi_score_launch(pd, q->d, a, x0d ? x0d + b0 * nx : nullptr, in, costd + b0 * S, viold + b0 * S, q->stream), me, "scoring", pd); if (rc) return rc; }
       mppi_weights_launch(q->d.B, desc->ncand, costd + b0 * S, viold + b0 * S, desc->viol_tol, desc->lambda, wd + b0 * S, std_ + b0 * 3, q->stream);
       HIPCHK(mppi_blend_launch(a, q->d.B, h->N, h->nu, in, nullptr, wd + b0 * S, std_ + b0 * 3, out, q->stream));
     }
     if (seed) {   // exactly as cddp_hip_set_initial_device(x0, U_out, NULL) tiles it
       if (x0d) io_tile(nullptr, x0d + b0 * nx, q->d.B, q->d.NB, h->N + 1, h->nx, q->d_Xinit, q->stream);
       io_tile(last + b0 * nU, nullptr, q->d.B, q->d.NB, h->N, h->nu, q->d_Uinit, q->stream);
-      q->have_initial = true; q->initialized = false; q->initial_dirty = true;
+      mark_seeded(q);
     }
     if (dev) {
       HIPCHK(hipMemcpyAsync(U_out + b0 * nU, last + b0 * nU, Bg * nU * sizeof(double), hipMemcpyDeviceToDevice, q->stream));
@@ -3237,14 +3196,7 @@ int cddp_hip_mppi_refine(cddp_hip_handle *h, cddp_hip_plant *plant, int flags, c
       if (stats) HIPCHK(hipMemcpyAsync(stats + b0 * 3, std_ + b0 * 3, Bg * 3 * sizeof(double), hipMemcpyDeviceToDevice, q->stream));
     }
   }
-  if (dev) return io_finish(h);
-  HIPCHK(hipGetLastError());
-  for (Inner *q : h->g) HIPCHK(hipStreamSynchronize(q->stream));
-  HIPCHK(hipMemcpy(U_out, last, B * nU * sizeof(double), hipMemcpyDeviceToHost));
-  if (cost_out) HIPCHK(hipMemcpy(cost_out, costd, B * S * sizeof(double), hipMemcpyDeviceToHost));
-  if (viol_out) HIPCHK(hipMemcpy(viol_out, viold, B * S * sizeof(double), hipMemcpyDeviceToHost));
-  if (stats) HIPCHK(hipMemcpy(stats, std_, B * 3 * sizeof(double), hipMemcpyDeviceToHost));
-  return join_to_user(h);
+  return st.finish();
 }
 
 // ---- Monte-Carlo evaluation of a solved plan under noise (inst_mc.hip): noise drawn in the kernel, sums over the samples of csrc/plan_mc.hpp ----
@@ -3285,18 +3237,12 @@ int cddp_hip_mc_sample_noise(cddp_hip_handle *h, int flags, const cddp_hip_mc_de
   const size_t B = (size_t)h->B, S = (size_t)desc->nsamp, nx = (size_t)h->nx, nu = (size_t)h->nu, N = (size_t)h->N;
   const size_t n0 = S * nx, nE = S * N * nu, nW = S * N * nx;   // per trajectory
   HIPCHK(hipSetDevice(h->device));
-  double *Zd = Z0, *Ed = E, *Wd = Wn;
-  if (dev) {
-    if (Z0) { int rc = io_check_pointer(h, Z0, B * n0 * sizeof(double), me, "Z0"); if (rc) return rc; }
-    if (E) { int rc = io_check_pointer(h, E, B * nE * sizeof(double), me, "E"); if (rc) return rc; }
-    if (Wn) { int rc = io_check_pointer(h, Wn, B * nW * sizeof(double), me, "Wn"); if (rc) return rc; }
-  } else {
-    { int rc = score_scratch(h, B * ((Z0 ? n0 : 0) + (E ? nE : 0) + (Wn ? nW : 0))); if (rc) return rc; }
-    double *top = h->d_score;
-    if (Z0) { Zd = top; top += B * n0; }
-    if (E) { Ed = top; top += B * nE; }
-    if (Wn) { Wd = top; top += B * nW; }
-  }
+  Staging st(h, me, dev);
+  double *Zd, *Ed, *Wd;
+  st.out("Z0", Z0, B * n0 * sizeof(double), &Zd);
+  st.out("E", E, B * nE * sizeof(double), &Ed);
+  st.out("Wn", Wn, B * nW * sizeof(double), &Wd);
+  { int rc = st.begin(); if (rc) return rc; }
   { int rc = fork_from_user(h); if (rc) return rc; }
   for (size_t gi = 0; gi < h->g.size(); ++gi) {
     const Inner *q = h->g[gi];
@@ -3304,13 +3250,7 @@ int cddp_hip_mc_sample_noise(cddp_hip_handle *h, int flags, const cddp_hip_mc_de
     a.b0 = (int)b0;
     HIPCHK(mc_noise_launch(a, f, q->d.B, h->N, h->nx, h->nu, Zd ? Zd + b0 * n0 : nullptr, Ed ? Ed + b0 * nE : nullptr, Wd ? Wd + b0 * nW : nullptr, q->stream));
   }
-  if (dev) return io_finish(h);
-  HIPCHK(hipGetLastError());
-  for (Inner *q : h->g) HIPCHK(hipStreamSynchronize(q->stream));
-  if (Z0) HIPCHK(hipMemcpy(Z0, Zd, B * n0 * sizeof(double), hipMemcpyDeviceToHost));
-  if (E) HIPCHK(hipMemcpy(E, Ed, B * nE * sizeof(double), hipMemcpyDeviceToHost));
-  if (Wn) HIPCHK(hipMemcpy(Wn, Wd, B * nW * sizeof(double), hipMemcpyDeviceToHost));
-  return join_to_user(h);
+  return st.finish();
 }
 
 int cddp_hip_plan_montecarlo(cddp_hip_handle *h, cddp_hip_plant *plant, int flags, const cddp_hip_mc_desc *desc, const double *x0, double *cost, double *viol,
@@ -3333,51 +3273,28 @@ int cddp_hip_plan_montecarlo(cddp_hip_handle *h, cddp_hip_plant *plant, int flag
   const size_t per[9] = {S, S, 8, (N + 1) * nx, nSX, N * nu, nSU, nXo, nUo};
   static const char *const names[9] = {"cost", "viol", "stats", "dXmean", "SX", "dUmean", "SU", "X_out", "U_out"};
   HIPCHK(hipSetDevice(h->device));
-  const double *x0d = x0;
+  Staging st(h, me, dev);
+  const double *x0d;
   double *od[9];
-  int32_t *cntd = nviol_step;
-  for (int i = 0; i < 9; ++i) od[i] = outs[i];
-  if (dev) {
-    if (x0) { int rc = io_check_pointer(h, x0, B * nx * sizeof(double), me, "x0"); if (rc) return rc; }
-    for (int i = 0; i < 9; ++i) if (outs[i]) { int rc = io_check_pointer(h, outs[i], B * per[i] * sizeof(double), me, names[i]); if (rc) return rc; }
-    if (nviol_step) { int rc = io_check_pointer(h, nviol_step, B * nCnt * sizeof(int32_t), me, "nviol_step"); if (rc) return rc; }
-  } else {
-    size_t total = x0 ? B * nx : 0;
-    for (int i = 0; i < 9; ++i) if (outs[i]) total += B * per[i];
-    if (nviol_step) total += (B * nCnt + 1) / 2;
-    { int rc = score_scratch(h, total); if (rc) return rc; }
-    double *top = h->d_score;
-    if (x0) { HIPCHK(hipMemcpy(top, x0, B * nx * sizeof(double), hipMemcpyHostToDevice)); x0d = top; top += B * nx; }
-    for (int i = 0; i < 9; ++i) if (outs[i]) { od[i] = top; top += B * per[i]; }
-    if (nviol_step) cntd = (int32_t *)top;
-  }
+  int32_t *cntd;
+  st.in("x0", x0, B * nx * sizeof(double), &x0d);
+  for (int i = 0; i < 9; ++i) st.out(names[i], outs[i], B * per[i] * sizeof(double), &od[i]);
+  st.out("nviol_step", nviol_step, B * nCnt * sizeof(int32_t), &cntd);
+  { int rc = st.begin(); if (rc) return rc; }
   { int rc = fork_from_user(h); if (rc) return rc; }
   for (size_t gi = 0; gi < h->g.size(); ++gi) {
     const Inner *q = h->g[gi];
     const size_t b0 = (size_t)h->b0[gi];
-    PlantDev pd;
-    if (plant) pd = plant->pd;
-    else {   // the handle's own model as a plant, as cddp_hip_score_rollouts dresses it
-      std::memset(&pd, 0, sizeof(pd));
-      pd.model = q->P.model; pd.integrator = q->P.integrator; pd.substeps = 1; pd.nx = q->P.nx; pd.nu = q->P.nu; pd.Bp = q->d.Bp; pd.h = q->P.dt;
-      pd.params = (const double *)((const char *)q->dP + offsetof(ProblemDev, mp));
-    }
+    const PlantDev pd = plant ? plant->pd : own_model_plant(q);
     a.b0 = (int)b0;
     a.x0 = x0d ? x0d + b0 * nx : nullptr;
     double *go[9];
     for (int i = 0; i < 9; ++i) go[i] = od[i] ? od[i] + b0 * per[i] : nullptr;
     a.cost = go[0]; a.viol = go[1]; a.stats = go[2]; a.dXmean = go[3]; a.SX = go[4]; a.dUmean = go[5]; a.SU = go[6]; a.X_out = go[7]; a.U_out = go[8];
     a.nviol_step = cntd ? cntd + b0 * nCnt : nullptr;
-    const hipError_t e = mc_launch(pd, q->d, a, f, q->stream);
-    if (e == hipErrorInvalidValue) return fail(-3, "%s: the library has no sampling kernel for model id %d with nx = %d, nu = %d", me, pd.model, pd.nx, pd.nu);
-    HIPCHK(e);
+    { int rc = plant_launch_rc(mc_launch(pd, q->d, a, f, q->stream), me, "sampling", pd); if (rc) return rc; }
   }
-  if (dev) return io_finish(h);
-  HIPCHK(hipGetLastError());
-  for (Inner *q : h->g) HIPCHK(hipStreamSynchronize(q->stream));
-  for (int i = 0; i < 9; ++i) if (outs[i]) HIPCHK(hipMemcpy(outs[i], od[i], B * per[i] * sizeof(double), hipMemcpyDeviceToHost));
-  if (nviol_step) HIPCHK(hipMemcpy(nviol_step, cntd, B * nCnt * sizeof(int32_t), hipMemcpyDeviceToHost));
-  return join_to_user(h);
+  return st.finish();
 }
 
 }  // extern "C"
