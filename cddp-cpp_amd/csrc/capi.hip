@@ -286,6 +286,17 @@ int fail_no_hessians(int model) {
   return fail(-3, "use_ilqr=false needs the plant's Hessian tensors, which model id %d does not have", model);
 }
 
+// The ladder a solver walks.  CLDDP, IPDDP and MSIPDDP walk the context's alphas_ = detail::buildLineSearchAlphas (cddp_core.cpp:60, 111);
+// LogDDP rebuilds the ladder in its initialize as the plain geometric sequence, without the stop at ls_min_step_size
+// (logddp_solver.cpp:104-109, 177-182).  alphas == NULL: the ladder's own length.
+int build_ladder(int solver, const cddp_hip_options *opt, double *alphas, int cap) {
+  if (solver != CDDP_HIP_SOLVER_LOGDDP) return cddp_hip_build_alphas(opt, alphas, cap);
+  int n = 0;
+  double cur = opt->ls_initial_step_size;
+  for (int i = 0; i < opt->ls_max_iterations; ++i) { if (alphas && n < cap) alphas[n] = cur; ++n; cur *= opt->ls_step_reduction_factor; }
+  return (alphas && n > cap) ? cap : n;
+}
+
 // cddp_hip_problem -> ProblemDev (constraints sorted by name as std::map iterates)
 int flatten(const cddp_hip_problem *p, ProblemDev &P) {
   std::memset(&P, 0, sizeof(P));
@@ -413,7 +424,7 @@ int flatten(const cddp_hip_problem *p, ProblemDev &P) {
     P.mT = offI; P.pT = offE;
     if (P.mT > 8 || P.pT > 16) return fail(-3, "terminal constraint dimension too large (ineq %d > 8 or eq %d > 16)", P.mT, P.pT);
   }
-  P.n_alphas = cddp_hip_build_alphas(&p->options, P.alphas, CDDP_HIP_MAX_ALPHAS);
+  P.n_alphas = build_ladder(p->solver, &p->options, P.alphas, CDDP_HIP_MAX_ALPHAS);
   if (P.n_alphas <= 0) return fail(-2, "empty line-search ladder");
   return 0;
 }
@@ -494,17 +505,34 @@ int cddp_hip_build_alphas(const cddp_hip_options *opt, double *alphas, int cap) 
   int n = 0;
   double cur = opt->ls_initial_step_size;
   for (int i = 0; i < opt->ls_max_iterations; ++i) {
-    if (n < cap) alphas[n] = cur;
+    if (alphas && n < cap) alphas[n] = cur;
     ++n;
     cur *= opt->ls_step_reduction_factor;
     if (cur < opt->ls_min_step_size && i < opt->ls_max_iterations - 1) {
-      if (n < cap) alphas[n] = opt->ls_min_step_size;
+      if (alphas && n < cap) alphas[n] = opt->ls_min_step_size;
       ++n;
       break;
     }
   }
-  if (n == 0) { if (cap > 0) alphas[0] = opt->ls_initial_step_size; n = 1; }
+  if (n == 0) { if (alphas && cap > 0) alphas[0] = opt->ls_initial_step_size; n = 1; }
+  if (!alphas) return n;   // the ladder's own length, whatever a buffer could hold
   return n > cap ? cap : n;
+}
+
+// What the fixed capacities of a handle cannot hold is refused, not truncated (cddp_hip_create and cddp_hip_set_options):
+//  * the ladder lives in ProblemDev::alphas[CDDP_HIP_MAX_ALPHAS]; the reference runs every step size buildLineSearchAlphas makes;
+//  * the IPDDP filter column holds kFilterCap points, and between an accept and the prune that follows it the reference's filter holds
+//    max_filter_size + 1 (ipddp_solver.cpp: acceptFilterEntry, then pruneFilterToBestPoints above max_filter_size).  MSIPDDP sizes its
+//    filter by max_iterations and never reads the option.
+static int check_capacities(int solver, const cddp_hip_options *opt) {
+  const int n_full = build_ladder(solver, opt, nullptr, 0);
+  if (n_full > CDDP_HIP_MAX_ALPHAS)
+    return fail(-3, "line_search: ls_max_iterations = %d gives a ladder of %d step sizes, more than CDDP_HIP_MAX_ALPHAS = %d", opt->ls_max_iterations,
+                n_full, CDDP_HIP_MAX_ALPHAS);
+  if (solver == CDDP_HIP_SOLVER_IPDDP && opt->ipddp_max_filter_size > kFilterCap - 1)
+    return fail(-3, "ipddp_max_filter_size = %d: the filter holds max_filter_size + 1 points before it is pruned and has %d slots, so at most %d",
+                opt->ipddp_max_filter_size, kFilterCap, kFilterCap - 1);
+  return 0;
 }
 
 
@@ -979,10 +1007,11 @@ static int in_set_options(Inner *h, const cddp_hip_options *opt) {
   if (!(opt->reg_update_factor > 1.0) || !(opt->reg_max_value > 0.0))
     return fail(-2, "regularization.update_factor must be > 1 and max_value > 0 (got %g, %g)", opt->reg_update_factor, opt->reg_max_value);
   if (!opt->use_ilqr && !model_has_hessians(h->P.model)) return fail_no_hessians(h->P.model);
+  { int rc = check_capacities(h->P.solver, opt); if (rc) return rc; }
   HIPCHK(hipSetDevice(h->device));
   { int rc = goal_to_host(h); if (rc) return rc; }   // P goes up whole below: with the goal the device holds
   double al[CDDP_HIP_MAX_ALPHAS];
-  const int na = cddp_hip_build_alphas(opt, al, CDDP_HIP_MAX_ALPHAS);
+  const int na = build_ladder(h->P.solver, opt, al, CDDP_HIP_MAX_ALPHAS);
   if (na != h->P.n_alphas) return fail(-3, "the line-search ladder size is fixed at create time (%d alphas, new options give %d)", h->P.n_alphas, na);
   if (h->d.ms && opt->max_iterations + 2 > h->d.filt_cap)
     return fail(-3, "max_iterations cannot grow beyond %d on an MSIPDDP handle (filter capacity fixed by cddp_hip_create)", h->d.filt_cap - 2);
@@ -1981,9 +2010,10 @@ extern "C" {
 int cddp_hip_create(const cddp_hip_problem *problem, int batch, int device, cddp_hip_handle **out) {
   if (!problem || !out) return fail(-1, "null argument");
   if (batch <= 0) return fail(-1, "batch must be positive");
+  { int rc = check_capacities(problem->solver, &problem->options); if (rc) return rc; }
   int conc = 1, part = 1;
   double ladder[CDDP_HIP_MAX_ALPHAS];
-  const int n_ladder = cddp_hip_build_alphas(&problem->options, ladder, CDDP_HIP_MAX_ALPHAS);   // the real ladder length (it can stop early at ls_min_step_size)
+  const int n_ladder = build_ladder(problem->solver, &problem->options, ladder, CDDP_HIP_MAX_ALPHAS);   // the real ladder length (it can stop early at ls_min_step_size)
   cddp_hip_handle *h = new cddp_hip_handle();
   const Knobs &knob = h->knob;
   if (knob.fail_costate) std::fprintf(stderr, "[cddp_hip] TEST HOOK active: CDDP_HIP_TEST_FAIL_COSTATE=%d discards line-search trials -- results are not the solver's\n", knob.fail_costate);

@@ -9,7 +9,7 @@ namespace cddp_dev {
 constexpr int kMaxCons = 4;     // path-constraint objects per problem
 constexpr int kMaxTerms = 2;    // terminal-constraint objects per problem
 constexpr int kPool = 1024;     // doubles of problem constants (Q, R, Qf, x_ref, bounds, ...)
-constexpr int kFilterCap = 8;   // > ipddp.max_filter_size + 1
+constexpr int kFilterCap = 8;   // >= ipddp.max_filter_size + 1: capi.hip::check_capacities refuses a larger max_filter_size
 constexpr int kHistCols = 9;
 
 // per-trajectory phases of the device state machine (cddp_solver_base.cpp:74-152)

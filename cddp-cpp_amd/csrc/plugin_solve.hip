@@ -933,8 +933,9 @@ int msipddp_solve(const Ctx &c, int device, int batch, const double *x0, const d
   { int rc = sw.open(device, m); if (rc) return rc; }
   if (m == 0) { int rc = cddp_hip_stacks_factor_cache(sw.h, 1); if (rc) return rc; }
   const int seg = o.msipddp_segment_length, rtype = o.msipddp_rollout_type;
-  std::vector<double> alphas;
-  { double a = o.ls_initial_step_size; for (int i = 0; i < o.ls_max_iterations; ++i) { alphas.push_back(a); a *= o.ls_step_reduction_factor; } }
+  // MSIPDDP never rebuilds the ladder: the base class walks the context's alphas_ = detail::buildLineSearchAlphas (cddp_core.cpp:60,
+  // cddp_solver_base.cpp:257), which stops at ls_min_step_size -- unlike LogDDP's own plain sequence (logddp_solver.cpp:177-182)
+  const std::vector<double> &alphas = c.alphas;
 
   std::vector<MTraj> T(B);
   std::vector<double> xn(nx);
@@ -1838,7 +1839,8 @@ static int plugin_solve_impl(const cddp_hip_plugin *pl, const cddp_hip_plugin_te
 
   Ctx c; c.pl = pl; c.o = opt; c.solver = solver; c.nx = nx; c.nu = nu; c.m = m; c.N = N; c.dt = dt;
   c.threads = (solver == CDDP_HIP_SOLVER_LOGDDP || solver == CDDP_HIP_SOLVER_MSIPDDP) ? 1 : host_threads(batch);
-  { double al[CDDP_HIP_MAX_ALPHAS]; const int na = cddp_hip_build_alphas(opt, al, CDDP_HIP_MAX_ALPHAS); c.alphas.assign(al, al + na); }
+  // (the host loop walks the ladder as a vector: every step size buildLineSearchAlphas makes, not the resident handles' CDDP_HIP_MAX_ALPHAS)
+  { c.alphas.resize(cddp_hip_build_alphas(opt, nullptr, 0)); cddp_hip_build_alphas(opt, c.alphas.data(), (int)c.alphas.size()); }
   g_last_stats = PluginStats(); g_last_stats.threads = c.threads;
   // Terminal constraints: only IPDDP reads the terminal set (clddp / logddp / msipddp_solver.cpp never touch getTerminalConstraintSet)
   if (tc && tc->n_terminal > 0 && solver == CDDP_HIP_SOLVER_IPDDP) {

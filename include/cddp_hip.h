@@ -169,7 +169,8 @@ typedef struct cddp_hip_options {
   int32_t _pad0;
   double termination_scaling_max_factor; /* 100 */
   /* LineSearchOptions */
-  int32_t ls_max_iterations;     /* 11 */
+  int32_t ls_max_iterations;     /* 11; a ladder of more than CDDP_HIP_MAX_ALPHAS step sizes is refused by cddp_hip_create and
+                                  * cddp_hip_set_options (the reference walks all of it; cddp_hip_plugin_solve does too) */
   int32_t _pad1;
   double ls_initial_step_size;   /* 1.0 */
   double ls_min_step_size;       /* 1e-8 */
@@ -201,7 +202,8 @@ typedef struct cddp_hip_options {
   double ipddp_mu_kappa_epsilon;      /* 10 */
   int32_t ipddp_check_state_stationarity; /* 0 */
   int32_t ipddp_theta_norm_l2;        /* 0 = "l1" */
-  int32_t ipddp_max_filter_size;      /* 5 */
+  int32_t ipddp_max_filter_size;      /* 5; IPDDP handles take at most 7: the filter holds max_filter_size + 1 points between an accept
+                                       * and the prune, in eight slots.  Larger values are refused, not truncated (MSIPDDP does not read it) */
   int32_t ipddp_warmstart_repair;     /* 0 */
   double ipddp_theta_0_floor;         /* 1.0 */
   double ipddp_warmstart_s_min;       /* 1e-4 */
@@ -376,7 +378,9 @@ int cddp_hip_device_count(void);
 const char *cddp_hip_status_string(int status);
 
 /* Build line-search ladder exactly as detail::buildLineSearchAlphas
- * (cddp_context_utils.cpp:37-57). Returns the number of alphas written (<= cap). */
+ * (cddp_context_utils.cpp:37-57). Returns the number of alphas written (<= cap); with alphas == NULL
+ * the ladder's own length, which may exceed CDDP_HIP_MAX_ALPHAS.  This is the ladder of CLDDP, IPDDP and
+ * MSIPDDP; LogDDP walks ls_max_iterations plain geometric steps (logddp_solver.cpp:177-182). */
 int cddp_hip_build_alphas(const cddp_hip_options *opt, double *alphas, int cap);
 
 /* Create a solver instance for `batch` independent trajectories of `problem` on `device`.

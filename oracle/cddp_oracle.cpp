@@ -2113,15 +2113,17 @@ static Solver *build(const cddp_hip_problem *p) {
     s->terms.push_back(d);
   }
   std::stable_sort(s->terms.begin(), s->terms.end(), [](const TerminalDesc &a, const TerminalDesc &b) { return a.name < b.name; });
-  // buildLineSearchAlphas (cddp_context_utils.cpp:37-57)
+  // buildLineSearchAlphas (cddp_context_utils.cpp:37-57); LogDDP rebuilds the ladder in its initialize as the plain geometric sequence,
+  // without the stop at ls_min_step_size (logddp_solver.cpp:104-109, 177-182)
   {
+    const bool plain = p->solver == CDDP_HIP_SOLVER_LOGDDP;
     double cur = p->options.ls_initial_step_size;
     for (int i = 0; i < p->options.ls_max_iterations; ++i) {
       s->alphas.push_back(cur);
       cur *= p->options.ls_step_reduction_factor;
-      if (cur < p->options.ls_min_step_size && i < p->options.ls_max_iterations - 1) { s->alphas.push_back(p->options.ls_min_step_size); break; }
+      if (!plain && cur < p->options.ls_min_step_size && i < p->options.ls_max_iterations - 1) { s->alphas.push_back(p->options.ls_min_step_size); break; }
     }
-    if (s->alphas.empty()) s->alphas.push_back(p->options.ls_initial_step_size);
+    if (s->alphas.empty() && !plain) s->alphas.push_back(p->options.ls_initial_step_size);
   }
   return s;
 }
@@ -2157,6 +2159,14 @@ void cddp_oracle_set_path_interior(void *o, double s_val, double y_val) {
   Solver *s = (Solver *)o;
   for (auto &v : s->S) for (int i = 0; i < v.size(); ++i) v(i) = s_val;
   for (auto &v : s->Y) for (int i = 0; i < v.size(); ++i) v(i) = y_val;
+}
+// the same per element: S, Y are [N][m] (what cddp_hip_set_duals takes for one trajectory); NULL keeps that side
+void cddp_oracle_set_duals(void *o, const double *S, const double *Y) {
+  Solver *s = (Solver *)o;
+  for (int t = 0; t < (int)s->S.size(); ++t) {
+    if (S) for (int i = 0; i < s->S[t].size(); ++i) s->S[t](i) = S[(size_t)t * s->m + i];
+    if (Y) for (int i = 0; i < s->Y[t].size(); ++i) s->Y[t](i) = Y[(size_t)t * s->m + i];
+  }
 }
 void cddp_oracle_set_terminal_interior(void *o, double s_val, double y_val) {
   Solver *s = (Solver *)o;

@@ -73,6 +73,11 @@ class Oracle:
     def set_path_interior(self, s_val, y_val):
         self.lib.cddp_oracle_set_path_interior(self.h, C.c_double(s_val), C.c_double(y_val))
 
+    def set_duals(self, S=None, Y=None):
+        """Per-element slack / dual rows (N, m) of the live solver object (HipBatchSolver.set_duals for one trajectory)."""
+        S = _api()._arr(S) if S is not None else None; Y = _api()._arr(Y) if Y is not None else None
+        self.lib.cddp_oracle_set_duals(self.h, _api()._ptr(S), _api()._ptr(Y))
+
     def set_terminal_interior(self, s_val, y_val):
         self.lib.cddp_oracle_set_terminal_interior(self.h, C.c_double(s_val), C.c_double(y_val))
 

@@ -1175,8 +1175,8 @@ class Twin:
                     best = r
             elif r["success"]:
                 best = r; break
-        if self.o["enable_parallel"]:
-            self.n_forward_last = (self.alphas.index(best["alpha"]) + 1) if best["success"] else len(self.alphas)
+        # (enable_parallel launches every step size, cddp_solver_base.cpp:264-314: all of them are counted, as the oracle and the
+        # library count them -- n_forward_last is already len(self.alphas) here)
         return best
 
     def apply(self, r):                        # applyForwardPassResult: base :190-198 + ipddp_solver.cpp:1878-1951

@@ -167,8 +167,13 @@ class MSIPDDP:
 
     def initialize(self):                                # :33-264
         o = self.o; N, nx, nu, m = self.N, self.nx, self.nu, self.m
+        # the context's ladder, detail::buildLineSearchAlphas (cddp_context_utils.cpp:37-57): msipddp_solver.cpp never rebuilds it
         a = o["ls_initial_step_size"]; self.alphas = []
-        for _ in range(o["ls_max_iterations"]): self.alphas.append(a); a *= o["ls_step_reduction_factor"]
+        for i in range(o["ls_max_iterations"]):
+            self.alphas.append(a); a *= o["ls_step_reduction_factor"]
+            if a < o["ls_min_step_size"] and i < o["ls_max_iterations"] - 1:
+                self.alphas.append(o["ls_min_step_size"]); break
+        if not self.alphas: self.alphas.append(o["ls_initial_step_size"])
         self.alpha_pr = o["ls_initial_step_size"]; self.alpha_du = 0.0
         self.n_backward = self.n_forward = 0
         self.inf_du = math.inf
