@@ -18,6 +18,7 @@
 #include "io_kernels.hpp"
 #include "sens_kernels.hpp"
 #include "cov_kernels.hpp"
+#include "lqr_kernels.hpp"
 #include "score_kernels.hpp"
 #include "mppi_kernels.hpp"
 #include "mc_kernels.hpp"
@@ -2707,6 +2708,49 @@ int cddp_hip_plan_covariance(cddp_hip_handle *h, int flags, const double *Sigma0
     a.Qdt = pool + q->P.off_Qdt; a.Rdt = pool + q->P.off_Rdt; a.Qf = pool + q->P.off_Qf;
     a.per_traj = per ? 1 : 0; a.diag = diag ? 1 : 0;
     HIPCHK(plan_cov(sens_stacks(q), a, q->stream));
+  }
+  return st.finish();
+}
+
+// ---- time-varying LQR gains along the plan (inst_lqr.hip): the backward Riccati recursion over the A / Bm stacks ----
+int cddp_hip_plan_tvlqr(cddp_hip_handle *h, int flags, const double *Q, const double *R, const double *Qf, double *K_out, double *P_out, int32_t *info) {
+  static const char *const me = "cddp_hip_plan_tvlqr";
+  constexpr int known = CDDP_HIP_LQR_DEVICE | CDDP_HIP_LQR_PER_TRAJ | CDDP_HIP_LQR_INSTALL;
+  if (!h) return fail(-1, "%s: null handle", me);
+  if (flags & ~known) return fail(-2, "%s: unknown flag bits 0x%x (CDDP_HIP_LQR_DEVICE, CDDP_HIP_LQR_PER_TRAJ and CDDP_HIP_LQR_INSTALL are the flags)", me, (unsigned)(flags & ~known));
+  const bool dev = (flags & CDDP_HIP_LQR_DEVICE) != 0, per = (flags & CDDP_HIP_LQR_PER_TRAJ) != 0, install = (flags & CDDP_HIP_LQR_INSTALL) != 0;
+  if (!K_out && !P_out && !install) return fail(-1, "%s: K_out and P_out are both null and CDDP_HIP_LQR_INSTALL is not set: nothing to compute", me);
+  { int rc = sens_refuse_handle(me, h); if (rc) return rc; }
+  const size_t nx = (size_t)h->nx, nu = (size_t)h->nu, B = (size_t)h->B, lead = per ? B : 1;
+  if (!dev) {
+    if (Q && !ref_all_finite(Q, lead * nx * nx)) return fail(-2, "%s: Q holds a non-finite value", me);
+    if (R && !ref_all_finite(R, lead * nu * nu)) return fail(-2, "%s: R holds a non-finite value", me);
+    if (Qf && !ref_all_finite(Qf, lead * nx * nx)) return fail(-2, "%s: Qf holds a non-finite value", me);
+  }
+  HIPCHK(hipSetDevice(h->device));
+  const size_t eK = (size_t)h->N * nu * nx, eP = (size_t)(h->N + 1) * nx * nx;     // doubles per trajectory of K_out, of P_out
+  Staging st(h, me, dev);
+  const double *Qd, *Rd, *Qfd; double *Kd, *Pd; int32_t *infd;
+  st.in("Q", Q, lead * nx * nx * sizeof(double), &Qd);
+  st.in("R", R, lead * nu * nu * sizeof(double), &Rd);
+  st.in("Qf", Qf, lead * nx * nx * sizeof(double), &Qfd);
+  st.out("K_out", K_out, B * eK * sizeof(double), &Kd);
+  st.out("P_out", P_out, B * eP * sizeof(double), &Pd);
+  st.out("info", info, B * sizeof(int32_t), &infd);
+  { int rc = st.begin(); if (rc) return rc; }
+  { int rc = fork_from_user(h); if (rc) return rc; }
+  for (size_t gi = 0; gi < h->g.size(); ++gi) {
+    const Inner *q = h->g[gi];
+    const size_t b0 = (size_t)h->b0[gi], p0 = per ? b0 : 0;
+    const double *pool = (const double *)((const char *)q->dP + offsetof(ProblemDev, pool));
+    LqrArgs a;
+    // a weight that is given: the caller's, times dt where it is read (Q, R); one that is not: the handle's own Q dt / R dt / Qf, shared
+    a.Q = Qd ? Qd + p0 * nx * nx : pool + q->P.off_Qdt; a.q_per = Qd && per; a.q_scale = Qd ? q->P.dt : 1.0;
+    a.R = Rd ? Rd + p0 * nu * nu : pool + q->P.off_Rdt; a.r_per = Rd && per; a.r_scale = Rd ? q->P.dt : 1.0;
+    a.Qf = Qfd ? Qfd + p0 * nx * nx : pool + q->P.off_Qf; a.qf_per = Qfd && per;
+    a.K_out = Kd ? Kd + b0 * eK : nullptr; a.P_out = Pd ? Pd + b0 * eP : nullptr; a.info = infd ? infd + b0 : nullptr;
+    a.K_stack = install ? q->d.K : nullptr;
+    HIPCHK(plan_lqr(sens_stacks(q), a, q->stream));
   }
   return st.finish();
 }

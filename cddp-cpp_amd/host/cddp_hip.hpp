@@ -928,6 +928,16 @@ class HipBatchSolver : public ISolverAlgorithm {
     if (!h_) throw std::runtime_error("cddp_hip: planCovariance needs a resident batch (the plug-in route has no resident handle)");
     check(cddp_hip_plan_covariance(h_, flags, Sigma0, W, Wu, SX, SU, dcost));
   }
+  // NEW: the time-varying LQR gains K_t and cost-to-go matrices P_t of the plan's linearisation for the caller's tracking weights
+  // (cddp_hip_plan_tvlqr), over the stacks of the last backward sweep.  flags: CDDP_HIP_LQR_DEVICE (device pointers of the solver's device),
+  // CDDP_HIP_LQR_PER_TRAJ (the weights that are given are per trajectory), CDDP_HIP_LQR_INSTALL (K_t also goes into the gain stack: until
+  // the next sweep trackPlan, planJvp / planVjp, planCovariance and the feedback scoring evaluate the designed controller).  Q and R are
+  // unscaled (times dt inside), Qf as given; a weight nullptr: the batch's own.  Any output nullptr; all of them only with INSTALL.
+  void planTvlqr(int flags, const double *Q /* nx*nx | batch*nx*nx | nullptr */, const double *R /* nu*nu | batch*nu*nu | nullptr */,
+                 const double *Qf /* as Q */, double *K_out /* batch*N*nu*nx */, double *P_out /* batch*(N+1)*nx*nx */, int32_t *info = nullptr /* batch */) {
+    if (!h_) throw std::runtime_error("cddp_hip: planTvlqr needs a resident batch (the plug-in route has no resident handle)");
+    check(cddp_hip_plan_tvlqr(h_, flags, Q, R, Qf, K_out, P_out, info));
+  }
   // NEW: what ncand candidate control sequences per trajectory are worth, in one launch (cddp_hip_score_rollouts), and the seed taken from
   // the best of them (cddp_hip_seed_best).  Arrays are [batch][ncand][t][e]; flags: CDDP_HIP_SCORE_DEVICE (device pointers of the solver's
   // device), CDDP_HIP_SCORE_FEEDBACK (u = U + K_t (x - X_t) around the live plan, U may then be nullptr), CDDP_HIP_SCORE_X0_PER_CANDIDATE.

@@ -169,6 +169,8 @@ MPC_SHIFT_DUALS, MPC_X_DEVICE = 1, 2
 SENS_DEVICE = 1
 # cddp_hip_plan_covariance (include/cddp_hip.h, "state and control covariance along a solved plan")
 COV_DEVICE, COV_DIAG, COV_PER_TRAJ = 1, 2, 4
+# cddp_hip_plan_tvlqr (include/cddp_hip.h, "time-varying LQR tracking gains along a solved plan")
+LQR_DEVICE, LQR_PER_TRAJ, LQR_INSTALL = 1, 2, 4
 # cddp_hip_score_rollouts / cddp_hip_seed_best (include/cddp_hip.h, "scoring candidate control sequences and seeding from the best")
 SCORE_DEVICE = 1
 SCORE_FEEDBACK = 2
@@ -863,6 +865,7 @@ DEVICE_IO_ARGTYPES = {
     "cddp_hip_plan_jvp": [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
     "cddp_hip_plan_vjp": [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
     "cddp_hip_plan_covariance": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    "cddp_hip_plan_tvlqr": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
     "cddp_hip_score_rollouts": [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
     "cddp_hip_seed_best": [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p],
     "cddp_hip_sample_controls": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
@@ -890,7 +893,7 @@ EXPORTED_SYMBOLS = [
     "cddp_hip_costate_mode", "cddp_hip_costate_redos", "cddp_hip_ls_stage_counts", "cddp_hip_mpc_advance", "cddp_hip_mpc_run",
     "cddp_hip_plant_create", "cddp_hip_plant_destroy", "cddp_hip_plant_step", "cddp_hip_mpc_run_plant", "cddp_hip_track_plan",
     "cddp_hip_field_shape", "cddp_hip_get_field_device", "cddp_hip_get_results_device", "cddp_hip_set_initial_device", "cddp_hip_get_live_slots",
-    "cddp_hip_plan_jvp", "cddp_hip_plan_vjp", "cddp_hip_plan_covariance",
+    "cddp_hip_plan_jvp", "cddp_hip_plan_vjp", "cddp_hip_plan_covariance", "cddp_hip_plan_tvlqr",
     "cddp_hip_score_rollouts", "cddp_hip_seed_best",
     "cddp_hip_sample_controls", "cddp_hip_mppi_blend", "cddp_hip_mppi_refine",
     "cddp_hip_mc_sample_noise", "cddp_hip_plan_montecarlo",
@@ -1450,6 +1453,65 @@ class HipBatchSolver:
             out = {k: np.zeros(shapes[k]) for k in want}
             ptr = lambda a: a.ctypes.data if a is not None else None
         self._check(self.lib.cddp_hip_plan_covariance(self.h, flags, ptr(s0), ptr(w), ptr(wu), ptr(out.get("SX")), ptr(out.get("SU")), ptr(out.get("dcost"))))
+        return out
+
+    # ---- time-varying LQR gains along the plan (cddp_hip_plan_tvlqr): numpy arrays take the host path, torch.float64 tensors on the
+    # handle's device the device path; every argument of a call is of one kind, and so is the result (no weight given: numpy)
+    def plan_tvlqr(self, Q=None, R=None, Qf=None, install=False, want=("K", "P"), device=None):
+        """The finite-horizon LQR of the plan's linearisation for the caller's tracking weights (cddp_hip_plan_tvlqr): the backward
+        Riccati recursion over the A / B stacks of the last backward sweep.  Q (nx, nx) and R (nu, nu) are unscaled (the library multiplies
+        by dt), Qf (nx, nx) is used as given; None = the handle's own.  A weight with a leading B axis is per trajectory, and then every
+        weight that is given must be.  Only the lower triangles are read.  numpy arrays or torch.float64 tensors on the handle's device.
+        Returns a dict of the arguments' kind with the entries `want` names -- "K" (B, N, nu, nx), "P" (B, N + 1, nx, nx) -- and "info"
+        (B,) int32: 0, or t + 1 of the step whose factorisation failed (K = 0 and P = NaN from there down).  install=True also writes K
+        into the handle's gain stack: until the next backward sweep gains(), field_device("K"), track_plan, plan_jvp / plan_vjp,
+        plan_covariance, plan_montecarlo and the feedback scoring read the designed gains; want may then be empty.  device: with no
+        weight given, whether the results are device tensors (default: numpy arrays)."""
+        want = tuple(want)
+        if any(w not in ("K", "P") for w in want) or (not want and not install):
+            raise ValueError("want: a subset of ('K', 'P') is expected, non-empty unless install=True, got %r" % (want,))
+        N, nx, nu, B = self.p.N, self.p.nx, self.p.nu, self.B
+        given = [(name, a, n) for name, a, n in (("Q", Q, nx), ("R", R, nu), ("Qf", Qf, nx)) if a is not None]
+        kinds = {hasattr(a, "data_ptr") and not isinstance(a, np.ndarray) for _, a, _ in given}
+        if len(kinds) > 1:
+            raise ValueError("plan_tvlqr: Q, R and Qf must all be numpy arrays or all be device tensors")
+        if kinds:
+            kind = kinds.pop()
+            if device is not None and bool(device) != kind:
+                raise ValueError("plan_tvlqr: device=%r, but the weights are %s" % (device, "device tensors" if kind else "numpy arrays"))
+            device = kind
+        device = bool(device)
+        conv = {}
+        for name, a, n in given:
+            if not device:
+                if isinstance(a, np.ndarray) and a.dtype != np.float64:
+                    raise ValueError("plan_tvlqr: %s: dtype float64 is expected, got %s" % (name, a.dtype))
+                a = np.ascontiguousarray(a, dtype=np.float64)
+            conv[name] = a
+        ndims = {len(tuple(a.shape)) for a in conv.values()}
+        if ndims - {2, 3} or len(ndims) > 1:
+            raise ValueError("plan_tvlqr: the weights that are given must all have shape (n, n) or all have shape %s, got %s"
+                             % ((B, "n", "n"), ", ".join("%s %s" % (k, tuple(a.shape)) for k, a in conv.items())))
+        per = ndims == {3}
+        lead = (B,) if per else ()
+        args = {name: None for name in ("Q", "R", "Qf")}
+        for name, a, n in given:
+            args[name] = self._score_arg("plan_tvlqr", name, conv[name], (lead + (n, n),), device)
+        flags = (LQR_DEVICE if device else 0) | (LQR_PER_TRAJ if per else 0) | (LQR_INSTALL if install else 0)
+        shapes = {"K": (B, N, nu, nx), "P": (B, N + 1, nx, nx)}
+        if device:
+            import torch
+            dev = self._torch_device()
+            out = {k: torch.empty(shapes[k], dtype=torch.float64, device=dev) for k in want}
+            out["info"] = torch.empty((B,), dtype=torch.int32, device=dev)
+            self._order_device_io()
+            ptr = lambda a: a.data_ptr() if a is not None else None
+        else:
+            out = {k: np.zeros(shapes[k]) for k in want}
+            out["info"] = np.zeros((B,), dtype=np.int32)
+            ptr = lambda a: a.ctypes.data if a is not None else None
+        self._check(self.lib.cddp_hip_plan_tvlqr(self.h, flags, ptr(args["Q"]), ptr(args["R"]), ptr(args["Qf"]), ptr(out.get("K")), ptr(out.get("P")),
+                                                 ptr(out["info"])))
         return out
 
     # ---- scoring candidate control sequences and seeding from the best (cddp_hip_score_rollouts / cddp_hip_seed_best): numpy arrays take

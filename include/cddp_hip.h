@@ -772,6 +772,63 @@ int cddp_hip_plan_covariance(cddp_hip_handle *h, int flags,
                              double *SU    /* B*N*nu*nu     (DIAG: B*N*nu)     or NULL */,
                              double *dcost /* B or NULL */);
 
+/* ---- time-varying LQR tracking gains along a solved plan --------------------
+ * The gain stack a solve leaves behind is a by-product of the optimiser: rows of a clamped control are zero (CLDDP), the gains carry the
+ * barrier curvature at the last mu (IPDDP), and they belong to the regularised Quu of the last sweep.  cddp_hip_plan_tvlqr designs the
+ * controller a caller would stabilise the plan with instead: the finite-horizon LQR of the plan's linearisation (A_t, B_t) for the
+ * caller's own tracking weights, du_t = K_t dx_t minimising sum_t dx_t^T Qd dx_t + du_t^T Rd du_t, plus dx_N^T Qf dx_N, with its
+ * cost-to-go matrices P_t (dx_t^T P_t dx_t is the cost from step t on).  The recursion runs on the device over the stacks where the sweep
+ * left them (csrc/inst_lqr.hip: one workgroup per tile of trajectories walks the horizon backward, P_t in LDS).
+ * WHICH SWEEP: A_t, B_t are the stacks cddp_hip_get_linearization reads at the time of the call.  They belong to the LAST BACKWARD SWEEP,
+ * which ran at the iterate before the last accepted step; a caller who wants them at the returned plan calls cddp_hip_backward first.
+ * Weights: Q (nx*nx) and R (nu*nu) are unscaled, as in cddp_hip_problem: Qd[i][j] = Q[i][j] * dt and Rd[i][j] = R[i][j] * dt, one rounded product per element (formed where the element is read);
+ * Qf (nx*nx) is used as given.  A NULL weight means the handle's own Q dt / R dt / Qf, as cddp_hip_plan_covariance reads them for dcost.
+ * With CDDP_HIP_LQR_PER_TRAJ every weight that is given is one matrix per trajectory, batch-major (B*nx*nx, B*nu*nu, B*nx*nx); weights
+ * that are not given stay the handle's.  Only the lower triangles (j <= i) are read: element [i][j] with j > i stands for element [j][i].
+ * Outputs: K_out [b][t][k][j] for t = 0 .. N-1, P_out [b][t][i][j] for t = 0 .. N (row N is Qf's lower triangle mirrored; every P_t is
+ * exactly symmetric), info [b]; any may be NULL.  Batch-major, contiguous, matrices row-major.
+ * flags without CDDP_HIP_LQR_DEVICE: host pointers; the call uploads, computes, downloads and returns when the outputs are written.
+ * CDDP_HIP_LQR_DEVICE: every array argument is a device pointer of the handle's device, checked and ordered as
+ * cddp_hip_plan_covariance checks and orders its own; a handle of several tile groups offsets the pointers per group.
+ * The handle's plan, duals and solver state are not modified.
+ * CDDP_HIP_LQR_INSTALL additionally writes K_t into the handle's gain stack; the feedforward k_t is left alone.  From then until the next
+ * backward sweep (cddp_hip_backward, cddp_hip_solve, an MPC step) the installed gains are what cddp_hip_get_gains and CDDP_HIP_FIELD_K
+ * return and what cddp_hip_track_plan, cddp_hip_plan_jvp / _vjp, cddp_hip_plan_covariance, cddp_hip_plan_montecarlo and
+ * cddp_hip_score_rollouts(CDDP_HIP_SCORE_FEEDBACK) read: they evaluate the designed controller.  The gain stack is dead state at the
+ * start of a solve (every iteration sweeps before it rolls out, and cddp_hip_mpc_advance moves X | U | S | Y only): a later solve is bit
+ * for bit the solve of a handle that never installed anything.  cddp_hip_forward is a single step of the solver, not one of the entries
+ * above: it rolls out with the gains of its own route, which need not be the installed ones; call cddp_hip_backward before it.
+ * Arithmetic (the library is built with -ffp-contract=off: every product is rounded before it is added; true division and square root,
+ * no reciprocals).  Every sum starts at the stated value and runs with the index ascending.  Per trajectory P_N = Qf mirrored; for
+ * t = N-1 .. 0, with P = P_{t+1}, A = A_t, B = B_t:
+ *  1. M[i][k] (nx x nu): s = 0; for l ascending s += P[i][l] * B[l][k].
+ *  2. Quu[r][c] for c <= r: s = 0; for l ascending s += B[l][r] * M[l][c]; then s += Rd[r][c].
+ *  3. Qux[k][j] (nu x nx): s = 0; for l ascending s += M[l][k] * A[l][j].
+ *  4. Quu = L L^T, rows r ascending.  For c < r: s = Quu[r][c]; for m < c ascending s -= L[r][m] * L[c][m]; L[r][c] = s / L[c][c].
+ *     Diagonal: s = Quu[r][r]; for m < r ascending s -= L[r][m] * L[r][m]; the step FAILS unless s > 0; L[r][r] = sqrt(s).
+ *  5. For every column j.  Forward, r ascending: s = Qux[r][j]; for m < r ascending s -= L[r][m] * y[m]; y[r] = s / L[r][r].
+ *     Backward, r descending: s = y[r]; for m > r ascending s -= L[m][r] * z[m]; z[r] = s / L[r][r].  K_t[r][j] = -z[r].
+ *  6. Acl[i][j]: s = A[i][j]; for k ascending s += B[i][k] * K_t[k][j].
+ *  7. Y[i][j]: s = 0; for l ascending s += P[i][l] * Acl[l][j].
+ *  8. T[k][j] (nu x nx): s = 0; for m ascending s += Rd[k][m] * K_t[m][j].
+ *  9. P_t[i][j] for j <= i: s = 0; for l ascending s += Acl[l][i] * Y[l][j]; h = 0; for k ascending h += K_t[k][i] * T[k][j]; s += h;
+ *     s += Qd[i][j].  Mirrored.  (The Joseph form P_t = Qd + K^T Rd K + Acl^T P Acl: symmetric by construction.)
+ * Failure of one trajectory: the walk goes backward, so the first failed step met is the largest such t.  Then info[b] = t + 1, and
+ * K_s = 0 (also in the installed stack) and P_s = NaN for every s <= t; rows s > t are those computed.  Otherwise info[b] = 0.  Other
+ * trajectories are unaffected.  Non-finite stack rows end in a failed pivot (NaN > 0 is false).  (The sign of an exact zero is not
+ * specified.)
+ * Refused before anything is launched, each with its own message, nothing changed: a NULL handle, unknown flag bits, K_out and P_out NULL
+ * without CDDP_HIP_LQR_INSTALL (nothing to compute), a handle that was never solved or swept, an MSIPDDP handle, a non-finite value in a
+ * host weight, and with CDDP_HIP_LQR_DEVICE a pointer cddp_hip_get_field_device would refuse.  (New entry point; ABI version unchanged.) */
+enum { CDDP_HIP_LQR_DEVICE = 1, CDDP_HIP_LQR_PER_TRAJ = 2, CDDP_HIP_LQR_INSTALL = 4 };
+int cddp_hip_plan_tvlqr(cddp_hip_handle *h, int flags,
+                        const double *Q  /* nx*nx | B*nx*nx with PER_TRAJ, or NULL */,
+                        const double *R  /* nu*nu | B*nu*nu, or NULL */,
+                        const double *Qf /* nx*nx | B*nx*nx, or NULL */,
+                        double *K_out    /* B*N*nu*nx or NULL */,
+                        double *P_out    /* B*(N+1)*nx*nx or NULL */,
+                        int32_t *info    /* B or NULL */);
+
 /* ---- scoring candidate control sequences and seeding from the best -----------
  * The plan a nonconvex solve ends in depends on the control sequence it starts from.  cddp_hip_score_rollouts rolls S candidate control
  * sequences per trajectory out in ONE launch (csrc/inst_score.hip, one lane per trajectory and candidate) and returns what each is worth:
