@@ -19,6 +19,7 @@
 #include "sens_kernels.hpp"
 #include "cov_kernels.hpp"
 #include "lqr_kernels.hpp"
+#include "kf_kernels.hpp"
 #include "score_kernels.hpp"
 #include "mppi_kernels.hpp"
 #include "mc_kernels.hpp"
@@ -2751,6 +2752,66 @@ int cddp_hip_plan_tvlqr(cddp_hip_handle *h, int flags, const double *Q, const do
     a.K_out = Kd ? Kd + b0 * eK : nullptr; a.P_out = Pd ? Pd + b0 * eP : nullptr; a.info = infd ? infd + b0 : nullptr;
     a.K_stack = install ? q->d.K : nullptr;
     HIPCHK(plan_lqr(sens_stacks(q), a, q->stream));
+  }
+  return st.finish();
+}
+
+// ---- Kalman filter gains and output-feedback covariance along the plan (inst_kf.hip): the forward dual of the recursion above ----
+int cddp_hip_plan_kalman(cddp_hip_handle *h, int flags, int ny, const double *C, const double *v, const double *Sigma0, const double *W, const double *Wu,
+                         double *L_out, double *SP_out, double *SF_out, double *SX, double *SU, double *dcost, int32_t *info) {
+  static const char *const me = "cddp_hip_plan_kalman";
+  constexpr int known = CDDP_HIP_KF_DEVICE | CDDP_HIP_KF_DIAG | CDDP_HIP_KF_PER_TRAJ;
+  if (!h) return fail(-1, "%s: null handle", me);
+  if (flags & ~known) return fail(-2, "%s: unknown flag bits 0x%x (CDDP_HIP_KF_DEVICE, CDDP_HIP_KF_DIAG and CDDP_HIP_KF_PER_TRAJ are the flags)", me, (unsigned)(flags & ~known));
+  if (ny < 1 || ny > CDDP_HIP_KF_MAX_NY) return fail(-2, "%s: ny = %d, 1 .. %d measurement rows are expected", me, ny, CDDP_HIP_KF_MAX_NY);
+  if (!C) return fail(-1, "%s: null C pointer", me);
+  if (!v) return fail(-1, "%s: null v pointer", me);
+  if (!Sigma0) return fail(-1, "%s: null Sigma0 pointer", me);
+  if (!L_out && !SP_out && !SF_out && !SX && !SU && !dcost && !info) return fail(-1, "%s: all six outputs and info are null: nothing to compute", me);
+  { int rc = sens_refuse_handle(me, h); if (rc) return rc; }
+  const bool dev = (flags & CDDP_HIP_KF_DEVICE) != 0, diag = (flags & CDDP_HIP_KF_DIAG) != 0, per = (flags & CDDP_HIP_KF_PER_TRAJ) != 0;
+  const size_t nx = (size_t)h->nx, nu = (size_t)h->nu, B = (size_t)h->B, lead = per ? B : 1, m = (size_t)ny;
+  if (!dev) {
+    for (size_t i = 0; i < lead * m; ++i)
+      if (!std::isfinite(v[i]) || !(v[i] > 0.0)) return fail(-2, "%s: v holds an entry that is not finite and > 0 (a measurement variance)", me);
+    if (!ref_all_finite(C, lead * m * nx)) return fail(-2, "%s: C holds a non-finite value", me);
+    if (!ref_all_finite(Sigma0, lead * nx * nx)) return fail(-2, "%s: Sigma0 holds a non-finite value", me);
+    if (W && !ref_all_finite(W, lead * nx * nx)) return fail(-2, "%s: W holds a non-finite value", me);
+    if (Wu && !ref_all_finite(Wu, lead * nu * nu)) return fail(-2, "%s: Wu holds a non-finite value", me);
+  }
+  HIPCHK(hipSetDevice(h->device));
+  const size_t eL = (size_t)(h->N + 1) * nx * m;                                                            // doubles per trajectory of L_out
+  const size_t eX = (size_t)(h->N + 1) * (diag ? nx : nx * nx), eU = (size_t)h->N * (diag ? nu : nu * nu);   // ... of SP / SF / SX, of SU
+  Staging st(h, me, dev);
+  const double *Cd, *vd, *S0d, *Wd, *Wud; double *Ld, *SPd, *SFd, *SXd, *SUd, *dcd; int32_t *infd;
+  st.in("C", C, lead * m * nx * sizeof(double), &Cd);
+  st.in("v", v, lead * m * sizeof(double), &vd);
+  st.in("Sigma0", Sigma0, lead * nx * nx * sizeof(double), &S0d);
+  st.in("W", W, lead * nx * nx * sizeof(double), &Wd);
+  st.in("Wu", Wu, lead * nu * nu * sizeof(double), &Wud);
+  st.out("L_out", L_out, B * eL * sizeof(double), &Ld);
+  st.out("SP_out", SP_out, B * eX * sizeof(double), &SPd);
+  st.out("SF_out", SF_out, B * eX * sizeof(double), &SFd);
+  st.out("SX", SX, B * eX * sizeof(double), &SXd);
+  st.out("SU", SU, B * eU * sizeof(double), &SUd);
+  st.out("dcost", dcost, B * sizeof(double), &dcd);
+  st.out("info", info, B * sizeof(int32_t), &infd);
+  { int rc = st.begin(); if (rc) return rc; }
+  { int rc = fork_from_user(h); if (rc) return rc; }
+  for (size_t gi = 0; gi < h->g.size(); ++gi) {
+    const Inner *q = h->g[gi];
+    const size_t b0 = (size_t)h->b0[gi], p0 = per ? b0 : 0;
+    const double *pool = (const double *)((const char *)q->dP + offsetof(ProblemDev, pool));
+    KfArgs a;
+    a.ny = ny;
+    a.C = Cd + p0 * m * nx; a.v = vd + p0 * m; a.Sigma0 = S0d + p0 * nx * nx;
+    a.W = Wd ? Wd + p0 * nx * nx : nullptr; a.Wu = Wud ? Wud + p0 * nu * nu : nullptr;
+    a.L = Ld ? Ld + b0 * eL : nullptr; a.SP = SPd ? SPd + b0 * eX : nullptr; a.SF = SFd ? SFd + b0 * eX : nullptr;
+    a.SX = SXd ? SXd + b0 * eX : nullptr; a.SU = SUd ? SUd + b0 * eU : nullptr; a.dcost = dcd ? dcd + b0 : nullptr;
+    a.info = infd ? infd + b0 : nullptr;
+    a.Qdt = pool + q->P.off_Qdt; a.Rdt = pool + q->P.off_Rdt; a.Qf = pool + q->P.off_Qf;
+    a.per_traj = per ? 1 : 0; a.diag = diag ? 1 : 0;
+    HIPCHK(plan_kf(sens_stacks(q), a, q->stream));
   }
   return st.finish();
 }

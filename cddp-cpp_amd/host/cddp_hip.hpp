@@ -938,6 +938,19 @@ class HipBatchSolver : public ISolverAlgorithm {
     if (!h_) throw std::runtime_error("cddp_hip: planTvlqr needs a resident batch (the plug-in route has no resident handle)");
     check(cddp_hip_plan_tvlqr(h_, flags, Q, R, Qf, K_out, P_out, info));
   }
+  // NEW: the Kalman filter gains L_t of the plan's linearisation for the sensors y_t = C dx_t + n_t, cov(n_t) = diag(v), and the covariance
+  // of states and controls when the batch's gains act on the filtered estimate (cddp_hip_plan_kalman), over the stacks of the last backward
+  // sweep; after planTvlqr with CDDP_HIP_LQR_INSTALL the gains are the installed ones.  flags: CDDP_HIP_KF_DEVICE (device pointers of the
+  // solver's device), CDDP_HIP_KF_DIAG (diagonals of SP, SF, SX and SU only), CDDP_HIP_KF_PER_TRAJ (every given input per trajectory).
+  // 1 <= ny <= CDDP_HIP_KF_MAX_NY.  W or Wu nullptr: no such noise; any output nullptr, not all.
+  void planKalman(int flags, int ny, const double *C /* ny*nx | batch*ny*nx */, const double *v /* ny | batch*ny */,
+                  const double *Sigma0 /* nx*nx | batch*nx*nx */, const double *W /* as Sigma0, or nullptr */,
+                  const double *Wu /* nu*nu | batch*nu*nu, or nullptr */, double *L_out /* batch*(N+1)*nx*ny */,
+                  double *SP_out /* batch*(N+1)*nx*nx (DIAG: batch*(N+1)*nx) */, double *SF_out /* as SP_out */, double *SX /* as SP_out */,
+                  double *SU /* batch*N*nu*nu (DIAG: batch*N*nu) */, double *dcost /* batch */, int32_t *info = nullptr /* batch */) {
+    if (!h_) throw std::runtime_error("cddp_hip: planKalman needs a resident batch (the plug-in route has no resident handle)");
+    check(cddp_hip_plan_kalman(h_, flags, ny, C, v, Sigma0, W, Wu, L_out, SP_out, SF_out, SX, SU, dcost, info));
+  }
   // NEW: what ncand candidate control sequences per trajectory are worth, in one launch (cddp_hip_score_rollouts), and the seed taken from
   // the best of them (cddp_hip_seed_best).  Arrays are [batch][ncand][t][e]; flags: CDDP_HIP_SCORE_DEVICE (device pointers of the solver's
   // device), CDDP_HIP_SCORE_FEEDBACK (u = U + K_t (x - X_t) around the live plan, U may then be nullptr), CDDP_HIP_SCORE_X0_PER_CANDIDATE.

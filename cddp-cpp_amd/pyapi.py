@@ -171,6 +171,9 @@ SENS_DEVICE = 1
 COV_DEVICE, COV_DIAG, COV_PER_TRAJ = 1, 2, 4
 # cddp_hip_plan_tvlqr (include/cddp_hip.h, "time-varying LQR tracking gains along a solved plan")
 LQR_DEVICE, LQR_PER_TRAJ, LQR_INSTALL = 1, 2, 4
+# cddp_hip_plan_kalman (include/cddp_hip.h, "Kalman filter gains and output-feedback covariance along a solved plan")
+KF_DEVICE, KF_DIAG, KF_PER_TRAJ = 1, 2, 4
+KF_MAX_NY = 16
 # cddp_hip_score_rollouts / cddp_hip_seed_best (include/cddp_hip.h, "scoring candidate control sequences and seeding from the best")
 SCORE_DEVICE = 1
 SCORE_FEEDBACK = 2
@@ -866,6 +869,7 @@ DEVICE_IO_ARGTYPES = {
     "cddp_hip_plan_vjp": [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
     "cddp_hip_plan_covariance": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
     "cddp_hip_plan_tvlqr": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    "cddp_hip_plan_kalman": [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 12,
     "cddp_hip_score_rollouts": [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
     "cddp_hip_seed_best": [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p],
     "cddp_hip_sample_controls": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
@@ -893,7 +897,7 @@ EXPORTED_SYMBOLS = [
     "cddp_hip_costate_mode", "cddp_hip_costate_redos", "cddp_hip_ls_stage_counts", "cddp_hip_mpc_advance", "cddp_hip_mpc_run",
     "cddp_hip_plant_create", "cddp_hip_plant_destroy", "cddp_hip_plant_step", "cddp_hip_mpc_run_plant", "cddp_hip_track_plan",
     "cddp_hip_field_shape", "cddp_hip_get_field_device", "cddp_hip_get_results_device", "cddp_hip_set_initial_device", "cddp_hip_get_live_slots",
-    "cddp_hip_plan_jvp", "cddp_hip_plan_vjp", "cddp_hip_plan_covariance", "cddp_hip_plan_tvlqr",
+    "cddp_hip_plan_jvp", "cddp_hip_plan_vjp", "cddp_hip_plan_covariance", "cddp_hip_plan_tvlqr", "cddp_hip_plan_kalman",
     "cddp_hip_score_rollouts", "cddp_hip_seed_best",
     "cddp_hip_sample_controls", "cddp_hip_mppi_blend", "cddp_hip_mppi_refine",
     "cddp_hip_mc_sample_noise", "cddp_hip_plan_montecarlo",
@@ -1512,6 +1516,69 @@ class HipBatchSolver:
             ptr = lambda a: a.ctypes.data if a is not None else None
         self._check(self.lib.cddp_hip_plan_tvlqr(self.h, flags, ptr(args["Q"]), ptr(args["R"]), ptr(args["Qf"]), ptr(out.get("K")), ptr(out.get("P")),
                                                  ptr(out["info"])))
+        return out
+
+    # ---- Kalman filter gains and output-feedback covariance along the plan (cddp_hip_plan_kalman): numpy arrays take the host path,
+    # torch.float64 tensors on the handle's device the device path; every argument of a call is of one kind, and so is the result
+    def plan_kalman(self, C, v, Sigma0, W=None, Wu=None, diag=False, want=("L", "SX", "SU", "dcost"), device=None):
+        """The Kalman filter of the plan's linearisation for the sensors y_t = C dx_t + n_t, cov(n_t) = diag(v), and the covariance of
+        states and controls when the handle's gains act on the filtered estimate (cddp_hip_plan_kalman), over the stacks of the last
+        backward sweep; after plan_tvlqr(install=True) the gains are the installed ones.  C: (ny, nx) with 1 <= ny <= KF_MAX_NY, v: (ny,)
+        measurement variances, Sigma0 (nx, nx), W (nx, nx) and Wu (nu, nu) or None; with a leading B axis on C every input is per
+        trajectory.  Only the lower triangles of Sigma0, W and Wu are read.  numpy arrays or torch.float64 tensors on the handle's device,
+        never mixed.  Returns a dict of the arguments' kind with the entries `want` names: "L" (B, N + 1, nx, ny) the filter gains, "SP"
+        and "SF" (B, N + 1, nx, nx) the error covariance before and after the measurement, "SX" (B, N + 1, nx, nx) and "SU" (B, N, nu, nu)
+        the covariance of states and controls under output feedback -- diag=True: the diagonals of SP, SF, SX and SU -- "dcost" (B,) and
+        "info" (B,) int32: 0, or t + 1 of the step at which a measurement row failed (NaN from that row on).  device: must agree with
+        the arguments' kind if given.  The handle's state is not modified."""
+        names = ("L", "SP", "SF", "SX", "SU", "dcost", "info")
+        want = tuple(want)
+        if not want or any(w not in names for w in want):
+            raise ValueError("want: a non-empty subset of %r is expected, got %r" % (names, want))
+        if C is None or v is None or Sigma0 is None:
+            raise ValueError("plan_kalman: C, v and Sigma0 must be given")
+        N, nx, nu, B = self.p.N, self.p.nx, self.p.nu, self.B
+        given = [(name, a) for name, a in (("C", C), ("v", v), ("Sigma0", Sigma0), ("W", W), ("Wu", Wu)) if a is not None]
+        kinds = {hasattr(a, "data_ptr") and not isinstance(a, np.ndarray) for _, a in given}
+        if len(kinds) > 1:
+            raise ValueError("plan_kalman: C, v, Sigma0, W and Wu must all be numpy arrays or all be device tensors")
+        kind = kinds.pop()
+        if device is not None and bool(device) != kind:
+            raise ValueError("plan_kalman: device=%r, but the arguments are %s" % (device, "device tensors" if kind else "numpy arrays"))
+        device = kind
+        conv = {}
+        for name, a in given:
+            if not device:
+                if isinstance(a, np.ndarray) and a.dtype != np.float64:
+                    raise ValueError("plan_kalman: %s: dtype float64 is expected, got %s" % (name, a.dtype))
+                a = np.ascontiguousarray(a, dtype=np.float64)
+            conv[name] = a
+        cs = tuple(conv["C"].shape)
+        if len(cs) not in (2, 3) or cs[-1] != nx or (len(cs) == 3 and cs[0] != B):
+            raise ValueError("plan_kalman: C: shape %s or %s is expected, got %s" % (("ny", nx), (B, "ny", nx), cs))
+        ny = int(cs[-2])
+        if not 1 <= ny <= KF_MAX_NY:
+            raise ValueError("plan_kalman: C has %d rows, 1 .. %d measurement rows are expected" % (ny, KF_MAX_NY))
+        per = len(cs) == 3
+        lead = (B,) if per else ()
+        tails = {"C": (ny, nx), "v": (ny,), "Sigma0": (nx, nx), "W": (nx, nx), "Wu": (nu, nu)}
+        args = {name: None for name in tails}
+        for name, _ in given:
+            args[name] = self._score_arg("plan_kalman", name, conv[name], (lead + tails[name],), device)
+        flags = (KF_DEVICE if device else 0) | (KF_DIAG if diag else 0) | (KF_PER_TRAJ if per else 0)
+        sx = (B, N + 1, nx) if diag else (B, N + 1, nx, nx)
+        shapes = {"L": (B, N + 1, nx, ny), "SP": sx, "SF": sx, "SX": sx, "SU": (B, N, nu) if diag else (B, N, nu, nu), "dcost": (B,), "info": (B,)}
+        if device:
+            import torch
+            dev = self._torch_device()
+            out = {k: torch.empty(shapes[k], dtype=torch.int32 if k == "info" else torch.float64, device=dev) for k in want}
+            self._order_device_io()
+            ptr = lambda a: a.data_ptr() if a is not None else None
+        else:
+            out = {k: np.zeros(shapes[k], dtype=np.int32 if k == "info" else np.float64) for k in want}
+            ptr = lambda a: a.ctypes.data if a is not None else None
+        self._check(self.lib.cddp_hip_plan_kalman(self.h, flags, ny, ptr(args["C"]), ptr(args["v"]), ptr(args["Sigma0"]), ptr(args["W"]), ptr(args["Wu"]),
+                                                  *[ptr(out.get(k)) for k in names]))
         return out
 
     # ---- scoring candidate control sequences and seeding from the best (cddp_hip_score_rollouts / cddp_hip_seed_best): numpy arrays take

@@ -829,6 +829,73 @@ int cddp_hip_plan_tvlqr(cddp_hip_handle *h, int flags,
                         double *P_out    /* B*(N+1)*nx*nx or NULL */,
                         int32_t *info    /* B or NULL */);
 
+/* ---- Kalman filter gains and output-feedback covariance along a solved plan --
+ * The entries above assume the controller sees the state.  With sensors, which estimator gains go with the plan, and how uncertain are
+ * states and controls when the feedback acts on the estimate?  The perturbation model is that of cddp_hip_plan_covariance,
+ * dx_{t+1} = A_t dx_t + B_t (du_t + eps_t) + w_t, cov(dx_0) = Sigma0, cov(w_t) = W, cov(eps_t) = Wu, white in time, with a measurement at
+ * every step t = 0 .. N, taken before u_t is applied: y_t = C dx_t + n_t, cov(n_t) = diag(v), C ny x nx with 1 <= ny <= CDDP_HIP_KF_MAX_NY
+ * (ny may exceed nx).  The feedback acts on the filtered estimate, du_t = K_t xhat_t|t, with K_t the handle's gain stack at the time of the
+ * call.  cddp_hip_plan_kalman runs the filter and the covariance recursion on the device over the stacks where the sweep left them
+ * (csrc/inst_kf.hip: one workgroup per tile of trajectories walks the horizon forward, the two covariances in LDS).
+ * Measurement noise is DIAGONAL on purpose: the rows of a step are then processed one at a time, with no factorisation, and ny is a
+ * run-time number.  Correlated measurement noise is the caller's to whiten (C <- V^-1/2 C, v <- 1).  C, v, W and Wu do not vary in time.
+ * WHICH SWEEP: K_t, A_t, B_t are the stacks cddp_hip_get_gains and cddp_hip_get_linearization read at the time of the call.  They belong to
+ * the LAST BACKWARD SWEEP, which ran at the iterate before the last accepted step; a caller who wants them at the returned plan calls
+ * cddp_hip_backward first.  After cddp_hip_plan_tvlqr with CDDP_HIP_LQR_INSTALL the recursion sees the installed gains.
+ * Arrays: batch-major, contiguous doubles, matrices row-major.  C (ny*nx), v (ny), Sigma0, W (nx*nx) and Wu (nu*nu) are ONE array each
+ * for the whole batch, or with CDDP_HIP_KF_PER_TRAJ one per trajectory, every given input together (B*ny*nx, B*ny, ...); W and Wu may be
+ * NULL (no such noise).  Only the lower triangles (j <= i) of Sigma0, W and Wu are read.  Outputs, any may be NULL, not all with info:
+ * L_out [b][t][i][r] the filter gain of step t (xhat_t|t = xhat_t|t-1 + L_t (y_t - C xhat_t|t-1)), SP_out [b][t][i][j] the error
+ * covariance Sm_t before the measurement of step t, SF_out the one after it (Sf_t), SX [b][t][i][j] the covariance of the true state
+ * under output feedback, all for t = 0 .. N; SU [b][t][i][j] = cov(du_t) for t = 0 .. N-1; dcost [b] as cddp_hip_plan_covariance's, with
+ * these SX and SU; info [b].  With CDDP_HIP_KF_DIAG only the diagonals of SP_out, SF_out, SX and SU are written ([b][t][i]); L_out is
+ * always full, and the recursion itself is the full one.
+ * flags without CDDP_HIP_KF_DEVICE: host pointers; the call uploads, computes, downloads and returns when the outputs are written.
+ * CDDP_HIP_KF_DEVICE: every array argument is a device pointer of the handle's device, checked and ordered as
+ * cddp_hip_plan_covariance checks and orders its own; a handle of several tile groups offsets the pointers per group.
+ * The handle's plan, gains, duals and solver state are not modified.
+ * Arithmetic (the library is built with -ffp-contract=off: every product is rounded before it is added; true division, no reciprocals).
+ * Every sum starts at the stated value and runs with the index ascending; every symmetric quantity is computed for j <= i and mirrored.
+ * Per trajectory Sm_0 = Sigma0 (mirrored) and Xm_0 = 0 (the covariance of the predicted estimate).  For t = 0 .. N:
+ *  1. The update.  S = Sm_t, G = 0; for the rows r = 0 .. ny-1 of C ascending, with c = C[r]:
+ *     a. h[i]: s = 0; for j ascending s += S[i][j] * c[j].
+ *     b. sr: s = v[r]; for j ascending s += c[j] * h[j].  The row FAILS unless sr > 0.
+ *     c. g[i] = h[i] / sr.
+ *     d. S[i][j] for j <= i: e = S[i][j]; e -= g[i] * h[j]; e -= h[i] * g[j]; q = sr * g[i]; e += q * g[j].  Mirrored.  (The symmetric
+ *        Joseph form S - g h^T - h g^T + sr g g^T.  An all-zero row of C leaves S unchanged: h = 0, g = 0.)
+ *     e. G[i][j] for j <= i: G[i][j] += h[i] * g[j].  Mirrored.  (A sum of rank-one terms: no covariance is subtracted from another.)
+ *     Sf_t = S after the last row.
+ *  2. L_t[i][r]: s = 0; for j ascending s += Sf_t[i][j] * C[r][j]; L_t[i][r] = s / v[r].  (Equal to Sm C^T (C Sm C^T + V)^-1.)
+ *  3. Xh_t[i][j] = Xm_t[i][j] + G[i][j] (the covariance of the filtered estimate), and SX_t[i][j] = Xh_t[i][j] + Sf_t[i][j].
+ *  4. For t < N, in the steps of cddp_hip_plan_covariance's arithmetic: Acl by its step 1; SU_t by its steps 2 and 3 with Xh_t in the place
+ *     of Sigma_t; Sm_{t+1} by its steps 4 and 5 with A_t in the place of Acl and Sf_t in the place of Sigma_t (W and Wu added as there);
+ *     Xm_{t+1} by its steps 4 and 5 with Xh_t in the place of Sigma_t and neither W nor Wu.
+ *  5. dcost by its step 6 with SX_t and SU_t, the term of Qf and SX_N added last.
+ * Failure of one trajectory: the walk goes forward; the first failed row, at step t, gives info[b] = t + 1, every output row s >= t of
+ * that trajectory is NaN (rows before it are those computed) and its dcost is NaN.  Otherwise info[b] = 0.  Other trajectories are
+ * unaffected.  Non-finite stack rows end in a failed row (NaN > 0 is false).  (The sign of an exact zero is not specified.)
+ * Not covered: correlated measurement noise, time-varying C, v or W, intermittent measurements, an estimator inside cddp_hip_track_plan,
+ * cddp_hip_plan_montecarlo or the MPC loop, and the relinearisation of an extended Kalman filter.
+ * Refused before anything is launched, each with its own message, nothing changed: a NULL handle, unknown flag bits, ny outside
+ * 1 .. CDDP_HIP_KF_MAX_NY, a NULL C, v or Sigma0, all six outputs and info NULL, a handle that was never solved or swept, an MSIPDDP
+ * handle, a host v with an entry that is not finite or not > 0, a non-finite value in any other host input, and with CDDP_HIP_KF_DEVICE a
+ * pointer cddp_hip_get_field_device would refuse.  (New entry point; ABI version unchanged.) */
+enum { CDDP_HIP_KF_DEVICE = 1, CDDP_HIP_KF_DIAG = 2, CDDP_HIP_KF_PER_TRAJ = 4 };
+#define CDDP_HIP_KF_MAX_NY 16
+int cddp_hip_plan_kalman(cddp_hip_handle *h, int flags, int ny,
+                         const double *C      /* ny*nx | B*ny*nx with PER_TRAJ */,
+                         const double *v      /* ny | B*ny: measurement variances */,
+                         const double *Sigma0 /* nx*nx | B*nx*nx */,
+                         const double *W      /* nx*nx | B*nx*nx, or NULL */,
+                         const double *Wu     /* nu*nu | B*nu*nu, or NULL */,
+                         double *L_out  /* B*(N+1)*nx*ny or NULL */,
+                         double *SP_out /* prior Sm_t:     B*(N+1)*nx*nx (DIAG: B*(N+1)*nx) or NULL */,
+                         double *SF_out /* posterior Sf_t: same shape, or NULL */,
+                         double *SX     /* as cddp_hip_plan_covariance's, or NULL */,
+                         double *SU     /* B*N*nu*nu (DIAG: B*N*nu) or NULL */,
+                         double *dcost  /* B or NULL */,
+                         int32_t *info  /* B or NULL */);
+
 /* ---- scoring candidate control sequences and seeding from the best -----------
  * The plan a nonconvex solve ends in depends on the control sequence it starts from.  cddp_hip_score_rollouts rolls S candidate control
  * sequences per trajectory out in ONE launch (csrc/inst_score.hip, one lane per trajectory and candidate) and returns what each is worth:
