@@ -23,6 +23,7 @@
 #include "score_kernels.hpp"
 #include "mppi_kernels.hpp"
 #include "mc_kernels.hpp"
+#include "mcof_kernels.hpp"
 #include "ref_kernels.hpp"
 
 // 1 when a[0] > a[1] > ... > a[n - 1] (NaN-free): the ladders cddp_hip_build_alphas makes; DevBuf::ladder_sorted
@@ -3428,6 +3429,108 @@ int cddp_hip_plan_montecarlo(cddp_hip_handle *h, cddp_hip_plant *plant, int flag
     a.cost = go[0]; a.viol = go[1]; a.stats = go[2]; a.dXmean = go[3]; a.SX = go[4]; a.dUmean = go[5]; a.SU = go[6]; a.X_out = go[7]; a.U_out = go[8];
     a.nviol_step = cntd ? cntd + b0 * nCnt : nullptr;
     { int rc = plant_launch_rc(mc_launch(pd, q->d, a, f, q->stream), me, "sampling", pd); if (rc) return rc; }
+  }
+  return st.finish();
+}
+
+
+// ---- Monte-Carlo evaluation under output feedback (inst_mcof.hip): the entries above with the estimator of csrc/plan_mcof.hpp in every lane ----
+// The refusals of the sensor model, after mc_refuse's: fills sd[r] = sqrt(v[r]) (the host's sqrt is correctly rounded).
+static int mcof_refuse(const char *me, const cddp_hip_mcof_desc *desc, int nx, bool need_C, double *sd) {
+  if (desc->ny < 1 || desc->ny > CDDP_HIP_KF_MAX_NY) return fail(-2, "%s: ny = %d, 1 .. %d measurement rows are expected", me, desc->ny, CDDP_HIP_KF_MAX_NY);
+  if (need_C && !desc->C) return fail(-1, "%s: null C pointer", me);
+  if (!desc->v) return fail(-1, "%s: null v pointer", me);
+  for (int r = 0; r < desc->ny; ++r) {
+    if (!std::isfinite(desc->v[r]) || !(desc->v[r] > 0.0)) return fail(-2, "%s: v[%d] = %g is not finite and > 0 (a measurement variance)", me, r, desc->v[r]);
+    sd[r] = std::sqrt(desc->v[r]);
+  }
+  if (need_C && !ref_all_finite(desc->C, (size_t)desc->ny * (size_t)nx)) return fail(-2, "%s: C holds a non-finite value", me);
+  return 0;
+}
+
+int cddp_hip_mc_sample_meas_noise(cddp_hip_handle *h, int flags, const cddp_hip_mcof_desc *desc, double *Yn) {
+  static const char *const me = "cddp_hip_mc_sample_meas_noise";
+  McArgs a;
+  McFactors f;
+  double sd[CDDP_HIP_KF_MAX_NY];
+  { int rc = mc_refuse(me, h, flags, CDDP_HIP_MC_DEVICE, desc ? &desc->mc : nullptr, &a, &f); if (rc) return rc; }
+  { int rc = mcof_refuse(me, desc, h->nx, false, sd); if (rc) return rc; }
+  if (!Yn) return fail(-1, "%s: Yn is NULL: there is nothing to write", me);
+  const bool dev = (flags & CDDP_HIP_MC_DEVICE) != 0;
+  const size_t B = (size_t)h->B, S = (size_t)desc->mc.nsamp, ny = (size_t)desc->ny, nY = S * (size_t)(h->N + 1) * ny;   // per trajectory
+  HIPCHK(hipSetDevice(h->device));
+  Staging st(h, me, dev);
+  double *Yd, *sdd;
+  st.scratch(ny * sizeof(double), &sdd);
+  st.out("Yn", Yn, B * nY * sizeof(double), &Yd);
+  { int rc = st.begin(); if (rc) return rc; }
+  HIPCHK(hipMemcpy(sdd, sd, ny * sizeof(double), hipMemcpyHostToDevice));
+  { int rc = fork_from_user(h); if (rc) return rc; }
+  for (size_t gi = 0; gi < h->g.size(); ++gi) {
+    const Inner *q = h->g[gi];
+    const size_t b0 = (size_t)h->b0[gi];
+    a.b0 = (int)b0;
+    HIPCHK(mcof_noise_launch(a, q->d.B, h->N, h->nx, h->nu, desc->ny, sdd, Yd + b0 * nY, q->stream));
+  }
+  return st.finish();
+}
+
+int cddp_hip_plan_montecarlo_of(cddp_hip_handle *h, cddp_hip_plant *plant, int flags, const cddp_hip_mcof_desc *desc, const double *x0, const double *L,
+                                double *cost, double *viol, double *stats, int32_t *nviol_step, double *dXmean, double *SX, double *dUmean, double *SU,
+                                double *X_out, double *U_out, double *dEmean, double *SE, double *Xh_out) {
+  static const char *const me = "cddp_hip_plan_montecarlo_of";
+  McArgs a;
+  McFactors f;
+  double sd[CDDP_HIP_KF_MAX_NY];
+  { int rc = mc_refuse(me, h, flags, CDDP_HIP_MC_DEVICE | CDDP_HIP_MC_DIAG, desc ? &desc->mc : nullptr, &a, &f); if (rc) return rc; }
+  { int rc = mcof_refuse(me, desc, h->nx, true, sd); if (rc) return rc; }
+  if (!L) return fail(-1, "%s: null L pointer", me);
+  if (!cost && !viol && !stats && !nviol_step && !dXmean && !SX && !dUmean && !SU && !X_out && !U_out && !dEmean && !SE && !Xh_out)
+    return fail(-1, "%s: every output is NULL: there is nothing to write", me);
+  { int rc = sens_refuse_handle(me, h); if (rc) return rc; }   // MSIPDDP, never swept: A_t and B_t are read
+  { int rc = plan_tracked(me, h); if (rc) return rc; }
+  if (plant) { int rc = plant_fits(me, h, plant); if (rc) return rc; }
+  const bool dev = (flags & CDDP_HIP_MC_DEVICE) != 0, diag = (flags & CDDP_HIP_MC_DIAG) != 0;
+  a.diag = diag ? 1 : 0;
+  const size_t B = (size_t)h->B, S = (size_t)desc->mc.nsamp, nx = (size_t)h->nx, nu = (size_t)h->nu, N = (size_t)h->N, ny = (size_t)desc->ny;
+  const size_t nL = (N + 1) * nx * ny;
+  if (!dev && !ref_all_finite(L, B * nL)) return fail(-2, "%s: L holds a non-finite value", me);
+  // doubles per trajectory of every double output, in the order of the argument list
+  const size_t nSX = (N + 1) * nx * (diag ? 1 : nx), nSU = N * nu * (diag ? 1 : nu), nXo = S * (N + 1) * nx, nUo = S * N * nu, nCnt = N + 1;
+  constexpr int NO = 12;
+  double *outs[NO] = {cost, viol, stats, dXmean, SX, dUmean, SU, X_out, U_out, dEmean, SE, Xh_out};
+  const size_t per[NO] = {S, S, 8, (N + 1) * nx, nSX, N * nu, nSU, nXo, nUo, (N + 1) * nx, nSX, nXo};
+  static const char *const names[NO] = {"cost", "viol", "stats", "dXmean", "SX", "dUmean", "SU", "X_out", "U_out", "dEmean", "SE", "Xh_out"};
+  HIPCHK(hipSetDevice(h->device));
+  Staging st(h, me, dev);
+  const double *x0d, *Ld;
+  double *od[NO], *Cd, *sdd;
+  int32_t *cntd;
+  st.scratch(ny * nx * sizeof(double), &Cd);
+  st.scratch(ny * sizeof(double), &sdd);
+  st.in("x0", x0, B * nx * sizeof(double), &x0d);
+  st.in("L", L, B * nL * sizeof(double), &Ld);
+  for (int i = 0; i < NO; ++i) st.out(names[i], outs[i], B * per[i] * sizeof(double), &od[i]);
+  st.out("nviol_step", nviol_step, B * nCnt * sizeof(int32_t), &cntd);
+  { int rc = st.begin(); if (rc) return rc; }
+  HIPCHK(hipMemcpy(Cd, desc->C, ny * nx * sizeof(double), hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(sdd, sd, ny * sizeof(double), hipMemcpyHostToDevice));
+  { int rc = fork_from_user(h); if (rc) return rc; }
+  for (size_t gi = 0; gi < h->g.size(); ++gi) {
+    const Inner *q = h->g[gi];
+    const size_t b0 = (size_t)h->b0[gi];
+    const PlantDev pd = plant ? plant->pd : own_model_plant(q);
+    a.b0 = (int)b0;
+    a.x0 = x0d ? x0d + b0 * nx : nullptr;
+    double *go[NO];
+    for (int i = 0; i < NO; ++i) go[i] = od[i] ? od[i] + b0 * per[i] : nullptr;
+    a.cost = go[0]; a.viol = go[1]; a.stats = go[2]; a.dXmean = go[3]; a.SX = go[4]; a.dUmean = go[5]; a.SU = go[6]; a.X_out = go[7]; a.U_out = go[8];
+    a.nviol_step = cntd ? cntd + b0 * nCnt : nullptr;
+    McofArgs o;
+    o.ny = desc->ny; o.t4 = q->route.t4 ? 1 : 0;   // (sens_stacks: the layout of A / Bm)
+    o.C = Cd; o.sd = sdd; o.L = Ld + b0 * nL;
+    o.dEmean = go[9]; o.SE = go[10]; o.Xh_out = go[11];
+    { int rc = plant_launch_rc(mcof_launch(pd, q->d, a, f, o, q->stream), me, "sampling", pd); if (rc) return rc; }
   }
   return st.finish();
 }

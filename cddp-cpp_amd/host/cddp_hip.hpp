@@ -1001,6 +1001,26 @@ class HipBatchSolver : public ISolverAlgorithm {
     if (!h_) throw std::runtime_error("cddp_hip: planMonteCarlo needs a resident batch (the plug-in route has no resident handle)");
     check(cddp_hip_plan_montecarlo(h_, plant ? plant->get() : nullptr, flags, &desc, x0, cost, viol, stats, nviol_step, dXmean, SX, dUmean, SU, X_out, U_out));
   }
+  // NEW: the same under output feedback (include/cddp_hip.h "Monte-Carlo evaluation of a solved plan under output feedback"): every sample
+  // carries the estimate of a linearised Kalman filter with the gains L (planKalman's L_out, or any) for the sensors desc.C [ny][nx],
+  // desc.v [ny] (host arrays), and the feedback acts on the estimate.  desc.mc is planMonteCarlo's descriptor; L and x0 follow the pointer
+  // flag.  mcSampleMeasNoise writes the measurement noise.  Outputs as planMonteCarlo's, then the moments of the estimation error and the
+  // estimates themselves.  Any output nullptr, not all.
+  void mcSampleMeasNoise(int flags, const cddp_hip_mcof_desc &desc, double *Yn /* batch*nsamp*(N+1)*ny */) {
+    if (!h_) throw std::runtime_error("cddp_hip: mcSampleMeasNoise needs a resident batch (the plug-in route has no resident handle)");
+    check(cddp_hip_mc_sample_meas_noise(h_, flags, &desc, Yn));
+  }
+  void planMonteCarloOf(Plant *plant, int flags, const cddp_hip_mcof_desc &desc, const double *x0 /* batch*nx | nullptr */,
+                        const double *L /* batch*(N+1)*nx*ny */, double *cost /* batch*nsamp */, double *viol /* batch*nsamp */,
+                        double *stats /* batch*8 */, int32_t *nviol_step = nullptr /* batch*(N+1) */, double *dXmean = nullptr /* batch*(N+1)*nx */,
+                        double *SX = nullptr /* batch*(N+1)*nx*nx (DIAG: batch*(N+1)*nx) */, double *dUmean = nullptr /* batch*N*nu */,
+                        double *SU = nullptr /* batch*N*nu*nu (DIAG: batch*N*nu) */, double *X_out = nullptr /* batch*nsamp*(N+1)*nx */,
+                        double *U_out = nullptr /* batch*nsamp*N*nu */, double *dEmean = nullptr /* batch*(N+1)*nx */,
+                        double *SE = nullptr /* as SX */, double *Xh_out = nullptr /* batch*nsamp*(N+1)*nx */) {
+    if (!h_) throw std::runtime_error("cddp_hip: planMonteCarloOf needs a resident batch (the plug-in route has no resident handle)");
+    check(cddp_hip_plan_montecarlo_of(h_, plant ? plant->get() : nullptr, flags, &desc, x0, L, cost, viol, stats, nviol_step, dXmean, SX, dUmean, SU, X_out,
+                                      U_out, dEmean, SE, Xh_out));
+  }
   // NEW: solve the resident batch again from the seed it holds now (setInitialDevice, mpcAdvance) -- solveBatch() without creating and uploading
   std::vector<CDDPSolution> resolveBatch(CDDP &ctx) {
     if (!h_) throw std::runtime_error("cddp_hip: resolveBatch needs a resident batch (the plug-in route has no resident handle)");

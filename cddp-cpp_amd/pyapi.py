@@ -185,6 +185,8 @@ MC_DEVICE, MC_DIAG = 1, 2
 MC_MAX_SAMPLES = 1024
 MC_STATS = ("n_finite", "n_viol", "cost_mean", "cost_var", "cost_min", "cost_max", "viol_mean", "viol_max")
 MC_OUTPUTS = ("cost", "viol", "stats", "nviol_step", "dXmean", "SX", "dUmean", "SU", "X", "U")
+# cddp_hip_mc_sample_meas_noise / cddp_hip_plan_montecarlo_of (include/cddp_hip.h, "Monte-Carlo evaluation of a solved plan under output feedback")
+MCOF_OUTPUTS = MC_OUTPUTS + ("dEmean", "SE", "Xh")
 # cddp_hip_get_field_device / cddp_hip_field_shape (include/cddp_hip.h, "device-resident inputs and outputs"): enum cddp_hip_field
 FIELD_NAMES = ("X", "U", "K", "KFF", "VX", "VXX", "A", "B", "S", "Y", "G", "LAMBDA")
 FIELD_IDS = {name: i for i, name in enumerate(FIELD_NAMES)}
@@ -228,6 +230,10 @@ class McDesc(C.Structure):   # cddp_hip_mc_desc
         ("seed", C.c_uint64), ("stream", C.c_uint32), ("nsamp", C.c_int32), ("keep_nominal", C.c_int32), ("_pad", C.c_int32),
         ("viol_tol", C.c_double), ("L0", _dp), ("Lw", _dp), ("Lu", _dp),
     ]
+
+
+class McofDesc(C.Structure):   # cddp_hip_mcof_desc
+    _fields_ = [("mc", McDesc), ("ny", C.c_int32), ("_pad", C.c_int32), ("C", _dp), ("v", _dp)]
 
 
 class Stats(C.Structure):
@@ -877,6 +883,8 @@ DEVICE_IO_ARGTYPES = {
     "cddp_hip_mppi_refine": [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
     "cddp_hip_mc_sample_noise": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
     "cddp_hip_plan_montecarlo": [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p] + [C.c_void_p] * 11,
+    "cddp_hip_mc_sample_meas_noise": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p],
+    "cddp_hip_plan_montecarlo_of": [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p] + [C.c_void_p] * 15,
     "cddp_hip_set_reference": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p],
     "cddp_hip_get_reference": [C.c_void_p, _dp, _dp, C.POINTER(C.c_int32)],
     "cddp_hip_mpc_set_reference_path": [C.c_void_p, C.POINTER(RefPathDesc)],
@@ -900,7 +908,7 @@ EXPORTED_SYMBOLS = [
     "cddp_hip_plan_jvp", "cddp_hip_plan_vjp", "cddp_hip_plan_covariance", "cddp_hip_plan_tvlqr", "cddp_hip_plan_kalman",
     "cddp_hip_score_rollouts", "cddp_hip_seed_best",
     "cddp_hip_sample_controls", "cddp_hip_mppi_blend", "cddp_hip_mppi_refine",
-    "cddp_hip_mc_sample_noise", "cddp_hip_plan_montecarlo",
+    "cddp_hip_mc_sample_noise", "cddp_hip_plan_montecarlo", "cddp_hip_mc_sample_meas_noise", "cddp_hip_plan_montecarlo_of",
     "cddp_hip_set_reference", "cddp_hip_get_reference", "cddp_hip_mpc_set_reference_path", "cddp_hip_mpc_reference_cursor",
 ]
 
@@ -1891,6 +1899,90 @@ class HipBatchSolver:
         flags = (MC_DEVICE if dev else 0) | (MC_DIAG if diag else 0)
         self._check(self.lib.cddp_hip_plan_montecarlo(self.h, plant.h if plant is not None else None, flags, C.addressof(d), self._addr(x0),
                                                       *[self._addr(out.get(k)) for k in MC_OUTPUTS]))
+        return out
+
+    # ---- Monte-Carlo evaluation under output feedback (cddp_hip_mc_sample_meas_noise / cddp_hip_plan_montecarlo_of): plan_montecarlo's
+    # conventions; C and v are small host arrays as the factors are, the gains L follow the pointer kind of the call
+    def _mcof_desc(self, who, Cm, v, Sigma0, W, Wu, nsamp, need_C=True, **draw):
+        """-> (McofDesc, the arrays it points into): _mc_desc's descriptor with the sensor model C (ny, nx), v (ny,) behind it."""
+        mc, keep = self._mc_desc(who, Sigma0, W, Wu, nsamp, **draw)
+        host = lambda a: a.detach().cpu().numpy() if hasattr(a, "data_ptr") and not isinstance(a, np.ndarray) else a
+        if v is None or (need_C and Cm is None):
+            raise ValueError("%s: C and v must be given" % who)
+        v = np.ascontiguousarray(host(v), dtype=np.float64)
+        if v.ndim != 1 or not 1 <= v.shape[0] <= KF_MAX_NY:
+            raise ValueError("%s: v: 1 .. %d measurement rows are expected, got shape %s" % (who, KF_MAX_NY, v.shape))
+        if not (np.isfinite(v).all() and (v > 0).all()):
+            raise ValueError("%s: v: finite variances > 0 are expected" % who)
+        d = McofDesc()
+        d.mc = mc
+        d.ny = int(v.shape[0])
+        d.v = _ptr(v)
+        keep.append(v)
+        if Cm is not None:
+            Cm = np.ascontiguousarray(host(Cm), dtype=np.float64)
+            if Cm.shape != (d.ny, self.p.nx) or not np.isfinite(Cm).all():
+                raise ValueError("%s: C: a finite matrix of shape %s is expected, got shape %s" % (who, (d.ny, self.p.nx), Cm.shape))
+            d.C = _ptr(Cm)
+            keep.append(Cm)
+        return d, keep
+
+    def mc_sample_meas_noise(self, v, nsamp=1, device=False, **draw):
+        """The measurement noise plan_montecarlo_of draws (cddp_hip_mc_sample_meas_noise): (B, S, N + 1, ny), sqrt(v[r]) * z with z the
+        standard normal of element nx + N (nu + nx) + t ny + r of plan_montecarlo's generator.  draw: seed, stream, keep_nominal.  A numpy
+        array, or a device tensor with device=True."""
+        who = "mc_sample_meas_noise"
+        d, keep = self._mcof_desc(who, None, v, None, None, None, nsamp, need_C=False, **draw)
+        out = self._mppi_out((self.B, d.mc.nsamp, self.p.N + 1, d.ny), device)
+        if device:
+            self._order_device_io()
+        self._check(self.lib.cddp_hip_mc_sample_meas_noise(self.h, MC_DEVICE if device else 0, C.addressof(d), self._addr(out)))
+        return out
+
+    def plan_montecarlo_of(self, C_, v, L, Sigma0=None, W=None, Wu=None, nsamp=64, seed=0, stream=0, keep_nominal=False, plant=None, x0=None,
+                           viol_tol=0.0, diag=False, factors=False, want=("stats", "nviol_step", "dXmean", "SX", "dUmean", "SU", "dEmean", "SE"),
+                           device=None):
+        """plan_montecarlo with the controller seeing only y_t = C dx_t + n_t, cov(n_t) = diag(v) (cddp_hip_plan_montecarlo_of): every
+        sample carries the estimate xh of x - X_t of a linearised Kalman filter with the gains L (B, N + 1, nx, ny) -- plan_kalman's "L", or
+        any gains -- updated by the measurement at every step, fed back as u_t = clip(U_t + Lu z + K_t xh) and predicted with A_t, B_t of
+        the handle's stacks.  C_ (ny, nx) and v (ny,) are small host arrays (tensors are copied to the host); Sigma0, W, Wu, nsamp, seed,
+        stream, keep_nominal, plant, x0, viol_tol, diag, factors as in plan_montecarlo, and the initial, actuator and process noise of a
+        sample are plan_montecarlo's at the same (seed, stream).  L and x0: numpy arrays, or torch.float64 tensors on the handle's device
+        (device tensors back), never mixed.  want: any of MCOF_OUTPUTS -- plan_montecarlo's, "dEmean" (B, N + 1, nx) and "SE" (B, N + 1, nx,
+        nx; diag=True: (B, N + 1, nx)), sample mean and covariance of the estimation error (x - X_t) - xh after the measurement of step t,
+        and "Xh" (B, S, N + 1, nx), the estimates.  The handle's state is not modified."""
+        who = "plan_montecarlo_of"
+        want = tuple(want)
+        if not want or any(w not in MCOF_OUTPUTS for w in want):
+            raise ValueError("%s: want: a non-empty subset of %r is expected, got %r" % (who, MCOF_OUTPUTS, want))
+        if L is None:
+            raise ValueError("%s: the filter gains L must be given" % who)
+        B, N, nx, nu = self.B, self.p.N, self.p.nx, self.p.nu
+        d, keep = self._mcof_desc(who, C_, v, Sigma0, W, Wu, nsamp, seed=seed, stream=stream, keep_nominal=keep_nominal, viol_tol=viol_tol, factors=factors)
+        S, ny = d.mc.nsamp, d.ny
+        dev = self._is_device(L, x0) if device is None else bool(device)
+        L = self._score_arg(who, "L", L, [(B, N + 1, nx, ny)], dev)
+        if x0 is not None:
+            x0 = self._score_arg(who, "x0", x0, [(B, nx)], dev)
+        sx = (B, N + 1, nx) if diag else (B, N + 1, nx, nx)
+        shapes = {"cost": (B, S), "viol": (B, S), "stats": (B, 8), "nviol_step": (B, N + 1), "dXmean": (B, N + 1, nx), "SX": sx,
+                  "dUmean": (B, N, nu), "SU": (B, N, nu) if diag else (B, N, nu, nu), "X": (B, S, N + 1, nx), "U": (B, S, N, nu),
+                  "dEmean": (B, N + 1, nx), "SE": sx, "Xh": (B, S, N + 1, nx)}
+        out = {}
+        for k in want:
+            if k == "nviol_step":
+                if dev:
+                    import torch
+                    out[k] = torch.empty(shapes[k], dtype=torch.int32, device=self._torch_device())
+                else:
+                    out[k] = np.zeros(shapes[k], dtype=np.int32)
+            else:
+                out[k] = self._mppi_out(shapes[k], dev)
+        if dev:
+            self._order_device_io()
+        flags = (MC_DEVICE if dev else 0) | (MC_DIAG if diag else 0)
+        self._check(self.lib.cddp_hip_plan_montecarlo_of(self.h, plant.h if plant is not None else None, flags, C.addressof(d), self._addr(x0),
+                                                         self._addr(L), *[self._addr(out.get(k)) for k in MCOF_OUTPUTS]))
         return out
 
 

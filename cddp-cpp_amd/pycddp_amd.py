@@ -1389,6 +1389,71 @@ class CDDP:                         # cddp_core.hpp:214-423 / bind_solver.cpp:57
         out["mc"] = mc
         return out
 
+    def solve_batch_lqg_mc(self, x0s, C, v, Sigma0, W=None, Wu=None, Q_track=None, R_track=None, Qf_track=None, nsamp=64, seed=0, stream=0,
+                           keep_nominal=False, viol_tol=0.0, diag=False, U0=None, X0=None, solver_type=SolverType.IPDDP,
+                           kf_want=("L", "SF", "SX", "SU", "dcost", "info"),
+                           mc_want=("stats", "nviol_step", "dXmean", "SX", "dUmean", "SU", "dEmean", "SE"), want=("X", "U")):
+        """NEW (no reference counterpart): solve_batch_lqg, then the Monte-Carlo evaluation of that design on the nonlinear model with the
+        estimator in the loop (cddp_hip_plan_montecarlo_of), on the same handle: nsamp noisy closed loops per trajectory in which the
+        controller sees only y_t = C dx_t + n_t and feeds back the estimate of a linearised Kalman filter with the gains plan_kalman
+        returned -- they stay on the device.  C (ny, nx), v (ny,), Sigma0, W (nx, nx), Wu (nu, nu): one each for the batch (the evaluation
+        takes no per-trajectory sensors), torch.float64, contiguous, on cuda:0; Sigma0, W and Wu must be positive definite (they are
+        factored on the host for the draws).  Returns what solve_batch_lqg returns ("L" is always among the entries of "kalman"), plus
+        "mc": the dict of HipBatchSolver.plan_montecarlo_of for mc_want, as device tensors.  "mc"["SE"] against "kalman"["SF"] is the
+        filter's consistency on the true plant."""
+        import torch
+        api = _api()
+        name = solver_type.value if isinstance(solver_type, SolverType) else str(solver_type)
+        want = tuple(want)
+        unknown = [w for w in want if w not in api.FIELD_IDS]
+        if unknown:
+            raise ValueError("want: unknown fields %s (known: %s)" % (unknown, ", ".join(api.FIELD_NAMES)))
+        if self._sys is None:
+            raise RuntimeError("Dynamical system must be set before solving.")
+        kind = self._resident_kind(name)
+        if kind is None:
+            raise NotImplementedError("solve_batch_lqg_mc needs a problem of the resident route (built-in plant, objective and constraints): "
+                                      "solver '%s' with this problem runs on the plug-in route, which has no resident handle" % name)
+        if not isinstance(x0s, torch.Tensor) or x0s.dim() != 2:
+            raise ValueError("x0s: a (B, nx) torch tensor is expected")
+        for nm, w in (("C", C), ("v", v), ("Sigma0", Sigma0)):
+            if not isinstance(w, torch.Tensor):
+                raise ValueError("%s: a torch tensor is expected" % nm)
+        if C.dim() != 2:
+            raise ValueError("C: a (ny, nx) tensor is expected: the evaluation takes one sensor model for the batch")
+        for nm, w in (("W", W), ("Wu", Wu), ("Q_track", Q_track), ("R_track", R_track), ("Qf_track", Qf_track)):
+            if w is not None and not isinstance(w, torch.Tensor):
+                raise ValueError("%s: a torch tensor or None is expected" % nm)
+        B = int(x0s.shape[0])
+        if B <= 0:
+            raise ValueError("x0s: an empty batch")
+        if U0 is None and self._U is not None and x0s.is_cuda:     # (the seed of set_initial_trajectory, as solve_batch_device takes it)
+            U0 = torch.as_tensor(np.ascontiguousarray(self._U, dtype=np.float64), device=x0s.device).expand(B, -1, -1).contiguous()
+        if X0 is None and self._X is not None and x0s.is_cuda:
+            X0 = torch.as_tensor(np.ascontiguousarray(self._X, dtype=np.float64), device=x0s.device).expand(B, -1, -1).contiguous()
+        track = any(w is not None for w in (Q_track, R_track, Qf_track))
+        kf_want = tuple(kf_want) if "L" in kf_want else ("L",) + tuple(kf_want)
+        p = self._problem(kind)
+        hs = api.HipBatchSolver(p, B)
+        try:
+            hs.set_initial_device(x0s, U0, X0)        # (shape, dtype, contiguity and device are checked there: ValueError)
+            st = hs.solve()
+            lqr = hs.plan_tvlqr(Q_track, R_track, Qf_track, install=True, device=True) if track else None
+            kf = hs.plan_kalman(C, v, Sigma0, W, Wu, diag=diag, want=kf_want)
+            mc = hs.plan_montecarlo_of(C, v, kf["L"], Sigma0, W, Wu, nsamp=nsamp, seed=seed, stream=stream, keep_nominal=keep_nominal,
+                                       viol_tol=viol_tol, diag=diag, want=mc_want, device=True)
+            out = {w: hs.field_device(w) for w in want}
+            res = hs.results_device()
+        finally:
+            hs.close()
+        out["results"] = {k: v_ for k, v_ in res.items() if k not in ("cols", "icols")}
+        out["solve_time_ms"] = float(st.solve_ms)
+        out["kalman"] = kf
+        out["mc"] = mc
+        if lqr is not None:
+            out["K_lqr"] = lqr["K"]; out["P_lqr"] = lqr["P"]; out["lqr_info"] = lqr["info"]
+        return out
+
     def solve_batch_sampled(self, x0s, U_candidates, solver_type=SolverType.IPDDP, viol_tol=0.0, want=("X", "U")):
         """NEW (no reference counterpart): solve_batch_device started from the best of S candidate control sequences per trajectory
         (cddp_hip_score_rollouts, cddp_hip_seed_best): every candidate is rolled out on the device in one launch, the admissible one

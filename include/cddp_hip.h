@@ -874,8 +874,9 @@ int cddp_hip_plan_tvlqr(cddp_hip_handle *h, int flags,
  * Failure of one trajectory: the walk goes forward; the first failed row, at step t, gives info[b] = t + 1, every output row s >= t of
  * that trajectory is NaN (rows before it are those computed) and its dcost is NaN.  Otherwise info[b] = 0.  Other trajectories are
  * unaffected.  Non-finite stack rows end in a failed row (NaN > 0 is false).  (The sign of an exact zero is not specified.)
- * Not covered: correlated measurement noise, time-varying C, v or W, intermittent measurements, an estimator inside cddp_hip_track_plan,
- * cddp_hip_plan_montecarlo or the MPC loop, and the relinearisation of an extended Kalman filter.
+ * Not covered: correlated measurement noise, time-varying C, v or W, intermittent measurements, an estimator inside cddp_hip_track_plan
+ * or the MPC loop (cddp_hip_plan_montecarlo_of below carries one through the Monte-Carlo evaluation), and the relinearisation of an
+ * extended Kalman filter.
  * Refused before anything is launched, each with its own message, nothing changed: a NULL handle, unknown flag bits, ny outside
  * 1 .. CDDP_HIP_KF_MAX_NY, a NULL C, v or Sigma0, all six outputs and info NULL, a handle that was never solved or swept, an MSIPDDP
  * handle, a host v with an entry that is not finite or not > 0, a non-finite value in any other host input, and with CDDP_HIP_KF_DEVICE a
@@ -1061,6 +1062,63 @@ int cddp_hip_plan_montecarlo(cddp_hip_handle *h, cddp_hip_plant *plant /* or NUL
                              double *SX /* [B][N+1][nx][nx] | DIAG [B][N+1][nx] */, double *dUmean /* [B][N][nu] */,
                              double *SU /* [B][N][nu][nu] | DIAG [B][N][nu] */, double *X_out /* [B][S][N+1][nx] */,
                              double *U_out /* [B][S][N][nu] */);   /* any output may be NULL, not all */
+
+/* ---- Monte-Carlo evaluation of a solved plan under output feedback ------------------------
+ * The nonlinear check of an LQG design made with cddp_hip_plan_tvlqr and cddp_hip_plan_kalman: does it hold on the true plant with the
+ * actuator box, is the filter consistent there (is the sample covariance of the estimation error Sf_t), how often is a constraint row
+ * violated when the controller sees only y_t?  cddp_hip_plan_montecarlo_of is cddp_hip_plan_montecarlo with a linearised Kalman estimator
+ * carried in every lane (csrc/inst_mcof.hip: the same workgroup per trajectory and lane per sample): the feedback acts on the estimate, the
+ * moments of the estimation error are reduced with the state's.  cddp_hip_mc_sample_meas_noise writes the measurement noise itself.
+ * csrc/plan_mcof.hpp is the normative statement of what is new (host and device compile it), restated here; everything else is the section
+ * above, line for line.  -ffp-contract=off, every sum starts at the stated value and runs with the index ascending, true division.
+ * Sensors: y_t = C dx_t + n_t at every step t = 0 .. N before u_t is applied, cov(n_t) = diag(v): C [ny][nx] and v [ny] are row-major HOST
+ *  arrays, one each for the batch, 1 <= ny <= CDDP_HIP_KF_MAX_NY.  sd[r] = sqrt(v[r]), correctly rounded, is formed on the host.
+ * Gains: L [b][t][i][r], t = 0 .. N: cddp_hip_plan_kalman's L_out, or any gains; a host array, or a device array with CDDP_HIP_MC_DEVICE (it
+ *  follows the pointer flag, as x0 does).  K_t, A_t, B_t are the handle's stacks at the time of the call (see cddp_hip_plan_kalman, WHICH SWEEP).
+ * Normals: the measurement normal of step t, row r is element e = nx + N (nu + nx) + t ny + r of the same (seed, stream, b, c) as above: past
+ *  the end of the elements of cddp_hip_plan_montecarlo, so the initial, actuator and process noise of a sample are bit for bit those of
+ *  that entry (common random numbers between state and output feedback).  keep_nominal zeroes the measurement noise of sample 0 too.
+ * Rollout of sample c: as above, with xh[nx], the estimate of x - X_t, next to x; xh = 0 at the start.  At every step t = 0 .. N:
+ *  1. dx[j] = x[j] - X_t[j] (the value whose moments go to dXmean and SX).
+ *  2. y[r] = s + n[r], with s = 0; for j ascending s += C[r][j] * dx[j], and n[r] = sd[r] * z.
+ *  3. inn[r] = y[r] - p, with p = 0; for j ascending p += C[r][j] * xh[j]: every inn from the xh held before step 4 changes any of it.
+ *  4. xh[i] = xh[i] + s, with s = 0; for r ascending s += L_t[i][r] * inn[r].
+ *  5. e[i] = dx[i] - xh[i]: dEmean and SE by the tree sum and the moment formulas above; row t of Xh_out is xh.
+ *  6. For t < N: fb[i] = s, s = 0; for j ascending s += K_t[i][j] * xh[j]; u[i] = (U_t[i] + eps[i]) + fb[i] (the line above with xh in the
+ *     place of x - X_t); the plant's box, the cost, the path rows, the step(s) and the process noise exactly as above; the prediction
+ *     xp[i] = s, s = 0; for j ascending s += A_t[i][j] * xh[j], then for j ascending s += B_t[i][j] * fb[j]; xh = xp.
+ *     The estimator predicts with the unclipped, noise-free fb: the model of cddp_hip_plan_kalman.
+ * Outputs: every output of cddp_hip_plan_montecarlo with the same shape and meaning, then dEmean [b][t][i], SE [b][t][i][j] (with
+ *  CDDP_HIP_MC_DIAG [b][t][i]) and Xh_out [b][c][t][i], t = 0 .. N.  Any may be NULL, not all.  The handle's state is not modified.
+ * Stream ordering: C and sd = sqrt(v) are uploaded into the handle's staging scratch by the call itself, so, unlike cddp_hip_plan_montecarlo,
+ *  a CDDP_HIP_MC_DEVICE call is not fully asynchronous on the stream of cddp_hip_set_stream: it copies the two small arrays synchronously,
+ *  and when the previous user of the scratch may still be running there (such as the call before it) it first waits for the group
+ *  streams on the host.  The outputs are ordered on the stream as those of cddp_hip_plan_montecarlo are.
+ * Not covered: nonlinear (EKF) or saturation-aware prediction, time-varying C or v, correlated measurement noise, intermittent
+ *  measurements, C or factors per trajectory, an estimator inside cddp_hip_track_plan or the MPC loop, NEES or quantiles on the device
+ *  (X_out and Xh_out are returned for them).
+ * Refused before anything is launched, each with its own message: everything cddp_hip_plan_montecarlo refuses; ny outside
+ * 1 .. CDDP_HIP_KF_MAX_NY; a NULL L, C or v; a v entry that is not finite or not > 0; a non-finite C; a non-finite host L; a handle that was
+ * never solved or swept or keeps no A / B / K stacks, and an MSIPDDP handle (A_t and B_t are read); with CDDP_HIP_MC_DEVICE an L
+ * cddp_hip_get_field_device would refuse.  (New entry points; ABI version unchanged.) */
+typedef struct cddp_hip_mcof_desc {
+  cddp_hip_mc_desc mc;                 /* seed, stream, nsamp, keep_nominal, viol_tol, L0, Lw, Lu: exactly as cddp_hip_plan_montecarlo reads them */
+  int32_t ny;                          /* 1 .. CDDP_HIP_KF_MAX_NY */
+  int32_t _pad;
+  const double *C;                     /* host, [ny][nx], one for the batch */
+  const double *v;                     /* host, [ny] measurement variances, finite and > 0 */
+} cddp_hip_mcof_desc;                  /* 80 bytes */
+int cddp_hip_mc_sample_meas_noise(cddp_hip_handle *h, int flags, const cddp_hip_mcof_desc *desc, double *Yn /* [B][S][N+1][ny]; C is not read */);
+int cddp_hip_plan_montecarlo_of(cddp_hip_handle *h, cddp_hip_plant *plant /* or NULL */, int flags, const cddp_hip_mcof_desc *desc,
+                                const double *x0 /* [B][nx] or NULL = row 0 of the live plan */,
+                                const double *L /* [B][N+1][nx][ny] */,
+                                double *cost /* [B][S] */, double *viol /* [B][S] */, double *stats /* [B][8] */,
+                                int32_t *nviol_step /* [B][N+1] */, double *dXmean /* [B][N+1][nx] */,
+                                double *SX /* [B][N+1][nx][nx] | DIAG [B][N+1][nx] */, double *dUmean /* [B][N][nu] */,
+                                double *SU /* [B][N][nu][nu] | DIAG [B][N][nu] */, double *X_out /* [B][S][N+1][nx] */,
+                                double *U_out /* [B][S][N][nu] */, double *dEmean /* [B][N+1][nx] */,
+                                double *SE /* [B][N+1][nx][nx] | DIAG [B][N+1][nx] */,
+                                double *Xh_out /* [B][S][N+1][nx] */);   /* any output may be NULL, not all */
 
 /* ---- multi-GPU: the single collective of the path --------------------------------------
  * One process (or host thread) per GPU, each with its own handle over a contiguous block of the global batch; nothing
