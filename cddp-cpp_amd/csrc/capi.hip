@@ -25,6 +25,7 @@
 #include "mc_kernels.hpp"
 #include "mcof_kernels.hpp"
 #include "ref_kernels.hpp"
+#include "ekf_kernels.hpp"
 
 // 1 when a[0] > a[1] > ... > a[n - 1] (NaN-free): the ladders cddp_hip_build_alphas makes; DevBuf::ladder_sorted
 static int ladder_strictly_decreasing(const double *a, int n) {
@@ -2314,7 +2315,7 @@ static int io_field(const Inner *q, int field, IoField *f) {
 }
 
 // A caller's pointer may reach a kernel only as device memory of the handle's device whose allocation holds every byte the call touches.
-static int io_check_pointer(const cddp_hip_handle *h, const void *p, size_t bytes, const char *entry, const char *what) {
+static int io_check_pointer(int device, const char *owner, const void *p, size_t bytes, const char *entry, const char *what) {
   hipPointerAttribute_t at;
   std::memset(&at, 0, sizeof(at));
   const hipError_t e = hipPointerGetAttributes(&at, p);
@@ -2322,13 +2323,16 @@ static int io_check_pointer(const cddp_hip_handle *h, const void *p, size_t byte
   if (at.type != hipMemoryTypeDevice)
     return fail(-2, "%s: %s is not device memory (%s)", entry, what,
                 at.type == hipMemoryTypeHost ? "a pinned host address" : at.type == hipMemoryTypeUnregistered ? "a host address" : "managed or array memory");
-  if (at.device != h->device) return fail(-2, "%s: %s lives on device %d, the handle on device %d", entry, what, at.device, h->device);
+  if (at.device != device) return fail(-2, "%s: %s lives on device %d, the %s on device %d", entry, what, at.device, owner, device);
   hipDeviceptr_t base = nullptr; size_t size = 0;
   const hipError_t e2 = hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p);
   if (e2 != hipSuccess) { (void)hipGetLastError(); return fail(-2, "%s: the allocation of %s is unknown (%s)", entry, what, hipGetErrorString(e2)); }
   const size_t room = (size_t)((const char *)base + size - (const char *)p);
   if (bytes > room) return fail(-2, "%s: %s needs %zu bytes, its allocation ends after %zu", entry, what, bytes, room);
   return 0;
+}
+static int io_check_pointer(const cddp_hip_handle *h, const void *p, size_t bytes, const char *entry, const char *what) {
+  return io_check_pointer(h->device, "handle", p, bytes, entry, what);
 }
 
 // Ordering as cddp_hip_mpc_advance with a device x_next: on the stream of cddp_hip_set_stream the kernels are ordered between the caller's
@@ -3533,6 +3537,375 @@ int cddp_hip_plan_montecarlo_of(cddp_hip_handle *h, cddp_hip_plant *plant, int f
     { int rc = plant_launch_rc(mcof_launch(pd, q->d, a, f, o, q->stream), me, "sampling", pd); if (rc) return rc; }
   }
   return st.finish();
+}
+
+}  // extern "C" (reopened below)
+
+// ================================================================================================================
+// Device-resident extended Kalman filter (include/cddp_hip.h "extended Kalman filter on the device"; kernels: inst_ekf.hip, arithmetic:
+// ekf.hpp).  The object owns its sensor and noise matrices, its state (xh, P, info, the step count) and the buffers of its entries; the
+// plant it was created on is only read.  It is not tied to a handle, so its host forms are staged through a scratch of its own
+// (EkfStage: the declarations, checks and order of the handle's Staging) on its own stream.
+// ================================================================================================================
+struct cddp_hip_ekf {
+  cddp_hip_plant *plant = nullptr;
+  EkfDev e;
+  int nx = 0, nu = 0, B = 0, device = 0, t = 0;
+  hipStream_t stream = nullptr;
+  double *d_mats = nullptr;          // C | v | W | Wu
+  double *d_state = nullptr;         // xh | P
+  int32_t *d_info = nullptr;
+  char *d_io = nullptr; size_t io_cap = 0;
+  // cddp_hip_mpc_run_ekf: the true state, y, the commanded u_0, nis of the step (B each); W [steps][B][nx] | Yn [steps][B][ny]; the logs
+  double *d_loop = nullptr;
+  double *d_noise = nullptr; size_t noise_cap = 0;
+  double *d_log = nullptr; size_t log_cap = 0;
+};
+
+namespace {
+
+int ekf_free(cddp_hip_ekf *k) {
+  hipSetDevice(k->device);
+  if (k->stream) { hipStreamSynchronize(k->stream); hipStreamDestroy(k->stream); }
+  void *bufs[] = {k->d_mats, k->d_state, k->d_info, k->d_io, k->d_loop, k->d_noise, k->d_log};
+  for (void *q : bufs) if (q) hipFree(q);
+  delete k;
+  return 0;
+}
+
+int ekf_grow(double **p, size_t *cap, size_t n) {
+  if (*cap >= n) return 0;
+  if (*p) hipFree(*p);
+  *p = nullptr; *cap = 0;
+  HIPCHK(hipMalloc((void **)p, n * sizeof(double)));
+  *cap = n;
+  return 0;
+}
+
+struct EkfStage {
+  struct Arr { const char *name; const void *caller; size_t bytes; void *slot; size_t off; int dir; };
+  cddp_hip_ekf *k; const char *me; bool dev;
+  std::vector<Arr> arr;
+  size_t total = 0;
+  EkfStage(cddp_hip_ekf *k_, const char *me_, bool dev_) : k(k_), me(me_), dev(dev_) {}
+  void add(const char *name, const void *caller, size_t bytes, void *slot, int dir) {
+    if (!caller) { Staging::put(slot, nullptr); return; }
+    if (dev) Staging::put(slot, caller);
+    arr.push_back(Arr{name, caller, bytes, slot, total, dir});
+    if (!dev) total += (bytes + 7) & ~(size_t)7;
+  }
+  template <class T> void in(const char *name, const T *p, size_t bytes, const T **slot) { add(name, p, bytes, slot, +1); }
+  template <class T> void out(const char *name, T *p, size_t bytes, T **slot) { add(name, p, bytes, slot, -1); }
+  int begin() {
+    if (dev) { for (const Arr &a : arr) { int rc = io_check_pointer(k->device, "estimator", a.caller, a.bytes, me, a.name); if (rc) return rc; } return 0; }
+    if (k->io_cap < total) {
+      if (k->d_io) hipFree(k->d_io);
+      k->d_io = nullptr; k->io_cap = 0;
+      HIPCHK(hipMalloc((void **)&k->d_io, total));
+      k->io_cap = total;
+    }
+    for (const Arr &a : arr) {
+      Staging::put(a.slot, k->d_io + a.off);
+      if (a.dir > 0) HIPCHK(hipMemcpy(k->d_io + a.off, a.caller, a.bytes, hipMemcpyHostToDevice));
+    }
+    return 0;
+  }
+  int finish() {
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(k->stream));
+    if (!dev) for (const Arr &a : arr) if (a.dir < 0) HIPCHK(hipMemcpy(const_cast<void *>(a.caller), k->d_io + a.off, a.bytes, hipMemcpyDeviceToHost));
+    return 0;
+  }
+};
+
+int ekf_flags(const char *me, const cddp_hip_ekf *k, int flags, int known) {
+  if (!k) return fail(-1, "%s: null estimator", me);
+  if (flags & ~known) return fail(-2, "%s: unknown flag bits 0x%x", me, (unsigned)(flags & ~known));
+  return 0;
+}
+
+// y with NaN allowed where the flag makes it a drop-out
+bool ekf_meas_finite(const double *y, size_t n, bool nan_ok) {
+  for (size_t i = 0; i < n; ++i)
+    if (!std::isfinite(y[i]) && !(nan_ok && y[i] != y[i])) return false;
+  return true;
+}
+
+int ekf_walk(cddp_hip_ekf *k, const char *me, const EkfWalk &w, hipStream_t s) {
+  const hipError_t e = ekf_launch_walk(k->plant->pd, k->e, w, s);
+  if (e == hipErrorInvalidValue) return fail(-3, "%s: the library has no filter kernel for model id %d with nx = %d, nu = %d", me, k->plant->pd.model, k->nx, k->nu);
+  HIPCHK(e);
+  return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int cddp_hip_ekf_create(cddp_hip_plant *model, const cddp_hip_ekf_desc *c, cddp_hip_ekf **out) {
+  static const char *const me = "cddp_hip_ekf_create";
+  if (!c || !out) return fail(-1, "%s: null argument", me);
+  if (c->abi_version != CDDP_HIP_ABI_VERSION) return fail(-2, "%s: ABI version mismatch: got %d want %d", me, c->abi_version, CDDP_HIP_ABI_VERSION);
+  if (c->ny < 1 || c->ny > CDDP_HIP_KF_MAX_NY) return fail(-2, "%s: ny = %d, 1 .. %d measurement rows are expected", me, c->ny, CDDP_HIP_KF_MAX_NY);
+  if (!c->C) return fail(-1, "%s: null C pointer", me);
+  if (!c->v) return fail(-1, "%s: null v pointer", me);
+  if (!model) return fail(-1, "%s: null model plant", me);   // (what precedes needs no plant, and so no device at all; what follows reads its dimensions)
+  const size_t nx = (size_t)model->pd.nx, nu = (size_t)model->pd.nu, B = (size_t)model->B, m = (size_t)c->ny, lead = c->per_trajectory ? B : 1;
+  for (size_t i = 0; i < lead * m; ++i)
+    if (!std::isfinite(c->v[i]) || !(c->v[i] > 0.0)) return fail(-2, "%s: v holds an entry that is not finite and > 0 (a measurement variance)", me);
+  if (!ref_all_finite(c->C, lead * m * nx)) return fail(-2, "%s: C holds a non-finite value", me);
+  if (c->W && !ref_all_finite(c->W, lead * nx * nx)) return fail(-2, "%s: W holds a non-finite value", me);
+  if (c->Wu && !ref_all_finite(c->Wu, lead * nu * nu)) return fail(-2, "%s: Wu holds a non-finite value", me);
+  if (model->pd.substeps > 1)
+    return fail(-2, "%s: the model plant takes %d substeps per control interval: the filter linearises one step of dt (the product of sub-step Jacobians is not available)", me, model->pd.substeps);
+  HIPCHK(hipSetDevice(model->device));
+  cddp_hip_ekf *k = new cddp_hip_ekf();
+  k->plant = model; k->nx = (int)nx; k->nu = (int)nu; k->B = (int)B; k->device = model->device;
+  const size_t nC = lead * m * nx, nv = lead * m, nW = c->W ? lead * nx * nx : 0, nWu = c->Wu ? lead * nu * nu : 0;
+  std::vector<double> mats(nC + nv + nW + nWu);
+  std::memcpy(mats.data(), c->C, nC * sizeof(double));
+  std::memcpy(mats.data() + nC, c->v, nv * sizeof(double));
+  if (nW) std::memcpy(mats.data() + nC + nv, c->W, nW * sizeof(double));
+  if (nWu) std::memcpy(mats.data() + nC + nv + nW, c->Wu, nWu * sizeof(double));
+  const size_t nS = B * nx + B * nx * nx;
+  hipError_t e = hipStreamCreateWithFlags(&k->stream, hipStreamNonBlocking);
+  if (e == hipSuccess) e = hipMalloc((void **)&k->d_mats, mats.size() * sizeof(double));
+  if (e == hipSuccess) e = hipMemcpy(k->d_mats, mats.data(), mats.size() * sizeof(double), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMalloc((void **)&k->d_state, nS * sizeof(double));
+  if (e == hipSuccess) e = hipMemset(k->d_state, 0, nS * sizeof(double));
+  if (e == hipSuccess) e = hipMalloc((void **)&k->d_info, B * sizeof(int32_t));
+  if (e == hipSuccess) e = hipMemset(k->d_info, 0, B * sizeof(int32_t));
+  if (e == hipSuccess) e = hipMalloc((void **)&k->d_loop, B * (nx + m + nu + 1) * sizeof(double));
+  if (e != hipSuccess) { ekf_free(k); return fail(-10, "%s: %s", me, hipGetErrorString(e)); }
+  EkfDev &d = k->e;
+  d.ny = c->ny; d.per_traj = c->per_trajectory ? 1 : 0;
+  d.C = k->d_mats; d.v = d.C + nC; d.W = nW ? d.v + nv : nullptr; d.Wu = nWu ? d.v + nv + nW : nullptr;
+  d.xh = k->d_state; d.P = d.xh + B * nx; d.info = k->d_info;
+  *out = k;
+  return 0;
+}
+
+int cddp_hip_ekf_destroy(cddp_hip_ekf *k) { return k ? ekf_free(k) : 0; }
+
+int cddp_hip_ekf_reset(cddp_hip_ekf *k, int flags, const double *xh0, const double *P0) {
+  static const char *const me = "cddp_hip_ekf_reset";
+  { int rc = ekf_flags(me, k, flags, CDDP_HIP_EKF_DEVICE | CDDP_HIP_EKF_PER_TRAJ); if (rc) return rc; }
+  if (!xh0) return fail(-1, "%s: null xh0 pointer", me);
+  if (!P0) return fail(-1, "%s: null P0 pointer", me);
+  const bool dev = (flags & CDDP_HIP_EKF_DEVICE) != 0, per = (flags & CDDP_HIP_EKF_PER_TRAJ) != 0;
+  const size_t nx = (size_t)k->nx, B = (size_t)k->B, nP = (per ? B : 1) * nx * nx;
+  if (!dev) {
+    if (!ref_all_finite(xh0, B * nx)) return fail(-2, "%s: xh0 holds a non-finite value", me);
+    if (!ref_all_finite(P0, nP)) return fail(-2, "%s: P0 holds a non-finite value", me);
+  }
+  HIPCHK(hipSetDevice(k->device));
+  EkfStage st(k, me, dev);
+  const double *xd, *Pd;
+  st.in("xh0", xh0, B * nx * sizeof(double), &xd);
+  st.in("P0", P0, nP * sizeof(double), &Pd);
+  { int rc = st.begin(); if (rc) return rc; }
+  HIPCHK(ekf_launch_reset(k->e, k->nx, k->B, xd, Pd, per ? 1 : 0, k->stream));
+  k->t = 0;
+  return st.finish();
+}
+
+int cddp_hip_ekf_update(cddp_hip_ekf *k, int flags, const double *y, double *nis) {
+  static const char *const me = "cddp_hip_ekf_update";
+  { int rc = ekf_flags(me, k, flags, CDDP_HIP_EKF_DEVICE | CDDP_HIP_EKF_SKIP_NAN); if (rc) return rc; }
+  if (!y) return fail(-1, "%s: null y pointer", me);
+  const bool dev = (flags & CDDP_HIP_EKF_DEVICE) != 0, skip = (flags & CDDP_HIP_EKF_SKIP_NAN) != 0;
+  const size_t B = (size_t)k->B, m = (size_t)k->e.ny;
+  if (!dev && !ekf_meas_finite(y, B * m, skip)) return fail(-2, "%s: y holds a non-finite value (a NaN is a missing measurement only with CDDP_HIP_EKF_SKIP_NAN)", me);
+  HIPCHK(hipSetDevice(k->device));
+  EkfStage st(k, me, dev);
+  EkfWalk w;
+  std::memset(&w, 0, sizeof(w));
+  st.in("y", y, B * m * sizeof(double), &w.Y);
+  st.out("nis", nis, B * sizeof(double), &w.nis_out);
+  { int rc = st.begin(); if (rc) return rc; }
+  w.B = k->B; w.t0 = k->t; w.upd0 = 1; w.skip_nan = skip ? 1 : 0;
+  { int rc = ekf_walk(k, me, w, k->stream); if (rc) return rc; }
+  return st.finish();
+}
+
+int cddp_hip_ekf_predict(cddp_hip_ekf *k, int flags, const double *u) {
+  static const char *const me = "cddp_hip_ekf_predict";
+  { int rc = ekf_flags(me, k, flags, CDDP_HIP_EKF_DEVICE); if (rc) return rc; }
+  if (!u) return fail(-1, "%s: null u pointer", me);
+  const bool dev = (flags & CDDP_HIP_EKF_DEVICE) != 0;
+  const size_t B = (size_t)k->B, nu = (size_t)k->nu;
+  if (!dev && !ref_all_finite(u, B * nu)) return fail(-2, "%s: u holds a non-finite value", me);
+  HIPCHK(hipSetDevice(k->device));
+  EkfStage st(k, me, dev);
+  EkfWalk w;
+  std::memset(&w, 0, sizeof(w));
+  st.in("u", u, B * nu * sizeof(double), &w.U);
+  { int rc = st.begin(); if (rc) return rc; }
+  w.B = k->B; w.t0 = k->t; w.T = 1;
+  { int rc = ekf_walk(k, me, w, k->stream); if (rc) return rc; }
+  k->t += 1;
+  return st.finish();
+}
+
+int cddp_hip_ekf_get(cddp_hip_ekf *k, int flags, double *xh, double *P, int32_t *info) {
+  static const char *const me = "cddp_hip_ekf_get";
+  { int rc = ekf_flags(me, k, flags, CDDP_HIP_EKF_DEVICE); if (rc) return rc; }
+  const bool dev = (flags & CDDP_HIP_EKF_DEVICE) != 0;
+  const size_t nx = (size_t)k->nx, B = (size_t)k->B;
+  HIPCHK(hipSetDevice(k->device));
+  struct { void *dst; const void *src; size_t bytes; const char *name; } cp[3] = {
+      {xh, k->e.xh, B * nx * sizeof(double), "xh"}, {P, k->e.P, B * nx * nx * sizeof(double), "P"}, {info, k->e.info, B * sizeof(int32_t), "info"}};
+  if (dev) for (const auto &c : cp) if (c.dst) { int rc = io_check_pointer(k->device, "estimator", c.dst, c.bytes, me, c.name); if (rc) return rc; }
+  for (const auto &c : cp) if (c.dst) HIPCHK(hipMemcpyAsync(c.dst, c.src, c.bytes, dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, k->stream));
+  HIPCHK(hipStreamSynchronize(k->stream));
+  return 0;
+}
+
+int cddp_hip_ekf_run(cddp_hip_ekf *k, int flags, int T, const double *Y, const double *U, double *Xh_out, double *P_out, double *nis_out, int32_t *info) {
+  static const char *const me = "cddp_hip_ekf_run";
+  { int rc = ekf_flags(me, k, flags, CDDP_HIP_EKF_DEVICE | CDDP_HIP_EKF_SKIP_NAN | CDDP_HIP_EKF_DIAG); if (rc) return rc; }
+  if (T < 0) return fail(-1, "%s: T must not be negative (got %d)", me, T);
+  if (!Y) return fail(-1, "%s: null Y pointer", me);
+  if (T > 0 && !U) return fail(-1, "%s: null U pointer", me);
+  const bool dev = (flags & CDDP_HIP_EKF_DEVICE) != 0, skip = (flags & CDDP_HIP_EKF_SKIP_NAN) != 0, diag = (flags & CDDP_HIP_EKF_DIAG) != 0;
+  const size_t nx = (size_t)k->nx, nu = (size_t)k->nu, B = (size_t)k->B, m = (size_t)k->e.ny, R = (size_t)T + 1;
+  if (!dev) {
+    if (!ekf_meas_finite(Y, B * R * m, skip)) return fail(-2, "%s: Y holds a non-finite value (a NaN is a missing measurement only with CDDP_HIP_EKF_SKIP_NAN)", me);
+    if (T > 0 && !ref_all_finite(U, B * T * nu)) return fail(-2, "%s: U holds a non-finite value", me);
+  }
+  HIPCHK(hipSetDevice(k->device));
+  EkfStage st(k, me, dev);
+  EkfWalk w;
+  std::memset(&w, 0, sizeof(w));
+  st.in("Y", Y, B * R * m * sizeof(double), &w.Y);
+  st.in("U", T > 0 ? U : nullptr, B * T * nu * sizeof(double), &w.U);
+  st.out("Xh_out", Xh_out, B * R * nx * sizeof(double), &w.Xh_out);
+  st.out("P_out", P_out, B * R * (diag ? nx : nx * nx) * sizeof(double), &w.P_out);
+  st.out("nis_out", nis_out, B * R * sizeof(double), &w.nis_out);
+  st.out("info", info, B * sizeof(int32_t), &w.info_out);
+  { int rc = st.begin(); if (rc) return rc; }
+  w.B = k->B; w.t0 = k->t; w.T = T; w.upd0 = 1; w.upd_after = 1; w.skip_nan = skip ? 1 : 0; w.diag = diag ? 1 : 0;
+  { int rc = ekf_walk(k, me, w, k->stream); if (rc) return rc; }
+  k->t += T;
+  return st.finish();
+}
+
+int cddp_hip_mpc_run_ekf(cddp_hip_handle *h, cddp_hip_plant *plant, cddp_hip_ekf *k, int steps, int mode, int flags, const double *x0_true, const double *W,
+                         const double *Yn, double *U_applied, double *X_visited, double *Xh_visited, double *nis, int32_t *iterations, int32_t *status,
+                         cddp_hip_stats *stats_sum) {
+  static const char *const me = "cddp_hip_mpc_run_ekf";
+  { int rc = plant_fits(me, h, plant); if (rc) return rc; }
+  if (!k) return fail(-1, "%s: null estimator", me);
+  if (k->nx != h->nx || k->nu != h->nu) return fail(-2, "%s: the estimator has nx = %d, nu = %d, the handle nx = %d, nu = %d", me, k->nx, k->nu, h->nx, h->nu);
+  if (k->B != h->B) return fail(-2, "%s: the estimator was created for a batch of %d, the handle for %d", me, k->B, h->B);
+  if (k->device != h->device) return fail(-2, "%s: the estimator lives on device %d, the handle on device %d", me, k->device, h->device);
+  if (steps <= 0) return fail(-1, "%s: steps must be positive (got %d)", me, steps);
+  const bool skip = (flags & CDDP_HIP_MPC_EKF_SKIP_NAN) != 0;
+  flags &= ~CDDP_HIP_MPC_EKF_SKIP_NAN;
+  for (Inner *q : h->g) { int rc = in_mpc_check(q, mode, flags); if (rc) return rc; }
+  if (!x0_true) return fail(-1, "%s: null x0_true pointer", me);
+  const size_t nx = (size_t)h->nx, nu = (size_t)h->nu, B = (size_t)h->B, m = (size_t)k->e.ny, S = (size_t)steps;
+  if (!ref_all_finite(x0_true, B * nx)) return fail(-2, "%s: x0_true holds a non-finite value", me);
+  if (W && !ref_all_finite(W, B * S * nx)) return fail(-2, "%s: W holds a non-finite value", me);
+  if (Yn && !ekf_meas_finite(Yn, B * (S + 1) * m, skip)) return fail(-2, "%s: Yn holds a non-finite value (a NaN is a missing measurement only with CDDP_HIP_MPC_EKF_SKIP_NAN)", me);
+  HIPCHK(hipSetDevice(h->device));
+  // the step's own arrays, and the noise step-major ([k][B][.]) so that a step reads one contiguous block, as the public entries do
+  double *const dx = k->d_loop, *const dy = dx + B * nx, *const du0 = dy + B * m, *const dnis = du0 + B * nu;
+  { int rc = ekf_grow(&k->d_noise, &k->noise_cap, S * B * (nx + m)); if (rc) return rc; }
+  { int rc = ekf_grow(&k->d_log, &k->log_cap, B * S * (nx + 1)); if (rc) return rc; }
+  double *const dW = k->d_noise, *const dYn = dW + S * B * nx, *const dXh = k->d_log, *const dNis = dXh + B * S * nx;
+  {
+    std::vector<double> buf(S * B * std::max(nx, m));
+    if (W) {
+      for (size_t b = 0; b < B; ++b) for (size_t s = 0; s < S; ++s) std::memcpy(&buf[(s * B + b) * nx], W + (b * S + s) * nx, nx * sizeof(double));
+      HIPCHK(hipMemcpy(dW, buf.data(), S * B * nx * sizeof(double), hipMemcpyHostToDevice));
+    }
+    if (Yn) {
+      for (size_t b = 0; b < B; ++b) for (size_t s = 0; s < S; ++s) std::memcpy(&buf[(s * B + b) * m], Yn + (b * (S + 1) + s) * m, m * sizeof(double));
+      HIPCHK(hipMemcpy(dYn, buf.data(), S * B * m * sizeof(double), hipMemcpyHostToDevice));
+    }
+  }
+  HIPCHK(hipMemcpy(dx, x0_true, B * nx * sizeof(double), hipMemcpyHostToDevice));
+  HIPCHK(hipMemset(k->d_log, 0, B * S * (nx + 1) * sizeof(double)));
+  HIPCHK(hipStreamSynchronize(k->stream));   // (an earlier entry of the estimator has completed: they all synchronise; this orders a failed one)
+  if (stats_sum) std::memset(stats_sum, 0, sizeof(*stats_sum));
+  { int rc = fork_from_user(h); if (rc) return rc; }
+  auto log_of = [&](size_t gi, int kk) {
+    EkfLog l;
+    std::memset(&l, 0, sizeof(l));
+    l.nx = (int)nx; l.nu = (int)nu; l.b0 = h->b0[gi]; l.B = h->g[gi]->d.B; l.steps = steps; l.k = kk;
+    l.Xh_log = dXh; l.nis_log = dNis; l.Ulog = h->g[gi]->d_log_u; l.Xlog = h->g[gi]->d_log_x;
+    return l;
+  };
+  for (size_t gi = 0; gi < h->g.size(); ++gi) {
+    Inner *q = h->g[gi];
+    int rc = in_mpc_log_begin(q, steps); if (rc) return rc;
+    EkfLog l = log_of(gi, -1);
+    l.x = dx;
+    HIPCHK(ekf_launch_log(l, q->stream));
+  }
+  const int aflags = flags | CDDP_HIP_MPC_X_DEVICE;
+  int rc_run = 0;
+  std::string err_run;
+  for (int kk = 0; kk < steps && !rc_run; ++kk) {
+    const int kmode = kk == 0 ? CDDP_HIP_MPC_KEEP_PLAN : mode, kflags = kk == 0 ? CDDP_HIP_MPC_X_DEVICE : aflags;
+    for (Inner *q : h->g) { rc_run = in_mpc_check(q, kmode, kflags); if (rc_run) break; }
+    // per group, on its stream: y from the true state, the update, the estimate into the log, the advance from the estimate
+    for (size_t gi = 0; gi < h->g.size() && !rc_run; ++gi) {
+      Inner *q = h->g[gi];
+      const int b0 = h->b0[gi], Bg = q->d.B;
+      hipError_t e = ekf_launch_measure(k->e, (int)nx, b0, Bg, dx, Yn ? dYn + (size_t)kk * B * m : nullptr, dy, q->stream);
+      if (e != hipSuccess) { rc_run = fail(-10, "%s: measurement: %s", me, hipGetErrorString(e)); break; }
+      EkfWalk w;
+      std::memset(&w, 0, sizeof(w));
+      w.b0 = b0; w.B = Bg; w.t0 = k->t; w.upd0 = 1; w.skip_nan = skip ? 1 : 0; w.Y = dy; w.nis_out = dnis;
+      rc_run = ekf_walk(k, me, w, q->stream);
+      if (rc_run) break;
+      EkfLog l = log_of(gi, kk);
+      l.xh = k->e.xh; l.nis = dnis;
+      e = ekf_launch_log(l, q->stream);
+      if (e != hipSuccess) { rc_run = fail(-10, "%s: log: %s", me, hipGetErrorString(e)); break; }
+      rc_run = in_mpc_advance(q, kmode, kflags, k->e.xh + (size_t)b0 * nx, false);
+    }
+    if (rc_run) break;
+    cddp_hip_stats st;
+    rc_run = cddp_hip_solve(h, stats_sum ? &st : nullptr);
+    if (rc_run) break;
+    if (stats_sum) stats_add(stats_sum, st);
+    // iterations and status (and the model's own head, which the rows below replace); u_0 of the plan; the plant on the true state; the
+    // prediction with the commanded u_0; the saturated u_0 and x_{k+1} into the log
+    for (size_t gi = 0; gi < h->g.size() && !rc_run; ++gi) {
+      Inner *q = h->g[gi];
+      const int b0 = h->b0[gi], Bg = q->d.B;
+      rc_run = in_mpc_log(q, steps, kk);
+      if (rc_run) break;
+      hipError_t e = ekf_launch_head(q->d, (int)nu, b0, du0, q->stream);
+      double *const xg = dx + (size_t)b0 * nx, *const ug = du0 + (size_t)b0 * nu;
+      if (e == hipSuccess) e = plant_launch_step(plant->pd, Bg, b0, xg, ug, W ? dW + ((size_t)kk * B + b0) * nx : nullptr, xg, q->stream);
+      if (e != hipSuccess) { rc_run = fail(-10, "%s: plant step: %s", me, hipGetErrorString(e)); break; }
+      EkfLog l = log_of(gi, kk);
+      l.u0 = du0; l.x = dx; l.lower = plant->pd.lower; l.upper = plant->pd.upper;
+      e = ekf_launch_log(l, q->stream);
+      if (e != hipSuccess) { rc_run = fail(-10, "%s: log: %s", me, hipGetErrorString(e)); break; }
+      EkfWalk w;
+      std::memset(&w, 0, sizeof(w));
+      w.b0 = b0; w.B = Bg; w.t0 = k->t; w.T = 1; w.U = du0;
+      rc_run = ekf_walk(k, me, w, q->stream);
+    }
+    if (!rc_run) k->t += 1;
+  }
+  if (rc_run) err_run = g_err;
+  for (size_t gi = 0; gi < h->g.size(); ++gi) {
+    const size_t b0 = (size_t)h->b0[gi];
+    int rc = in_mpc_log_fetch(h->g[gi], steps, U_applied ? U_applied + b0 * S * nu : nullptr, X_visited ? X_visited + b0 * (S + 1) * nx : nullptr,
+                              iterations ? iterations + b0 * S : nullptr, status ? status + b0 * S : nullptr);
+    if (rc && !rc_run) return rc;
+  }
+  // (every group stream has been synchronised by its fetch)
+  if (Xh_visited) HIPCHK(hipMemcpy(Xh_visited, dXh, B * S * nx * sizeof(double), hipMemcpyDeviceToHost));
+  if (nis) HIPCHK(hipMemcpy(nis, dNis, B * S * sizeof(double), hipMemcpyDeviceToHost));
+  if (rc_run) { g_err = err_run; return rc_run; }
+  return join_to_user(h);
 }
 
 }  // extern "C"

@@ -779,6 +779,62 @@ class Plant {
   int batch_ = 0, nx_ = 0, nu_ = 0;
 };
 
+// ---- the device-resident extended Kalman filter (cddp_hip_ekf; include/cddp_hip.h "extended Kalman filter on the device") ----------
+// A thin owner of the C handle over host vectors, batch-major.  The model plant must outlive the filter.
+class Ekf {
+ public:
+  Ekf(Plant &model, const cddp_hip_ekf_desc &desc, int nx, int nu) : batch_(model.batch()), nx_(nx), nu_(nu), ny_(desc.ny) {
+    if (cddp_hip_ekf_create(model.get(), &desc, &k_) != 0) throw std::runtime_error(std::string("cddp_hip: ") + cddp_hip_last_error());
+  }
+  ~Ekf() { if (k_) cddp_hip_ekf_destroy(k_); }
+  Ekf(const Ekf &) = delete;
+  Ekf &operator=(const Ekf &) = delete;
+  Ekf(Ekf &&o) noexcept : k_(o.k_), batch_(o.batch_), nx_(o.nx_), nu_(o.nu_), ny_(o.ny_) { o.k_ = nullptr; }
+  // xh0: batch * nx; P0: nx * nx for the batch, or batch * nx * nx (only its lower triangle is read)
+  void reset(const std::vector<double> &xh0, const std::vector<double> &P0) {
+    const size_t one = (size_t)nx_ * nx_;
+    if (xh0.size() != (size_t)batch_ * nx_ || (P0.size() != one && P0.size() != one * batch_)) throw std::invalid_argument("cddp_hip: Ekf::reset: xh0 must hold batch * nx, P0 nx * nx or batch * nx * nx doubles");
+    check(cddp_hip_ekf_reset(k_, P0.size() != one ? CDDP_HIP_EKF_PER_TRAJ : 0, xh0.data(), P0.data()));
+  }
+  // the measurement update with y (batch * ny) -> nis (batch); flags: CDDP_HIP_EKF_SKIP_NAN
+  std::vector<double> update(const std::vector<double> &y, int flags = 0) {
+    if (y.size() != (size_t)batch_ * ny_) throw std::invalid_argument("cddp_hip: Ekf::update: y must hold batch * ny doubles");
+    std::vector<double> nis((size_t)batch_);
+    check(cddp_hip_ekf_update(k_, flags & CDDP_HIP_EKF_SKIP_NAN, y.data(), nis.data()));
+    return nis;
+  }
+  void predict(const std::vector<double> &u) {
+    if (u.size() != (size_t)batch_ * nu_) throw std::invalid_argument("cddp_hip: Ekf::predict: u must hold batch * nu doubles");
+    check(cddp_hip_ekf_predict(k_, 0, u.data()));
+  }
+  struct State { std::vector<double> xh, P; std::vector<int32_t> info; };   // [b][nx], [b][nx][nx], [b]
+  State get() {
+    State s;
+    s.xh.assign((size_t)batch_ * nx_, 0.0); s.P.assign((size_t)batch_ * nx_ * nx_, 0.0); s.info.assign((size_t)batch_, 0);
+    check(cddp_hip_ekf_get(k_, 0, s.xh.data(), s.P.data(), s.info.data()));
+    return s;
+  }
+  // a whole log in one launch: Y [b][T + 1][ny], U [b][T][nu]; flags: CDDP_HIP_EKF_SKIP_NAN | CDDP_HIP_EKF_DIAG
+  struct Log { std::vector<double> Xh, P, nis; std::vector<int32_t> info; };   // [b][T + 1][nx], [b][T + 1][nx][nx] (DIAG: [nx]), [b][T + 1], [b]
+  Log run(int T, const std::vector<double> &Y, const std::vector<double> &U, int flags = 0) {
+    const size_t B = (size_t)batch_, R = (size_t)std::max(T, 0) + 1;
+    if (Y.size() != B * R * ny_ || U.size() != B * (R - 1) * nu_) throw std::invalid_argument("cddp_hip: Ekf::run: Y must hold batch * (T + 1) * ny, U batch * T * nu doubles");
+    Log g;
+    const bool diag = (flags & CDDP_HIP_EKF_DIAG) != 0;
+    g.Xh.assign(B * R * nx_, 0.0); g.P.assign(B * R * nx_ * (diag ? 1 : nx_), 0.0); g.nis.assign(B * R, 0.0); g.info.assign(B, 0);
+    check(cddp_hip_ekf_run(k_, flags & (CDDP_HIP_EKF_SKIP_NAN | CDDP_HIP_EKF_DIAG), T, Y.data(), U.empty() ? nullptr : U.data(), g.Xh.data(), g.P.data(),
+                           g.nis.data(), g.info.data()));
+    return g;
+  }
+  cddp_hip_ekf *get_handle() const { return k_; }
+  int ny() const { return ny_; }
+
+ private:
+  static void check(int rc) { if (rc != 0) throw std::runtime_error(std::string("cddp_hip: ") + cddp_hip_last_error()); }
+  cddp_hip_ekf *k_ = nullptr;
+  int batch_ = 0, nx_ = 0, nu_ = 0, ny_ = 0;
+};
+
 // ---- the GPU solver strategy ----------------------------------------------------------------------
 class HipBatchSolver : public ISolverAlgorithm {
  public:
@@ -866,6 +922,23 @@ class HipBatchSolver : public ISolverAlgorithm {
     g.U_applied.assign(B * K * nu_, 0.0); g.X_visited.assign(B * (K + 1) * nx_, 0.0); g.iterations.assign(B * K, 0); g.status.assign(B * K, 0);
     check(cddp_hip_mpc_run_plant(h_, plant.get(), steps, mode, flags, W.empty() ? nullptr : W.data(), g.U_applied.data(), g.X_visited.data(),
                                  g.iterations.data(), g.status.data(), &g.stats_sum));
+    return g;
+  }
+  // NEW: the loop closed through an estimator that sees only y = C x + Yn (cddp_hip_mpc_run_ekf).  x0_true: batch * nx; W: batch * steps * nx
+  // or empty; Yn: batch * (steps + 1) * ny or empty.  The batch needs a current plan (initialize() or a solve).
+  struct MpcEkfLog : MpcLog { std::vector<double> Xh_visited, nis; };   // [b][k][nx], [b][k]
+  MpcEkfLog mpcRunEkf(Plant &plant, Ekf &ekf, int steps, int mode, const std::vector<double> &x0_true, int flags = 0, const std::vector<double> &W = {},
+                      const std::vector<double> &Yn = {}) {
+    if (!h_) throw std::runtime_error("cddp_hip: mpcRunEkf needs a resident batch (the plug-in route keeps no plan on the device)");
+    MpcEkfLog g;
+    const size_t B = (size_t)batch_, K = (size_t)std::max(steps, 0);
+    if (x0_true.size() != B * nx_ || (!W.empty() && W.size() != B * K * nx_) || (!Yn.empty() && Yn.size() != B * (K + 1) * ekf.ny()))
+      throw std::invalid_argument("cddp_hip: mpcRunEkf: x0_true must hold batch * nx, W batch * steps * nx, Yn batch * (steps + 1) * ny doubles");
+    g.U_applied.assign(B * K * nu_, 0.0); g.X_visited.assign(B * (K + 1) * nx_, 0.0); g.iterations.assign(B * K, 0); g.status.assign(B * K, 0);
+    g.Xh_visited.assign(B * K * nx_, 0.0); g.nis.assign(B * K, 0.0);
+    check(cddp_hip_mpc_run_ekf(h_, plant.get(), ekf.get_handle(), steps, mode, flags, x0_true.data(), W.empty() ? nullptr : W.data(),
+                               Yn.empty() ? nullptr : Yn.data(), g.U_applied.data(), g.X_visited.data(), g.Xh_visited.data(), g.nis.data(),
+                               g.iterations.data(), g.status.data(), &g.stats_sum));
     return g;
   }
   // NEW: the solved plan's feedback policy on the plant over the horizon (cddp_hip_track_plan).  x0: batch * nx or empty = row 0 of the

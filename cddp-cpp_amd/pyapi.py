@@ -236,6 +236,16 @@ class McofDesc(C.Structure):   # cddp_hip_mcof_desc
     _fields_ = [("mc", McDesc), ("ny", C.c_int32), ("_pad", C.c_int32), ("C", _dp), ("v", _dp)]
 
 
+# cddp_hip_ekf_* / cddp_hip_mpc_run_ekf (include/cddp_hip.h, "extended Kalman filter on the device; the MPC loop closed through it")
+EKF_DEVICE, EKF_SKIP_NAN, EKF_PER_TRAJ, EKF_DIAG = 1, 2, 4, 8
+MPC_EKF_SKIP_NAN = 256
+
+
+class EkfDesc(C.Structure):   # cddp_hip_ekf_desc
+    _fields_ = [("abi_version", C.c_int32), ("ny", C.c_int32), ("per_trajectory", C.c_int32), ("_pad", C.c_int32),
+                ("C", _dp), ("v", _dp), ("W", _dp), ("Wu", _dp)]
+
+
 class Stats(C.Structure):
     _fields_ = [
         ("solve_ms", C.c_double), ("backward_ms", C.c_double), ("forward_ms", C.c_double),
@@ -862,6 +872,16 @@ PLANT_ARGTYPES = {
     "cddp_hip_plant_step": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
     "cddp_hip_mpc_run_plant": [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(Stats)],
     "cddp_hip_track_plan": [C.c_void_p, C.c_void_p, _dp, _dp, _dp, _dp],
+    # (the arrays of the step entries are host OR device addresses, by the flag: plain pointer values)
+    "cddp_hip_ekf_create": [C.c_void_p, C.POINTER(EkfDesc), C.POINTER(C.c_void_p)],
+    "cddp_hip_ekf_destroy": [C.c_void_p],
+    "cddp_hip_ekf_reset": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p],
+    "cddp_hip_ekf_update": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p],
+    "cddp_hip_ekf_predict": [C.c_void_p, C.c_int, C.c_void_p],
+    "cddp_hip_ekf_get": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
+    "cddp_hip_ekf_run": [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 6,
+    "cddp_hip_mpc_run_ekf": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp,
+                             C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(Stats)],
 }
 # (device addresses: plain pointer values)
 DEVICE_IO_ARGTYPES = {
@@ -910,6 +930,8 @@ EXPORTED_SYMBOLS = [
     "cddp_hip_sample_controls", "cddp_hip_mppi_blend", "cddp_hip_mppi_refine",
     "cddp_hip_mc_sample_noise", "cddp_hip_plan_montecarlo", "cddp_hip_mc_sample_meas_noise", "cddp_hip_plan_montecarlo_of",
     "cddp_hip_set_reference", "cddp_hip_get_reference", "cddp_hip_mpc_set_reference_path", "cddp_hip_mpc_reference_cursor",
+    "cddp_hip_ekf_create", "cddp_hip_ekf_destroy", "cddp_hip_ekf_reset", "cddp_hip_ekf_update", "cddp_hip_ekf_predict", "cddp_hip_ekf_get",
+    "cddp_hip_ekf_run", "cddp_hip_mpc_run_ekf",
 ]
 
 
@@ -1099,6 +1121,27 @@ class HipBatchSolver:
         self._check(self.lib.cddp_hip_mpc_run_plant(self.h, plant.h if plant is not None else None, steps, int(mode), MPC_SHIFT_DUALS if shift_duals else 0,
                                                     _ptr(Wa), _ptr(U), _ptr(X), it.ctypes.data_as(i32), st.ctypes.data_as(i32), C.byref(stats)))
         return {"U_applied": U, "X_visited": X, "iterations": it, "status": st, "stats": stats}
+
+    def mpc_run_ekf(self, plant, ekf, steps, mode, x0_true, W=None, Yn=None, shift_duals=False, skip_nan=False):
+        """`steps` closed-loop MPC steps against a DevicePlant with a controller that sees only y = C x + Yn (cddp_hip_mpc_run_ekf): per step
+        the DeviceEkf's update, the advance from its estimate, the solve, the plant step on the TRUE state (which starts at x0_true (B, nx)),
+        the prediction with the commanded u_0.  W: None or (B, steps, nx); Yn: None or (B, steps + 1, ny); both uploaded once.  The handle
+        needs a current plan (set_initial and initialize or solve).  Returns the dict of mpc_run_plant plus Xh_visited (B, steps, nx), the
+        estimate each solve started from, and nis (B, steps)."""
+        steps = int(steps); self.plan_epoch += 1
+        n = max(steps, 0); nx, nu = self.p.nx, self.p.nu
+        U = np.zeros((self.B, n, nu)); X = np.zeros((self.B, n + 1, nx)); Xh = np.zeros((self.B, n, nx)); nis = np.zeros((self.B, n))
+        it = np.zeros((self.B, n), dtype=np.int32); st = np.zeros((self.B, n), dtype=np.int32)
+        x0a = _arr(x0_true).reshape(self.B, nx) if x0_true is not None else None
+        Wa = _arr(W).reshape(self.B, n, nx) if W is not None else None
+        Ya = _arr(Yn).reshape(self.B, n + 1, ekf.ny) if Yn is not None else None
+        stats = Stats()
+        i32 = C.POINTER(C.c_int32)
+        flags = (MPC_SHIFT_DUALS if shift_duals else 0) | (MPC_EKF_SKIP_NAN if skip_nan else 0)
+        self._check(self.lib.cddp_hip_mpc_run_ekf(self.h, plant.h if plant is not None else None, ekf.h if ekf is not None else None, steps, int(mode),
+                                                  flags, _ptr(x0a), _ptr(Wa), _ptr(Ya), _ptr(U), _ptr(X), _ptr(Xh), _ptr(nis),
+                                                  it.ctypes.data_as(i32), st.ctypes.data_as(i32), C.byref(stats)))
+        return {"U_applied": U, "X_visited": X, "Xh_visited": Xh, "nis": nis, "iterations": it, "status": st, "stats": stats}
 
     def track_plan(self, plant, x0=None, W=None):
         """The solved plan's feedback policy u_t = U_t + K_t (x_t - X_t) rolled out on a DevicePlant over the horizon (cddp_hip_track_plan).
@@ -2055,6 +2098,117 @@ class DevicePlant:
     def close(self):
         if self.h:
             self.lib.cddp_hip_plant_destroy(self.h); self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class DeviceEkf:
+    """A device-resident extended Kalman filter for a batch of trajectories (cddp_hip_ekf) with a DevicePlant as its model: sensors
+    y = C x + n, cov(n) = diag(v); C (ny, nx) and v (ny,) shared by the batch, or (B, ny, nx) and (B, ny) -- then W (nx, nx) and Wu (nu, nu),
+    where given, carry the batch axis too.  reset / update / predict / get / run take numpy arrays (uploaded, computed, returned as numpy)
+    or float64 torch tensors on the plant's device (read and written in place, after a synchronisation of their current stream; torch
+    tensors are returned).  The plant must outlive the filter: the object keeps a reference to it."""
+
+    def __init__(self, plant, C_, v, W=None, Wu=None):
+        self.lib = plant.lib
+        self.plant = plant
+        self.B, self.nx, self.nu, self._device = plant.B, plant.nx, plant.nu, plant._device
+        Ca = _arr(C_); va = _arr(v)
+        per = Ca.ndim == 3
+        self.ny = int(Ca.shape[-2]) if Ca.ndim >= 2 else 0
+        lead = (self.B,) if per else ()
+        self.keep = [Ca.reshape(lead + (self.ny, self.nx)), va.reshape(lead + (self.ny,))]
+        d = EkfDesc()
+        d.abi_version = ABI_VERSION; d.ny = self.ny; d.per_trajectory = 1 if per else 0
+        d.C = _ptr(self.keep[0]); d.v = _ptr(self.keep[1])
+        for name, M, n in (("W", W, self.nx), ("Wu", Wu, self.nu)):
+            if M is not None:
+                a = _arr(M).reshape(lead + (n, n)); self.keep.append(a); setattr(d, name, _ptr(a))
+        self.desc = d
+        self.h = C.c_void_p()
+        self._check(self.lib.cddp_hip_ekf_create(plant.h, C.byref(d), C.byref(self.h)))
+
+    def _check(self, rc):
+        if rc != 0:
+            raise HipError("cddp_hip error %d: %s" % (rc, self.lib.cddp_hip_last_error().decode()))
+
+    @staticmethod
+    def _is_torch(a):
+        return a is not None and hasattr(a, "data_ptr") and not isinstance(a, np.ndarray)
+
+    def _args(self, named):
+        """named: (name, array or None, shape) triples, all numpy-like or all device tensors -> (device?, the arrays kept, their addresses)"""
+        dev = any(self._is_torch(a) for _, a, _ in named)
+        keep, ptrs = [], []
+        for name, a, shape in named:
+            if a is None:
+                keep.append(None); ptrs.append(None); continue
+            if dev:
+                import torch
+                if not self._is_torch(a) or not a.is_cuda or a.dtype != torch.float64 or tuple(a.shape) != tuple(shape):
+                    raise ValueError("%s: a float64 device tensor of shape %s is expected" % (name, tuple(shape)))
+                if a.device.index != self._device:
+                    raise ValueError("%s lives on device %s, the estimator on device %d" % (name, a.device.index, self._device))
+                t = a.contiguous(); keep.append(t); ptrs.append(t.data_ptr())
+            else:
+                t = _arr(a).reshape(shape); keep.append(t); ptrs.append(t.ctypes.data)
+        if dev:
+            import torch
+            torch.cuda.current_stream(torch.device("cuda", self._device)).synchronize()
+        return dev, keep, ptrs
+
+    def _out(self, dev, shape, dtype=np.float64):
+        if dev:
+            import torch
+            return torch.empty(shape, dtype=torch.float64 if dtype == np.float64 else torch.int32, device=torch.device("cuda", self._device))
+        return np.zeros(shape, dtype=dtype)
+
+    @staticmethod
+    def _addr(a):
+        return None if a is None else (a.data_ptr() if hasattr(a, "data_ptr") else a.ctypes.data)
+
+    def reset(self, xh0, P0):
+        """xh <- xh0 (B, nx); P <- P0 (nx, nx) for the batch or (B, nx, nx), its lower triangle mirrored; info and the step count <- 0"""
+        per = len(P0.shape) == 3 if hasattr(P0, "shape") else np.asarray(P0).ndim == 3
+        dev, keep, ptrs = self._args([("xh0", xh0, (self.B, self.nx)), ("P0", P0, ((self.B,) if per else ()) + (self.nx, self.nx))])
+        self._check(self.lib.cddp_hip_ekf_reset(self.h, (EKF_DEVICE if dev else 0) | (EKF_PER_TRAJ if per else 0), ptrs[0], ptrs[1]))
+
+    def update(self, y, skip_nan=False):
+        """The measurement update with y (B, ny) -> nis (B,).  skip_nan: a NaN in y is a missing measurement."""
+        dev, keep, ptrs = self._args([("y", y, (self.B, self.ny))])
+        nis = self._out(dev, (self.B,))
+        self._check(self.lib.cddp_hip_ekf_update(self.h, (EKF_DEVICE if dev else 0) | (EKF_SKIP_NAN if skip_nan else 0), ptrs[0], self._addr(nis)))
+        return nis
+
+    def predict(self, u):
+        """The prediction with the commanded control u (B, nu): the model plant clips it."""
+        dev, keep, ptrs = self._args([("u", u, (self.B, self.nu))])
+        self._check(self.lib.cddp_hip_ekf_predict(self.h, EKF_DEVICE if dev else 0, ptrs[0]))
+
+    def get(self, device=False):
+        """(xh (B, nx), P (B, nx, nx), info (B,) int32) of the object, as numpy arrays or (device=True) torch tensors"""
+        xh = self._out(device, (self.B, self.nx)); P = self._out(device, (self.B, self.nx, self.nx)); info = self._out(device, (self.B,), np.int32)
+        self._check(self.lib.cddp_hip_ekf_get(self.h, EKF_DEVICE if device else 0, self._addr(xh), self._addr(P), self._addr(info)))
+        return xh, P, info
+
+    def run(self, Y, U=None, skip_nan=False, diag=False, want=("Xh", "P", "nis", "info")):
+        """A whole log in one launch from the object's state: Y (B, T + 1, ny), U (B, T, nu) (None at T = 0) -> dict of the wanted
+        Xh (B, T + 1, nx), P (B, T + 1, nx, nx) (diag: (B, T + 1, nx)), nis (B, T + 1), info (B,)."""
+        T = int(Y.shape[1]) - 1
+        dev, keep, ptrs = self._args([("Y", Y, (self.B, T + 1, self.ny)), ("U", U if T > 0 else None, (self.B, T, self.nu))])
+        shapes = {"Xh": (self.B, T + 1, self.nx), "P": (self.B, T + 1, self.nx) + (() if diag else (self.nx,)), "nis": (self.B, T + 1), "info": (self.B,)}
+        out = {k: self._out(dev, shapes[k], np.int32 if k == "info" else np.float64) for k in want}
+        flags = (EKF_DEVICE if dev else 0) | (EKF_SKIP_NAN if skip_nan else 0) | (EKF_DIAG if diag else 0)
+        self._check(self.lib.cddp_hip_ekf_run(self.h, flags, T, ptrs[0], ptrs[1], *[self._addr(out.get(k)) for k in ("Xh", "P", "nis", "info")]))
+        return out
+
+    def close(self):
+        if self.h:
+            self.lib.cddp_hip_ekf_destroy(self.h); self.h = C.c_void_p()
 
     def __del__(self):
         try:

@@ -1082,7 +1082,7 @@ class CDDP:                         # cddp_core.hpp:214-423 / bind_solver.cpp:57
         return {"CLDDP": api.SOLVER_CLDDP, "IPDDP": api.SOLVER_IPDDP, "LogDDP": api.SOLVER_LOGDDP, "MSIPDDP": api.SOLVER_MSIPDDP}[name]
 
     def solve_mpc_batch(self, x0s, steps, solver_type=SolverType.IPDDP, warm_start="provided", shift_duals=False, plant=None, disturbances=None,
-                        reference_path=None, rows_per_step=1.0):
+                        reference_path=None, rows_per_step=1.0, estimator=None, meas_noise=None):
         """NEW (no reference counterpart): `steps` closed-loop MPC steps of one device-resident batch, the model as the plant -- solve, apply
         u_0, start the next solve at x_1 -- without the plan leaving the device between solves (cddp_hip_mpc_run).  Trajectory i starts at
         x0s[i]; the first solve is seeded as solve_batch seeds it.  warm_start names how every later solve is seeded:
@@ -1102,9 +1102,34 @@ class CDDP:                         # cddp_core.hpp:214-423 / bind_solver.cpp:57
         reference_path (None = the objective's fixed goal and reference states, today's call): (L, nx), a path the run follows
         (cddp_hip_mpc_set_reference_path) -- solve k tracks the window of rows (k + t) * rows_per_step, t = 0 .. horizon, linearly
         interpolated between rows and held at the last row past the end, with the window's last row as its goal; the windows are made
-        on the device, one small launch per step."""
+        on the device, one small launch per step.
+        estimator (None = the controller is handed the plant's exact state, today's call): a dict describing the sensors and the filter
+        of an output-feedback loop (cddp_hip_mpc_run_ekf) -- every solve starts from the estimate of a device-resident extended Kalman
+        filter that sees only y = C x + meas_noise: "C" (ny, nx) and "v" (ny,) measurement variances (required), "W" (nx, nx) and "Wu"
+        (nu, nu) process and actuator noise covariances of the filter, "P0" (nx, nx) the covariance of the initial estimate (default:
+        the identity), "xh0" (B, nx) the initial estimate (default: x0s), "model" a dict like `plant` describing the filter's model
+        (default: this problem's own model; it takes one step per control interval), "skip_nan" (a NaN in meas_noise is a missing
+        measurement).  x0s are then the TRUE initial states; needs a plant ({} = the model itself).  meas_noise: (B, steps + 1, ny), the
+        caller's draws, added to C x; needs an estimator.  The result also holds "estimate_trajectory" (B, steps, nx), the estimate
+        every solve started from, and "nis" (B, steps)."""
         api = _api()
         name = solver_type.value if isinstance(solver_type, SolverType) else str(solver_type)
+        if meas_noise is not None and estimator is None:
+            raise ValueError("meas_noise acts on the measurements of an estimator: pass estimator={...}")
+        if estimator is not None:
+            if plant is None:
+                raise ValueError("an estimator observes a plant: pass plant={} for a copy of the model")
+            unknown = set(estimator) - {"C", "v", "W", "Wu", "P0", "xh0", "model", "skip_nan"}
+            if unknown:
+                raise ValueError("estimator: unknown keys %s (known: C, v, W, Wu, P0, xh0, model, skip_nan)" % sorted(unknown))
+            if "C" not in estimator or "v" not in estimator:
+                raise ValueError("estimator: C and v must be given")
+            em = estimator.get("model") or {}
+            unknown = set(em) - {"params", "integrator", "u_lower", "u_upper"}
+            if unknown:
+                raise ValueError("estimator model: unknown keys %s (known: params, integrator, u_lower, u_upper)" % sorted(unknown))
+            if "integrator" in em and em["integrator"] not in _INTEGRATORS:
+                raise ValueError("Unknown integration type: " + str(em["integrator"]))
         modes = {"provided": api.MPC_SHIFT_PROVIDED, "existing": api.MPC_SHIFT_EXISTING, "keep": api.MPC_KEEP_PLAN}
         if warm_start not in modes:
             raise ValueError("warm_start must be 'provided', 'existing' or 'keep' (got %r)" % (warm_start,))
@@ -1129,12 +1154,25 @@ class CDDP:                         # cddp_core.hpp:214-423 / bind_solver.cpp:57
         U0 = None if self._U is None else np.ascontiguousarray(np.tile(self._U, (B, 1, 1)))
         X0 = None if self._X is None else np.ascontiguousarray(np.tile(self._X, (B, 1, 1)))
         hs = api.HipBatchSolver(p, B)
-        dp = None
+        dp = mp = ekf = None
         try:
             hs.set_initial(x0, U0, X0)
             if reference_path is not None:
                 hs.mpc_set_reference_path(reference_path, 0, rows_per_step)
-            if plant is None:
+            if estimator is not None:
+                def device_plant(d):
+                    over = {k: d[k] for k in ("params", "substeps", "u_lower", "u_upper") if k in d}
+                    if "integrator" in d:
+                        over["integrator"] = _INTEGRATORS[d["integrator"]]
+                    return api.DevicePlant.of_problem(p, B, **over)
+                dp = device_plant(plant); mp = device_plant(estimator.get("model") or {})
+                ekf = api.DeviceEkf(mp, estimator["C"], estimator["v"], estimator.get("W"), estimator.get("Wu"))
+                xh0 = estimator.get("xh0")
+                ekf.reset(x0 if xh0 is None else np.asarray(xh0, dtype=np.float64), np.asarray(estimator.get("P0", np.eye(p.nx)), dtype=np.float64))
+                hs.initialize()                     # the first step is an advance from the estimate: it needs a plan
+                r = hs.mpc_run_ekf(dp, ekf, int(steps), modes[warm_start], x0, W=disturbances, Yn=meas_noise, shift_duals=shift_duals,
+                                   skip_nan=bool(estimator.get("skip_nan", False)))
+            elif plant is None:
                 r = hs.mpc_run(int(steps), modes[warm_start], shift_duals=shift_duals)
             else:
                 over = {k: plant[k] for k in ("params", "substeps", "u_lower", "u_upper") if k in plant}
@@ -1143,12 +1181,16 @@ class CDDP:                         # cddp_core.hpp:214-423 / bind_solver.cpp:57
                 dp = api.DevicePlant.of_problem(p, B, **over)
                 r = hs.mpc_run_plant(dp, int(steps), modes[warm_start], shift_duals=shift_duals, W=disturbances)
         finally:
-            if dp is not None:
-                dp.close()
+            for o in (ekf, mp, dp):
+                if o is not None:
+                    o.close()
             hs.close()
-        return {"state_trajectory": r["X_visited"], "control_trajectory": r["U_applied"], "iterations": r["iterations"],
-                "status_message": [[api.STATUS_STRINGS[int(s)] for s in row] for row in r["status"]],
-                "solve_time_ms": float(r["stats"].solve_ms)}
+        out = {"state_trajectory": r["X_visited"], "control_trajectory": r["U_applied"], "iterations": r["iterations"],
+               "status_message": [[api.STATUS_STRINGS[int(s)] for s in row] for row in r["status"]],
+               "solve_time_ms": float(r["stats"].solve_ms)}
+        if estimator is not None:
+            out["estimate_trajectory"] = r["Xh_visited"]; out["nis"] = r["nis"]
+        return out
 
     def solve_batch_device(self, x0s, U0=None, X0=None, solver_type=SolverType.IPDDP, want=("X", "U")):
         """NEW (no reference counterpart): solve_batch from device tensors to device tensors (cddp_hip_set_initial_device,

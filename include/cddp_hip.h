@@ -1120,6 +1120,89 @@ int cddp_hip_plan_montecarlo_of(cddp_hip_handle *h, cddp_hip_plant *plant /* or 
                                 double *SE /* [B][N+1][nx][nx] | DIAG [B][N+1][nx] */,
                                 double *Xh_out /* [B][S][N+1][nx] */);   /* any output may be NULL, not all */
 
+/* ---- extended Kalman filter on the device; the MPC loop closed through it ------------
+ * A cddp_hip_ekf is a device-resident extended Kalman filter for a batch of trajectories.  Its model is a cddp_hip_plant: the filter
+ * uses that object's model, parameters (shared or per trajectory), integrator, dt, box, batch and device, and the plant must outlive it.
+ * Sensors: y = C x + n, cov(n) = diag(v), C ny x nx with 1 <= ny <= CDDP_HIP_KF_MAX_NY (ny may exceed nx); process noise W (nx x nx) and
+ * actuator noise Wu (nu x nu), either may be NULL.  The state of the object is the estimate xh [B][nx], its covariance P [B][nx][nx]
+ * (kept full and symmetric), info [B] and a step count (the number of predictions since cddp_hip_ekf_reset).
+ * (New entry points; ABI version unchanged; the descriptor carries its own abi_version.)
+ *
+ * Arithmetic (csrc/ekf.hpp; no FMA contraction; the tests are bitwise).  Every sum starts from the stated value, its index ascending.
+ *  Measurement update of trajectory b, rows r = 0 .. ny-1 ascending, c = C[r]:
+ *   1. h[i] = sum_j P[i][j] * c[j], from 0.0            2. s = v[r]; s += c[j] * h[j]
+ *   3. m = sum_j c[j] * xh[j], from 0.0;  e = y[r] - m   4. g[i] = h[i] / s            5. xh[i] = xh[i] + g[i] * e
+ *   6. for i ascending, j <= i:  q = P[i][j]; q -= g[i] * h[j]; q -= h[i] * g[j]; q += (s * g[i]) * g[j];  P[i][j] = P[j][i] = q
+ *      (cddp_hip_plan_kalman's row update)              7. nis += (e * e) / s, from 0.0 at the first row
+ *   With CDDP_HIP_EKF_SKIP_NAN a row whose y[r] is NaN is skipped entirely (a sensor drop-out).  A row whose s is not > 0 leaves xh and P
+ *   alone and sets info = t + 1 (t: the object's step count; the first such row wins; 0 otherwise); that trajectory's xh, P and nis are NaN
+ *   from that step on, in the outputs and in the object, until the next reset.  Other trajectories are unaffected.
+ *  Prediction with control u:
+ *   1. u_s = the plant's clip of u (cddp_hip_plant_step's line; only with a box)       2. Fx, Fu = the model's Jacobians at (params_b, xh, u_s)
+ *   3. A[i][j] = h * Fx[i][j], then += 1.0 where i == j;  Bm = h * Fu -- the solver's own linearisation, discrete plants included; h = dt
+ *   4. xh <- one step of the plant from (xh, u_s)
+ *   5. P <- A P A^T + W + Bm Wu Bm^T, cddp_hip_plan_covariance's steps 4 and 5 with A for Acl: Y = A P; element (i, j <= i) =
+ *      sum_l A[i][l] * Y[j][l] from 0.0, then += W[i][j], then += sum_k (sum_m Bm[i][m] * Wu[m][k]) * Bm[j][k]; mirrored.  Only the lower
+ *      triangles of W and Wu are read.
+ * Not covered: sub-stepped estimator models (the product of sub-step Jacobians), nonlinear measurement functions, correlated measurement
+ *  noise, unscented or iterated filters, smoothing, an estimator inside cddp_hip_track_plan and the Monte-Carlo entries. */
+typedef struct cddp_hip_ekf_desc {
+  int32_t abi_version;           /* CDDP_HIP_ABI_VERSION */
+  int32_t ny;                    /* 1 .. CDDP_HIP_KF_MAX_NY */
+  int32_t per_trajectory;        /* 0: one C, v, W, Wu for the batch; 1: one set per trajectory, batch-major, all of them */
+  int32_t _pad;
+  const double *C;               /* host, [ny][nx] */
+  const double *v;               /* host, [ny] measurement variances, finite and > 0 */
+  const double *W;               /* host, [nx][nx] or NULL */
+  const double *Wu;              /* host, [nu][nu] or NULL */
+} cddp_hip_ekf_desc;             /* 48 bytes */
+typedef struct cddp_hip_ekf cddp_hip_ekf;
+enum { CDDP_HIP_EKF_DEVICE = 1,     /* the array arguments are device pointers of the plant's device, complete when the call is made */
+       CDDP_HIP_EKF_SKIP_NAN = 2,   /* a NaN in y is a missing measurement */
+       CDDP_HIP_EKF_PER_TRAJ = 4,   /* cddp_hip_ekf_reset: P0 is [B][nx][nx] */
+       CDDP_HIP_EKF_DIAG = 8 };     /* cddp_hip_ekf_run: P_out holds the diagonals, [B][T+1][nx] */
+/* The descriptor is checked BEFORE the device is looked at, each refusal with its own message, in this order: a NULL desc or out; wrong
+ * abi_version; ny outside 1 .. CDDP_HIP_KF_MAX_NY; a NULL C or v; a NULL model plant (the checks before it need no plant, those after it
+ * read its dimensions); a v entry that is not finite and > 0; a non-finite C, W or Wu; a model plant with substeps > 1.  The arrays are
+ * copied.  The filter starts at xh = 0, P = 0: call cddp_hip_ekf_reset. */
+int cddp_hip_ekf_create(cddp_hip_plant *model, const cddp_hip_ekf_desc *desc, cddp_hip_ekf **out);
+int cddp_hip_ekf_destroy(cddp_hip_ekf *ekf);
+/* Every entry below returns after its outputs are written.  Host pointers are uploaded and downloaded through the object's own scratch;
+ * with CDDP_HIP_EKF_DEVICE every array must be device memory of the plant's device whose allocation holds every byte the call touches
+ * (checked as cddp_hip_plan_kalman checks its device arguments).  Host inputs must be finite (y: NaN is allowed with SKIP_NAN).
+ * reset: xh <- xh0, P <- the lower triangle of P0 mirrored, info <- 0, step count <- 0. */
+int cddp_hip_ekf_reset(cddp_hip_ekf *ekf, int flags, const double *xh0 /* B*nx */, const double *P0 /* nx*nx, or B*nx*nx with PER_TRAJ */);
+int cddp_hip_ekf_update(cddp_hip_ekf *ekf, int flags, const double *y /* B*ny */, double *nis /* B or NULL */);
+int cddp_hip_ekf_predict(cddp_hip_ekf *ekf, int flags, const double *u /* B*nu */);
+int cddp_hip_ekf_get(cddp_hip_ekf *ekf, int flags, double *xh /* B*nx */, double *P /* B*nx*nx */, int32_t *info /* B */);   /* any may be NULL */
+/* A whole log in ONE launch from the object's current (xh, P): update with Y[:, 0]; then for t = 0 .. T-1 predict with U[:, t] and update
+ * with Y[:, t+1].  The outputs are the posterior after each update and that step's nis; any may be NULL.  The object is left at the
+ * final posterior.  Bitwise the loop over cddp_hip_ekf_update / cddp_hip_ekf_predict / cddp_hip_ekf_get.  T >= 0 (U may be NULL at T = 0). */
+int cddp_hip_ekf_run(cddp_hip_ekf *ekf, int flags, int T, const double *Y /* [B][T+1][ny] */, const double *U /* [B][T][nu] */,
+                     double *Xh_out /* [B][T+1][nx] */, double *P_out /* [B][T+1][nx][nx] | DIAG [B][T+1][nx] */,
+                     double *nis_out /* [B][T+1] */, int32_t *info /* [B] */);
+/* cddp_hip_mpc_run_plant with a controller that sees only y.  The true state lives in a device buffer of its own, starting at x0_true.
+ * Per step k:  y = C x_k (+ Yn[:, k]), rows formed as m above, then y = m + noise;  cddp_hip_ekf_update(y);  the equivalent of
+ * cddp_hip_mpc_advance(k == 0 ? CDDP_HIP_MPC_KEEP_PLAN : mode, (k == 0 ? 0 : flags) | CDDP_HIP_MPC_X_DEVICE, xh);  cddp_hip_solve;
+ * x_{k+1} = plant(x_k, u_0, W[:, k]) with u_0 = row 0 of the plan;  cddp_hip_ekf_predict(u_0) -- the commanded u_0, the estimator's own
+ * plant clips it;  the saturated u_0, x_{k+1}, xh_k (the posterior the solve started from), nis_k, iterations and status into the device
+ * log.  W and Yn are uploaded once; only the logs cross the bus afterwards.  X_visited[:, 0] = x0_true.  flags: those of
+ * cddp_hip_mpc_advance (CDDP_HIP_MPC_SHIFT_DUALS) and CDDP_HIP_MPC_EKF_SKIP_NAN (a NaN in Yn is a drop-out).  Bitwise the loop written out
+ * over cddp_hip_ekf_update, cddp_hip_ekf_get, cddp_hip_mpc_advance, cddp_hip_solve, cddp_hip_get_plan_head, cddp_hip_plant_step and
+ * cddp_hip_ekf_predict.  The estimator's model may differ from `plant`.  On a solve error the steps completed so far come back, as from
+ * cddp_hip_mpc_run.  The first step is an advance: the handle needs a current plan (cddp_hip_set_initial and cddp_hip_initialize or
+ * cddp_hip_solve), as cddp_hip_mpc_advance does.
+ * Refused, with nothing launched and nothing changed: everything cddp_hip_mpc_run_plant refuses; a NULL estimator or x0_true; an
+ * estimator whose nx, nu, batch or device differ from the handle's; a non-finite x0_true or W; a Yn that is not finite (NaN allowed
+ * with CDDP_HIP_MPC_EKF_SKIP_NAN). */
+enum { CDDP_HIP_MPC_EKF_SKIP_NAN = 256 };
+int cddp_hip_mpc_run_ekf(cddp_hip_handle *h, cddp_hip_plant *plant, cddp_hip_ekf *ekf, int steps, int mode, int flags,
+                         const double *x0_true /* B*nx, host */, const double *W /* B*steps*nx or NULL, host */,
+                         const double *Yn /* B*(steps+1)*ny or NULL, host; rows 0 .. steps-1 are read */,
+                         double *U_applied /* B*steps*nu */, double *X_visited /* B*(steps+1)*nx */, double *Xh_visited /* B*steps*nx */,
+                         double *nis /* B*steps */, int32_t *iterations /* B*steps */, int32_t *status /* B*steps */,
+                         cddp_hip_stats *stats_sum);
+
 /* ---- multi-GPU: the single collective of the path --------------------------------------
  * One process (or host thread) per GPU, each with its own handle over a contiguous block of the global batch; nothing
  * is exchanged during a solve.  After it, ONE RCCL all-gather collects every trajectory's 16-byte record.
